@@ -12,10 +12,11 @@ A "step" = one frame.  Inputs (raw frames, master flat, bad-pixel mask, crosstal
 coefficients, reference image, PSFs) are synthetic and resident in HBM when the timed
 region starts; every step includes the host-side overscan fits and the small device<->host
 hops of the path.  --workload selects configs[1] (calibration + LA-Cosmic) or configs[2]
-(full calibration + background mesh + satellite trail) as the timed workload instead; their
-rates are also measured briefly and attached to the headline line (other_workloads).
+(full calibration + background mesh + satellite trail) as the timed workload instead; with --full
+their rates are also measured briefly and attached to the headline line (other_workloads).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload zogy|full|calib] [--small]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload zogy|full|calib] [--small] [--full]
+                  [--dump-outputs DIR]
   N > 1: one rank per GPU (torch.distributed.run; `--gpus N` alone spawns it); every rank
   reduces its own frames (independent, no data-path collective) -> weak scaling.
 
@@ -24,11 +25,18 @@ Timing: depth + W + K + depth frames go through the frames-in-flight pipeline in
 completion of the K-th frame after it: exactly K completions with the pipeline full at both
 ends (neither its fill nor its drain inside the region; barrier + device synchronisation
 around the run).  `idle_to_idle` is the rate of all those frames from an idle device to an idle
-device, `long_run` the same steady-state measurement over 240 frames.
+device, `long_run` (--full) the same steady-state measurement over 240 frames.
 
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel and a CPU baseline.
+Prints ONE JSON line (rank 0) with the roofline of the dominant kernel, from the launches of the timed region.
+A plain run does nothing else: set-up, warm-up, the K timed steps, the result line.  Everything beside the headline
+takes `--full` (`--no-cpu` / `--no-extras` then leave the CPU baseline / the extras out): serial frames before the
+timed region (`single_frame_latency_ms`, `stage_ms_serial`, the kernels alone in `roofline`) and what follows.
 
-Beside the headline (N = 1, default run): `roofline.stages` (the calibration and full-calibration workloads),
+--dump-outputs DIR: after the timed steps, what the timed path handed its caller for the frame of the last timed step
+goes to DIR/<name>.npy (dump_outputs).  The inputs are the same from run to run for the same arguments (seeded, and
+made with deterministic algorithms), so two builds can be compared output for output.
+
+Beside the headline (N = 1, --full): `roofline.stages` (the calibration and full-calibration workloads),
 `io_inclusive.measured` = files to files through the operator's own entry -- a child `python blackbox.py --image_list`
 over 96 full-size fpacked raws, every product written, once onto the RAM disk and once onto local scratch (after an
 untimed 48-file warm-up run) --, `process_per_file` (one `python blackbox.py --image` process), `process_pool`
@@ -421,6 +429,10 @@ def run_pipeline(torch, ctx, tel, geom, raws, kw, steps, warmup, depth, lanes, p
                 for h in mark.get('prof_h', ()):
                     _lib.check(_lib.lib.bbx_profile_enable(h, 2), 'bbx_profile_enable')      # pause, keep the records
             mark['last'] = f
+            if f.idx == first + steps - 1:
+                # the frame fed in as the last timed step (frames of different lanes complete out of order: the one
+                # counted last is not the same frame in every run)
+                mark['last_timed'] = f
             if n == n_all:
                 all_done.set()
     stage = None
@@ -503,6 +515,7 @@ def run_pipeline(torch, ctx, tel, geom, raws, kw, steps, warmup, depth, lanes, p
     if mark['err'] is not None:
         raise mark['err']
     out = dict(dt=mark['t1'] - mark['t0'], dt_all=t_end - t_all0, n_all=n_all, t_stats=list(pipe.t_stats), last=mark.get('last'),
+               last_timed=mark.get('last_timed'),
                nworkers=pipe.pool.n, bytes_written=mark['bytes'], files_written=mark['files'],
                lane_fetch_wait_ms_per_frame=1e3 * (_lib.WAIT_STATS[0] - wait0[0]) / max(1, n_all), lane_fetch_waits_per_frame=(_lib.WAIT_STATS[1] - wait0[1]) / max(1, n_all),
                host_ms_per_frame=dict(lane_threads_cpu=1e3 * pipe.lane_cpu[0] / max(1, pipe.lane_cpu[2]),
@@ -824,6 +837,43 @@ def load_pmc(args):
         return None, 'PMC summary unreadable: %s' % e
 
 
+DUMP_SAMPLE = 1 << 20                    # pixels drawn from each image product by --dump-outputs (4 MB per image)
+DUMP_LIMIT = 64 << 20                    # bytes of all the files of one dump
+
+
+def dump_outputs(outdir, f):
+    """--dump-outputs: the arrays the timed path hands its caller for frame f -> outdir/<name>.npy, float32 (float64 for
+    indices and the transient table).  The image products (red, mask, and with a subtraction D, Scorr, Fpsf, Fpsferr)
+    are full frames of 446 MB each: a fixed sample of their pixels is written instead, at the flat indices of
+    sample_index.npy (seeded: the same pixels in every run).  The mini images of the background mesh (bkg_mini,
+    bkg_std_mini), the catalogue columns (cat_<COLUMN>) and the transient candidates (trans_<field>) are written whole.
+    -> {name: shape}"""
+    import torch
+    sub = f.sub or {}
+    n = f.data.numel()
+    idx = np.unique(np.random.RandomState(12345).randint(0, n, min(n, DUMP_SAMPLE)))
+    d_idx = torch.from_numpy(idx).to(f.data.device)
+    arrays = {'sample_index': idx.astype(np.float64)}
+    images = [('red', f.data), ('mask', f.mask)] + [(k, sub[k]) for k in ('D', 'Scorr', 'Fpsf', 'Fpsferr') if sub.get(k) is not None]
+    for name, t in images:
+        arrays[name] = t.reshape(-1)[d_idx].to(torch.float32).cpu().numpy()
+    for name in ('bkg_mini_new', 'bkg_std_mini_new'):
+        if sub.get(name) is not None:
+            arrays[name[:-4]] = np.asarray(sub[name], np.float32)
+    for col, a in (sub.get('catalog') or {}).items():
+        arrays['cat_' + col] = np.asarray(a, np.float32)
+    if 'transients' in sub:
+        for k in ('y', 'x', 'scorr', 'fpsf', 'fpsferr'):
+            arrays['trans_' + k] = np.array([t[k] for t in sub['transients']], np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError('--dump-outputs: %d bytes, more than the %d allowed' % (total, DUMP_LIMIT))
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` outside torch.distributed.run: start the N ranks as a child
     launcher (fresh processes; nothing in this process has touched the GPU) and pass its exit code on"""
@@ -843,8 +893,14 @@ def main():
                     help='zogy: reduce + ZOGY + photometry (headline, configs[4] per frame); full: configs[2]; calib: configs[1]')
     ap.add_argument('--raw', default='u16', choices=['u16', 'f32'])
     ap.add_argument('--small', action='store_true', help='reduced geometry (debug)')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the other workloads and the I/O-inclusive figures')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline as well: serial frames (latency, stage times, kernels alone), the '
+                         'child-process runs, long_run, the other workloads, the I/O-inclusive figures, the CPU baseline')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: without the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the other workloads and the I/O-inclusive figures')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed for its last step to DIR/<name>.npy (dump_outputs); the timed '
+                         'pipeline then keeps every frame\'s device products for its caller, as blackbox.py runs it')
     ap.add_argument('--depth', type=int, default=None, help='frames in flight')
     ap.add_argument('--workers', type=int, default=None, help='host fit worker processes')
     ap.add_argument('--lanes', type=int, default=None, help='stage-C lanes (context + stream + issuing thread) per GPU')
@@ -855,6 +911,10 @@ def main():
     ap.add_argument('--io-simple', action='store_true', help='with --io-only: one files-to-files run on the RAM disk (profiling)')
     ap.add_argument('--psf-size', type=int, default=49, help='side of the PSF stamps of the ZOGY stage (SURVEY 8d: 49)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    with_extras = args.full and not args.no_extras
+    with_cpu = args.full and not args.no_cpu
     if args.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
 
@@ -890,6 +950,9 @@ def main():
     lanes = args.lanes or {'zogy': 6, 'full': 6, 'calib': 8}[wl]          # (calib: 4 / 6 / 8 / 10 lanes -> 1180 / 1230 / 1370 / 1210 frames/s)
     depth = args.depth or {'zogy': 16, 'full': 18, 'calib': 24}[wl]
     seed = 1000 * 4 + rank
+    # the same inputs in every run: the star fields are summed by index_add_, whose atomic adds land in any order unless
+    # torch uses its deterministic algorithms (for the synthesis only: the product's own torch calls stay as they are)
+    torch.use_deterministic_algorithms(True)
     # the scene follows the PSF model ZOGY is handed (zogy_psf_field): star shapes per sub-image, reference fluxes / fratio
     raw, flat, bpm, ex = synth_frame_device(torch, dev, ysz, xsz, os_y, os_x, seed, args.raw, extras=True, ntrans=50,
                                             psf_field=zogy_psf_field(2 * ysz // size, 8 * xsz // size, size))
@@ -897,7 +960,7 @@ def main():
     geom = R.geometry(raw.shape, ysz, xsz)
     tel = 'ML1'
     cpu_full = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.small and args.raw == 'u16' and not (args.io_only or args.proc_only):
+    if rank == 0 and world == 1 and with_cpu and not args.small and args.raw == 'u16' and not (args.io_only or args.proc_only):
         # the frame of this run for the CPU baseline's whole-frame check (host copies on the RAM disk, removed after use)
         cpu_full = os.path.join('/dev/shm' if os.path.isdir('/dev/shm') else '/tmp', 'bbx_cpu_full_%d_' % os.getpid())
         np.save(cpu_full + 'raw.npy', raw.cpu().numpy()); np.save(cpu_full + 'flat.npy', flat.cpu().numpy()); np.save(cpu_full + 'bpm.npy', bpm.cpu().numpy())
@@ -910,6 +973,7 @@ def main():
     for _ in range(nbuf - 1):
         r = (raw.to(torch.float32) + 2.0 * torch.randn(raw.shape, device=dev, generator=g)).round().clamp(0, 65535)
         raws.append(r.to(torch.int32).to(torch.uint16).contiguous() if args.raw == 'u16' else r.contiguous())
+    torch.use_deterministic_algorithms(False)
     rs = np.random.RandomState(0)
     coeffs = np.zeros((16, 16)); coeffs[~np.eye(16, dtype=bool)] = rs.uniform(0, 2e-4, 240)
     S = args.psf_size
@@ -948,13 +1012,13 @@ def main():
     # done nothing on the GPU but make the synthetic inputs: started behind its own pipelines (which leave their queues,
     # workspaces and a busy card behind) the first list run measured 30-49 frames/s in four of seven default runs, 65-79 here.
     early = {}
-    if rank == 0 and world == 1 and not args.no_extras and wl == 'zogy' and not args.small:
+    if rank == 0 and world == 1 and with_extras and wl == 'zogy' and not args.small:
         t_e = time.perf_counter()
         early['process_per_file'] = process_cold(torch, ctx, raw, flat, bpm, ref, ref_mask, coeffs, sub_kw, box, raws=raws, list_frames=96)
         sys.stderr.write('[bench] process_per_file + image_list: %.1f s\n' % (time.perf_counter() - t_e)); sys.stderr.flush()
-    # ---- serial reference run of one frame (stage breakdown + isolated kernel timings; untimed) --
+    # ---- serial reference run of one frame (stage breakdown + isolated kernel timings; untimed; --full) --
     from blackbox_amd import zogy as G
-    stage_ms = {}
+    stage_ms, serial, iso_ms = {}, {}, None
 
     def frame_serial(with_sub):
         header, hm = {}, {}
@@ -981,34 +1045,41 @@ def main():
         ctx.sync()
         return ev, st, res
 
-    frame_serial(wl == 'zogy')
-    _lib.check(_lib.lib.bbx_profile_enable(ctx.h, 1), 'bbx_profile_enable')
-    nser = 3
-    for _ in range(nser):
+    if args.full:
         frame_serial(wl == 'zogy')
-    iso_ms = (C.c_double * NSL)()
-    iso_calls = (C.c_int32 * NSL)()
-    _lib.check(_lib.lib.bbx_profile_read(ctx.h, iso_ms, iso_calls, NSL), 'bbx_profile_read', ctx.h)
-    _lib.check(_lib.lib.bbx_profile_enable(ctx.h, 0), 'bbx_profile_enable')
-    t0 = time.perf_counter()
-    ev, st, res = frame_serial(wl == 'zogy')
-    latency_ms = 1e3 * (time.perf_counter() - t0)
-    for i, n in enumerate(['overscan(stats+host fits)', 'calibrate', 'mask_finish', 'lacosmic', 'xtalk+sat+counts+edge_fill',
-                           'optimal_subtraction']):
-        stage_ms[n] = ev[i].elapsed_time(ev[i + 1])
-    stats = st.cpu().numpy().tolist()
-    sub_info = None
-    if res is not None:
-        sub_info = dict(ntransients=len(res['transients']), ncatalog=int(len(res['catalog']['X_POS'])) if res['catalog'] else 0,
-                        scorr_median=res['header_trans']['Z-SCMED'][0], scorr_std=res['header_trans']['Z-SCSTD'][0],
-                        injected=len(ex['transients']))
-    del res
-    torch.cuda.empty_cache()
+        _lib.check(_lib.lib.bbx_profile_enable(ctx.h, 1), 'bbx_profile_enable')
+        nser = 3
+        for _ in range(nser):
+            frame_serial(wl == 'zogy')
+        iso_ms = (C.c_double * NSL)()
+        iso_calls = (C.c_int32 * NSL)()
+        _lib.check(_lib.lib.bbx_profile_read(ctx.h, iso_ms, iso_calls, NSL), 'bbx_profile_read', ctx.h)
+        _lib.check(_lib.lib.bbx_profile_enable(ctx.h, 0), 'bbx_profile_enable')
+        t0 = time.perf_counter()
+        ev, st, res = frame_serial(wl == 'zogy')
+        latency_ms = 1e3 * (time.perf_counter() - t0)
+        for i, n in enumerate(['overscan(stats+host fits)', 'calibrate', 'mask_finish', 'lacosmic', 'xtalk+sat+counts+edge_fill',
+                               'optimal_subtraction']):
+            stage_ms[n] = ev[i].elapsed_time(ev[i + 1])
+        stats = st.cpu().numpy().tolist()
+        sub_info = None
+        if res is not None:
+            sub_info = dict(ntransients=len(res['transients']), ncatalog=int(len(res['catalog']['X_POS'])) if res['catalog'] else 0,
+                            scorr_median=res['header_trans']['Z-SCMED'][0], scorr_std=res['header_trans']['Z-SCSTD'][0],
+                            injected=len(ex['transients']))
+        serial = dict(single_frame_latency_ms=latency_ms, stage_ms_serial=stage_ms, lacosmic_stats=stats, subtraction=sub_info)
+        del res
+        torch.cuda.empty_cache()
 
     # ---- timed region ----------------------------------------------------------------------------
-    r = run_pipeline(torch, ctx, tel, geom, raws, kws[wl], args.steps, args.warmup, depth, lanes, pool, barrier, prof_ctx=ctx)
+    kw_timed = dict(kws[wl], keep_outputs=True) if args.dump_outputs else kws[wl]
+    r = run_pipeline(torch, ctx, tel, geom, raws, kw_timed, args.steps, args.warmup, depth, lanes, pool, barrier, prof_ctx=ctx)
     dt, dt_all = r['dt'], r['dt_all']
     ms_tot, calls = r['prof']
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, r['last_timed'])
+    del r['last_timed'], r['last']                              # (with --dump-outputs they hold device products)
     if world > 1:
         t = torch.tensor([dt, dt_all], device=dev if backend == 'nccl' else 'cpu', dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -1042,7 +1113,8 @@ def main():
         }
         zogy_kernels = ('k_psf_rowdft', 'k_psf_cols', 'k_psf_rows', 'k_img_rows', 'k_img_cols', 'k_var_cols', 'k_final_rows')
         zogy_io_model = int(4 * 4 * nsub * L * L + 4 * 4 * N)     # 4 inputs read with the tile overlap, 4 outputs written
-        iso = {k: (iso_ms[sl] / max(1, iso_calls[sl]), by, iso_calls[sl]) for k, (sl, by) in kern.items() if iso_calls[sl]}
+        iso = {k: (iso_ms[sl] / max(1, iso_calls[sl]), by, iso_calls[sl]) for k, (sl, by) in kern.items()
+               if iso_ms is not None and iso_calls[sl]}             # (the kernels alone: serial frames, --full)
         live = {k: (ms_tot[sl] / max(1, calls[sl]), by, calls[sl]) for k, (sl, by) in kern.items() if calls[sl]}
 
         def gbs(t):
@@ -1061,13 +1133,12 @@ def main():
             frame_bytes += int(9 * N + 6 * N + 8 * N + 9 * N)                                     # configs[2]
         if wl == 'zogy':
             frame_bytes += int(zogy_io_model + 12000 * S * S * 12)                                # configs[4]
-        if wl == 'zogy' and all(k in live for k in zogy_kernels) and all(k in iso for k in zogy_kernels):
+        if wl == 'zogy' and all(k in live for k in zogy_kernels):
             # the dominant launch group of the headline workload: bbx_zogy_frame = 6 launches per frame (one library call).
             # achieved = SURVEY 8d algorithmic bytes of the stage (inputs once with the tile overlap + outputs once)
             # / the summed duration of its launches in the timed region (HIP events stamped by the launches themselves,
             # lane 0's stream)
             zms = sum(live[k][0] * per_frame[k] for k in zogy_kernels)
-            zms_iso = sum(iso[k][0] * per_frame[k] for k in zogy_kernels)
             moved = int(sum(live[k][1] * per_frame[k] for k in zogy_kernels))
             roof = dict(bound='hbm', kernel='bbx_zogy_frame (launch group: k_psf_rowdft, k_psf_cols, k_psf_rows, k_img_rows, k_img_cols, '
                                             'k_var_cols, k_final_rows)',
@@ -1076,13 +1147,17 @@ def main():
                         bytes_per_launch=zogy_io_model, traffic=None,
                         bytes_model='SURVEY 8d: 4 inputs (new, ref, 2 sigma images) read once with the tile overlap (L/size)^2 + '
                                     '4 outputs (D, Scorr, Fpsf, Fpsferr) written once = 34N',
-                        alone=dict(avg_launch_ms=zms_iso, achieved=zogy_io_model / (zms_iso * 1e-3) / 1e9,
-                                   frac=zogy_io_model / (zms_iso * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                   note='serial frames before the timed region: the group alone on the GPU'),
                         moved_bytes_by_design=moved, achieved_moved=moved / (zms * 1e-3) / 1e9,
                         frac_moved=moved / (zms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                        kernels={k: dict(kdict(live[k]), alone_ms=iso[k][0], per_frame=per_frame[k]) for k in zogy_kernels},
+                        kernels={k: dict(kdict(live[k]), per_frame=per_frame[k]) for k in zogy_kernels},
                         others={k: kdict(live[k]) for k in live if k not in zogy_kernels})
+            if all(k in iso for k in zogy_kernels):
+                zms_iso = sum(iso[k][0] * per_frame[k] for k in zogy_kernels)
+                roof['alone'] = dict(avg_launch_ms=zms_iso, achieved=zogy_io_model / (zms_iso * 1e-3) / 1e9,
+                                     frac=zogy_io_model / (zms_iso * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                     note='serial frames before the timed region: the group alone on the GPU')
+                for k in zogy_kernels:
+                    roof['kernels'][k]['alone_ms'] = iso[k][0]
             if pmc is not None and all(k in pmc for k in zogy_kernels):
                 roof['traffic'] = int(sum(pmc[k]['traffic_bytes_per_launch'] * per_frame[k] for k in zogy_kernels))
                 roof['traffic_per_kernel'] = {k: pmc[k]['traffic_bytes_per_launch'] for k in zogy_kernels}
@@ -1131,9 +1206,9 @@ def main():
                                      note='all frames of the run from an idle device to an idle device (pipeline fill and drain included)'),
                    pipeline_wall_ms_per_frame=dict(zip(['stageA_stats', 'stageB_host_fits', 'stageC_device'],
                                                        [1e3 * t / max(1, r['t_stats'][3]) for t in r['t_stats'][:3]])),
-                   host_ms_per_frame=r['host_ms_per_frame'],
-                   single_frame_latency_ms=latency_ms, stage_ms_serial=stage_ms, lacosmic_stats=stats, subtraction=sub_info,
-                   roofline=roof)
+                   host_ms_per_frame=r['host_ms_per_frame'], **serial, roofline=roof)
+        if dumped is not None:
+            out['dumped_outputs'] = dict(dir=args.dump_outputs, arrays=dumped)
     # ---- the other workloads, briefly, and the I/O-inclusive figures (not part of `value`) ---------
     t_sec = [time.perf_counter()]
 
@@ -1143,7 +1218,7 @@ def main():
         sys.stderr.write('[bench] %s: %.1f s\n' % (name, now - t_sec[0]))
         sys.stderr.flush()
         t_sec[0] = now
-    if world == 1 and not args.no_extras:
+    if world == 1 and with_extras:
         # the same steady-state measurement over a long run (the headline's K frames are few), first of the extras: behind
         # the other workloads' pipelines (more lanes, more frames in flight) the same 240 frames measure 8-10 % lower
         r3 = run_pipeline(torch, ctx, tel, geom, raws, kws[wl], 240, 4, depth, lanes, pool, barrier)
@@ -1204,7 +1279,7 @@ def main():
             out['io_inclusive']['measured'] = measure_io(torch, ctx, tel, geom, raws, kws[wl], depth, lanes, pool, barrier, args, section)
     pool.close()
     if rank == 0:
-        if not args.no_cpu and world == 1:                           # (the CPU baseline: at N = 1 only)
+        if with_cpu and world == 1:                                  # (the CPU baseline: at N = 1 only)
             full_path = None
             if not args.small and world == 1 and cpu_full is not None:
                 full_path = cpu_full

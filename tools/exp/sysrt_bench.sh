@@ -8,7 +8,7 @@ for rep in 1 2; do
 for v in bundled system; do
   if [ $v = system ]; then e=(LD_PRELOAD=$PRE); else e=(A=1); fi
   env "${e[@]}" timeout -k 10 300 python bench.py --io-only --io-simple --steps 60 > /tmp/io.json 2>/tmp/io.err
-  env "${e[@]}" timeout -k 10 200 python bench.py --steps 100 --warmup 10 --no-extras --no-cpu > /tmp/b.json 2>/tmp/b.err
+  env "${e[@]}" timeout -k 10 200 python bench.py --steps 100 --warmup 10 --full --no-extras --no-cpu > /tmp/b.json 2>/tmp/b.err
   python3 - "$v" >> $out <<PY
 import json,sys
 try:
