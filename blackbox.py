@@ -11,8 +11,12 @@ zogy.optimal_subtraction that the hot path covers (set_blackbox.py:157-164): `_r
 `_red_trans` (+ `_red_trans_hdr`).  The reference image, its mask and the PSFs are explicit
 inputs (--ref, --ref_mask, --psf_new, --psf_ref), like the masters (--mflat, --mbias, --bpm):
 their selection / creation (reference building, PSFEx, astrometry) is orchestration.
-Flags of the reference that concern orchestration only (night mode, dates, master creation)
-are accepted and ignored with a warning.  With WORLD_SIZE > 1 (torch.distributed.run) every
+`--master_date D --red_dir R --master_dir M` makes the masters of the evening date D (or of a file
+of dates) from the reduced bias / dark / flat frames under R (blackbox.py:617-782, create_masters;
+blackbox_amd/masters.py): one line per master, its path or None; the exit status is non-zero when
+a master failed.  Given --image / --image_list as well, those are reduced afterwards as usual (the
+reference stops after the masters).  Flags of the reference that concern orchestration only
+(night mode, dates) are accepted and ignored with a warning.  With WORLD_SIZE > 1 (torch.distributed.run) every
 rank takes every world-th file of --image_list on its own GPU; an --image_list of object
 frames runs through the frames-in-flight pipeline (blackbox_amd.pipeline.FramePipeline).
 """
@@ -131,7 +135,7 @@ def _rebuild_wrapexception(args, formatted):
 # configure() stores it in this process and in the environment, so that spawned pool workers -- which import this
 # module afresh and must create their GPU context themselves -- find it.
 _ENV_KEY = 'BBX_BLACKBOX_ARGV'
-_STATE = {'argv': None, 'reducer': None}
+_STATE = {'argv': None, 'reducer': None, 'exit_status': 0}
 
 
 def configure(argv):
@@ -421,8 +425,8 @@ class Reducer:
         header['BUNIT'] = ('e-', 'pixel values are in electrons')
         if imgtype == 'flat' and R.hval(header, 'OS-P'):
             from blackbox_amd import flatstats
-            flatstats.get_flatstats(self.ctx, data, header, mask, self.tel, ysize_chan=self.args.ysize_chan,
-                                    xsize_chan=self.args.xsize_chan)
+            flatstats.get_flatstats(self.ctx, data, header, mask, self.tel, statsec=self.args.flat_norm_sec,
+                                    ysize_chan=self.args.ysize_chan, xsize_chan=self.args.xsize_chan)
         self.bookkeeping(header, time.time())
         qc.run_qc_check(header, self.tel)
         fits_out = fits_out.replace('_red.fits', '.fits')       # calibration frames keep their plain name
@@ -877,10 +881,10 @@ def reduce_list_in_processes(argv, files, nproc):
         if skip:
             skip = False
             continue
-        if a in ('--image_list', '--list_procs', '--image'):
+        if a in ('--image_list', '--list_procs', '--image', '--master_date'):      # (the masters are made by the parent)
             skip = True
             continue
-        if a.startswith('--image_list=') or a.startswith('--list_procs=') or a.startswith('--image='):
+        if a.startswith(('--image_list=', '--list_procs=', '--image=', '--master_date=')):
             continue
         base.append(a)
     td = tempfile.mkdtemp(prefix='bbx_list_')
@@ -931,6 +935,45 @@ def reduce_list_in_processes(argv, files, nproc):
     return res
 
 
+def section(v):
+    """'y0:y1,x0:x1' (0-based Python slices of the y and x axes) -> (slice, slice)"""
+    try:
+        parts = [[int(p) for p in s.split(':')] for s in v.split(',')]
+        if len(parts) != 2 or any(len(p) != 2 or p[0] < 0 or p[1] <= p[0] for p in parts):
+            raise ValueError(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError('section y0:y1,x0:x1 expected (0-based, y0 < y1, x0 < x1), got {!r}'.format(v))
+    return slice(*parts[0]), slice(*parts[1])
+
+
+def make_masters(args, argv):
+    """--master_date: the masters of the evening date(s) (masters.create_masters, blackbox.py:617-782), one line per
+    master printed (its path, or None).  A master that failed sets the exit status; one skipped for a reason the
+    reference skips it too (too few frames, all too old) does not.  With --nproc > 1 the masters are spread over
+    pool_func's spawned workers, one GPU context each.  -> [path or None]"""
+    from blackbox_amd import masters
+    kw = dict(tel=args.telescope, imgtypes=args.imgtypes, filters=args.filters, bpm=args.bpm,
+              flat_norm_sec=args.flat_norm_sec, ysize_chan=args.ysize_chan, xsize_chan=args.xsize_chan,
+              fpack=bool(args.fpack))
+    if args.nproc > 1:
+        configure(argv)
+        res = masters.create_masters(args.master_date, args.red_dir, args.master_dir,
+                                     pool=lambda func, items: pool_func(func, items, nproc=args.nproc), **kw)
+    else:
+        from blackbox_amd import farm, reduce as R
+        ctx = R.Context(farm.rank_world()[2])
+        try:
+            res = masters.create_masters(args.master_date, args.red_dir, args.master_dir, ctx=ctx, **kw)
+        finally:
+            ctx.close()
+    for name, path, err in res:
+        print(path)
+        if err is not None:
+            log.error('master %s failed: %s', name, err)
+            _STATE['exit_status'] = 1
+    return [path for _, path, _ in res]
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description='BlackBOX per-image reduction on MI355X')
     ap.add_argument('--telescope', type=str, default='ML1')
@@ -946,7 +989,11 @@ def build_parser():
     ap.add_argument('--cat_extract', type=str2bool, default=False)
     ap.add_argument('--trans_extract', type=str2bool, default=False)
     ap.add_argument('--force_reproc_new', type=str2bool, default=False)
-    ap.add_argument('--master_date', type=str, default=None)
+    ap.add_argument('--master_date', type=str, default=None,
+                    help='make the masters of this evening date yyyymmdd, or of the dates in this file (one per line, '
+                         'optionally followed by the flat filters), from the frames under --red_dir')
+    ap.add_argument('--master_dir', type=str, default=None,
+                    help='--master_date: root of the masters (<master_dir>/<yyyy/mm/dd>/<imgtype>/)')
     ap.add_argument('--name_genlog', type=str, default=None)
     ap.add_argument('--keep_tmp', type=str2bool, default=None)
     # explicit calibration inputs (the date-based master selection of master_prep is orchestration)
@@ -971,6 +1018,8 @@ def build_parser():
     ap.add_argument('--zogy_dx', type=float, default=0.0, help='[pix] astrometric scatter in x (Z-DXSTD)')
     ap.add_argument('--zogy_dy', type=float, default=0.0)
     ap.add_argument('--subimage_size', type=int, default=None)
+    ap.add_argument('--flat_norm_sec', type=section, default=None,
+                    help='y0:y1,x0:x1: flat normalisation / statistics section (default set_bb.flat_norm_sec of the telescope)')
     ap.add_argument('--subimage_border', type=int, default=None)
     ap.add_argument('--bkg_boxsize', type=int, default=None)
     ap.add_argument('--zeropoint', type=float, default=None,
@@ -987,17 +1036,30 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(argv)
     logging.basicConfig(level='INFO', format='%(asctime)s [%(levelname)s, %(process)s] %(message)s')
-    for flag in ('date', 'read_path', 'imgtypes', 'filters', 'master_date', 'name_genlog'):
+    _STATE['exit_status'] = 0
+    for flag in ('date', 'read_path', 'name_genlog') + (() if args.master_date else ('imgtypes', 'filters')):
         if getattr(args, flag):
             log.warning('--%s concerns orchestration and is ignored by the hot-path build', flag)
     if args.mode != 'day':
         log.warning('night mode (watchdog) is out of scope; running the given files once')
+    if args.master_date:
+        if not (args.red_dir and args.master_dir):
+            ap.error('--master_date needs --red_dir (the reduced calibration frames) and --master_dir')
+        from blackbox_amd import masters
+        try:
+            masters.master_dates(args.master_date)
+        except ValueError as e:
+            ap.error(str(e))
     files = []
     if args.image:
         files.append(args.image)
     if args.image_list:
         with open(args.image_list) as f:
             files += [ln.strip() for ln in f if ln.strip()]
+    if args.master_date:
+        made = make_masters(args, argv)
+        if not files:
+            return made
     if not files:
         ap.error('--image or --image_list required')
     tel = telescope_of(args, files[0])
@@ -1048,4 +1110,5 @@ if __name__ == '__main__':
     sys.stdout.flush()
     sys.stderr.flush()
     if os.environ.get('BBX_FAST_EXIT', '1') != '0':
-        os._exit(0)
+        os._exit(_STATE['exit_status'])
+    sys.exit(_STATE['exit_status'])

@@ -317,7 +317,12 @@ def funpack_image(ctx, path, ext=None):
     file): RICE_1, tiles = whole rows, integer images (BITPIX 8/16/32; 16 with BZERO 32768 ->
     uint16) and float images quantised with SUBTRACTIVE_DITHER_1; rows in the
     GZIP_COMPRESSED_DATA column are inflated on the host.  -> (device tensor, header dict)"""
-    import gzip
+    return funpack_decode(ctx, funpack_read(path, ext))
+
+
+def funpack_read(path, ext=None):
+    """the host half of funpack_image: the file read and its compressed-image HDU located, no GPU call (reader
+    threads run it while the device decodes the previous file) -> (path, header, table rows, heap)"""
     hv = fitsio._hv
     hdus = fitsio.read_hdus(path)
     cand = [i for i, (h, d) in enumerate(hdus) if hv(h, 'ZIMAGE', False) is True] if ext is None else [ext]
@@ -325,6 +330,14 @@ def funpack_image(ctx, path, ext=None):
         raise ValueError('{}: no tile-compressed image extension'.format(path))
     h, table = hdus[cand[0]]
     heap = h.pop('__heap__', np.zeros(0, np.uint8))
+    return path, h, table, heap
+
+
+def funpack_decode(ctx, parts):
+    """the device half of funpack_image: funpack_read's result decoded (bbx_funpack_tiles) -> (device tensor, header)"""
+    import gzip
+    hv = fitsio._hv
+    path, h, table, heap = parts
     if str(hv(h, 'ZCMPTYPE')).strip() not in ('RICE_1', 'RICE_ONE'):
         raise ValueError('compression {} not supported (RICE_1 only)'.format(hv(h, 'ZCMPTYPE')))
     ny, nx, zbitpix = int(hv(h, 'ZNAXIS2')), int(hv(h, 'ZNAXIS1')), int(hv(h, 'ZBITPIX'))

@@ -566,9 +566,15 @@ def count_objects(ctx, data_mask, bit):
 
 def image_to_device(ctx, path, dtype):
     """a FITS image (master frame, reference image, mask) -> device tensor of [dtype].  float32 and uint8 files go up as
-    their bytes, float32 words are put into host order on the device (bbx_be32); anything else is converted on the host"""
+    their bytes, float32 words are put into host order on the device (bbx_be32); anything else is converted on the host.
+    A tile-compressed file (.fz: the form the reference keeps its masters in) is decoded on the device (fpack.funpack_image)"""
     from . import fitsio
-    got = fitsio.read_image_file_order(path) if str(path).endswith(('.fits', '.fit')) else None
+    if str(path).endswith('.fz'):
+        from . import fpack
+        t, _ = fpack.funpack_image(ctx, path)
+        want = torch.from_numpy(np.zeros(0, dtype)).dtype
+        return t if t.dtype == want else t.to(want)
+    got =fitsio.read_image_file_order(path) if str(path).endswith(('.fits', '.fit')) else None
     if got is not None:
         data = got[0]
         if data.dtype == np.dtype('>f4') and np.dtype(dtype) == np.float32:

@@ -13,6 +13,10 @@ detect_sats = True
 correct_nonlin = False
 voscan_poldeg = 3
 ncal_max = {'bias': 20, 'dark': 20, 'flat': 15}
+# master frames (set_blackbox.py:47, 331): days either side of the evening date searched for
+# reduced calibration frames; flats taken in the evening (or just after midnight UT) left out
+cal_window = {'bias': 3, 'dark': 3, 'flat': 7}
+flat_reject_eve = {'ML': False, 'BG': True}
 
 # ---- LA-Cosmic (set_blackbox.py:211-218) ---------------------------------------
 sigclip = {'ML1': 15, 'BG': 20}
@@ -67,8 +71,8 @@ subimage_size = 1320
 subimage_border = 40
 transient_nsigma = 6
 
-# calibration files (explicit paths; the date-based master selection of
-# master_prep, blackbox.py:4625-4905, is orchestration and out of scope)
+# calibration files of a reduction (explicit paths; the date-based master selection
+# of master_prep, blackbox.py:4625-4905, is blackbox_amd.masters, run by --master_date)
 bad_pixel_mask = None      # path containing 'bpm' -> 'bpm_{filt}' (blackbox.py:4386)
 crosstalk_file = None
 master_flat = None
