@@ -24,6 +24,7 @@ import argparse
 import logging
 import os
 import sys
+import threading
 import time
 
 import numpy as np
@@ -56,7 +57,6 @@ def _start_sampler(path):
         return None
     import atexit
     import collections
-    import threading
     counts = collections.Counter()
     stop = threading.Event()
 
@@ -210,8 +210,7 @@ def telescope_of(args, filename=None):
 
 def outname(header, tel, red_dir):
     """{tel}_{yyyymmdd}_{hhmmss}_red.fits from DATE-OBS (blackbox.py:1004-1022, 1166-1184)"""
-    from blackbox_amd.reduce import hval
-    date_obs = str(hval(header, 'DATE-OBS')) if 'DATE-OBS' in header else time.strftime('%Y-%m-%dT%H:%M:%S')
+    date_obs = str(_hval(header, 'DATE-OBS', time.strftime('%Y-%m-%dT%H:%M:%S')))
     d, t = date_obs.split('T')[0].replace('-', ''), date_obs.split('T')[-1].split('.')[0].replace(':', '')
     return os.path.join(red_dir, '{}_{}_{}_red.fits'.format(tel, d, t))
 
@@ -222,6 +221,53 @@ def _base(p):
 
 def _stem(p):
     return os.path.basename(p).split('.fits')[0] if p else 'None'
+
+
+def _frame_header(h):
+    """the header of a raw frame as a dict, without the keywords that describe its stored pixels"""
+    header = dict(h)
+    for k in ('BZERO', 'BSCALE', 'BITPIX', 'NAXIS', 'NAXIS1', 'NAXIS2', 'SIMPLE', 'EXTEND'):
+        header.pop(k, None)
+    return header
+
+
+def _hval(header, key, default):
+    from blackbox_amd.reduce import hval
+    return hval(header, key) if key in header else default
+
+
+def imgtype_of(header):
+    return str(_hval(header, 'IMAGETYP', 'object')).lower()
+
+
+def exptime_of(header):
+    return _hval(header, 'EXPTIME', 1.0)
+
+
+class _Products:
+    """where the products of one frame go.  Direct (staged=None): each is written at once.  Staged (a frame of the list run
+    whose images [staged] the output stage is writing, compressed on its lane): such an image only hands its header over;
+    the small products (mini image, table, header file) are noted for one catalogs.write_small_products in a worker process"""
+
+    def __init__(self, reducer, staged=None):
+        self.reducer, self.staged = reducer, None if staged is None else set(staged)
+        self.headers, self.deferred = {}, []          # staged name -> its header (the names the frame keeps); [(kind, args)]
+
+    def stages(self, path):
+        return self.staged is not None and (path + '.fz') in self.staged
+
+    def image(self, path, img, header):
+        if not self.stages(path):
+            return self.reducer.write_image(path, img, header)
+        # the output stage is writing this image already: it only waits for the header
+        self.headers[path + '.fz'] = dict(header)
+        return path + '.fz'
+
+    def small(self, kind, *args):
+        if self.staged is not None:
+            return self.deferred.append((kind, args))
+        from blackbox_amd import catalogs
+        catalogs.write_small_products([(kind, args)])
 
 
 class Reducer:
@@ -241,7 +287,6 @@ class Reducer:
         _mark('gpu_context')
         self.tel = tel
         self.args = args
-        dev = self.ctx.device
 
         def load(path, dtype, what):
             """a master that cannot be read is not applied: <X>-P False (blackbox.py:1674-1699, 1820-1846)"""
@@ -347,7 +392,7 @@ class Reducer:
 
     def read_raw(self, filename):
         """-> (raw device tensor, header dict)"""
-        R, torch, fitsio = self.R, self.torch, self.fitsio
+        torch, fitsio = self.torch, self.fitsio
         if filename.endswith('.fz'):
             # fpacked raw frame (the reference's usual input): the compressed bytes go to the GPU
             # and are decoded there
@@ -360,10 +405,7 @@ class Reducer:
             if raw.dtype not in (np.uint16, np.float32):
                 raw = raw.astype(np.float32)
             d_raw = torch.from_numpy(np.ascontiguousarray(raw)).to(self.ctx.device)
-        header = dict(hraw)
-        for k in ('BZERO', 'BSCALE', 'BITPIX', 'NAXIS', 'NAXIS1', 'NAXIS2', 'SIMPLE', 'EXTEND'):
-            header.pop(k, None)
-        return d_raw, header
+        return d_raw, _frame_header(hraw)
 
     def names(self, header):
         red_dir = self.args.red_dir or '.'
@@ -388,8 +430,7 @@ class Reducer:
         os.makedirs(red_dir, exist_ok=True)
         fh = self.open_image_log(fits_out)
         try:
-            exptime = R.hval(header, 'EXPTIME') if 'EXPTIME' in header else 1.0
-            imgtype = str(R.hval(header, 'IMAGETYP')).lower() if 'IMAGETYP' in header else 'object'
+            exptime, imgtype = exptime_of(header), imgtype_of(header)
             data, mask, header, hm = R.reduce_object(
                 self.ctx, d_raw, header, self.tel, mflat=self.mflat, mbias=self.mbias, bpm=self.bpm,
                 xtalk_coeffs=self.xtalk, exptime=exptime, ysize_chan=self.args.ysize_chan,
@@ -397,7 +438,7 @@ class Reducer:
             _mark('reduced')
             if imgtype != 'object':
                 return self.finish_calibration_frame(data, mask, header, imgtype, fits_out)
-            return self.finish_object(filename, data, mask, header, hm, fits_out, t0)
+            return self.finish_object(filename, data, mask, header, hm, fits_out, t0, _Products(self))
         finally:
             self.close_image_log(fh)
 
@@ -462,7 +503,7 @@ class Reducer:
         header['FRRATIO'] = ('None', 'fringe ratio (science/fringe map) applied')
 
     # ---- object frames -------------------------------------------------------------------------
-    def finish_object(self, filename, data, mask, header, hm, fits_out, t0, sub_result=None):
+    def finish_object(self, filename, data, mask, header, hm, fits_out, t0, products, sub_result=None):
         R, fitsio = self.R, self.fitsio
         from blackbox_amd import qc
         header['BUNIT'] = ('e-', 'pixel values are in electrons')
@@ -477,8 +518,8 @@ class Reducer:
         if qc_flag == 'red':
             # red flag: dummy catalogues, no subtraction (blackbox.py:2015-2046)
             log.error('red QC flag in image %s; making dummy catalogs and returning', fits_out)
-            written = self.write_image(fits_out, data, header)
-            self.write_image(fits_out.replace('_red', '_mask'), mask, hm)
+            written = products.image(fits_out, data, header)
+            products.image(fits_out.replace('_red', '_mask'), mask, hm)
             fitsio.write_header(base + '_hdr.fits', header)
             if self.sub is not None:
                 qc.run_qc_check(header, self.tel, cat_type='new', cat_dummy=base + '_cat.fits', check_key_type='full')
@@ -486,46 +527,28 @@ class Reducer:
                 qc.run_qc_check(htrans, self.tel, cat_type='trans', cat_dummy=base + '_trans.fits', check_key_type='trans')
             return written
         if self.sub is not None:
-            self.subtract_and_write(data, mask, header, base, sub_result)
-        written = self.write_image(fits_out, data, header)
-        self.write_image(fits_out.replace('_red', '_mask'), mask, hm)
-        self._small('header', base + '_hdr.fits', dict(header))               # update_imcathead(create_hdrfile=True), 2011
+            self.subtract_and_write(data, mask, header, base, products, sub_result)
+        written = products.image(fits_out, data, header)
+        products.image(fits_out.replace('_red', '_mask'), mask, hm)
+        products.small('header', base + '_hdr.fits', dict(header))              # update_imcathead(create_hdrfile=True), 2011
         log.info('reduced %s -> %s in %.2f s', filename, written, time.time() - t0)
         _mark('products_written')
         return written
 
-    def _small(self, kind, *args):
-        """a small product (mini image, table, header file): written at once -- or, for a frame of the list run whose
-        images the output stage is writing, noted for one call of catalogs.write_small_products in a worker process"""
-        staged = getattr(self, '_staged', None)
-        if staged is not None and staged.get('deferred') is not None:
-            staged['deferred'].append((kind, args))
-            return
-        from blackbox_amd import catalogs
-        catalogs.write_small_products([(kind, args)])
-
     def write_image(self, path, img, header):
-        staged = getattr(self, '_staged', None)
-        if staged is not None and (path + '.fz') in staged['names']:
-            # the output stage is writing this image already (compressed on its lane): it only waits for the header
-            staged['headers'][path + '.fz'] = dict(header)
-            staged['wanted'].add(path + '.fz')
-            return path + '.fz'
-        if self.args.fpack:
+        if self.args.fpack and self.torch.is_tensor(img):
             # products leave the GPU tile-compressed (reference: fpack of the files kept,
             # copy_files2keep 4033-4035): only the compressed bytes cross PCIe
             from blackbox_amd import fpack as P
-            if self.torch.is_tensor(img):
-                P.fpack_image(self.ctx, path, img, header)
-                return path + '.fz'
+            P.fpack_image(self.ctx, path, img, header)
+            return path + '.fz'
         self.fitsio.write_image(path, img.cpu().numpy() if self.torch.is_tensor(img) else img, header)
         return path
 
-    def subtract_and_write(self, data, mask, header, base, res=None):
+    def subtract_and_write(self, data, mask, header, base, products, res=None):
         """zogy.optimal_subtraction + the products it leaves (set_blackbox.py:157-164); a failure
         keeps the reduction products (blackbox.py:2364-2382)"""
         from blackbox_amd import zogy as G, qc
-        fitsio = self.fitsio
         try:
             if res is None:
                 kw = {k: v for k, v in self.sub.items() if k not in ('ref', 'ref_mask', 'psf_new', 'psf_ref')}
@@ -540,27 +563,27 @@ class Reducer:
         hnew, htrans = res['header_new'], res['header_trans']
         header.update(hnew)
         bkg_hdr = {'BKG-SIZE': hnew['BKG-SIZE']}
-        self._small('image', base + '_bkg_mini.fits', np.asarray(res['bkg_mini_new']), bkg_hdr)
-        self._small('image', base + '_bkg_std_mini.fits', np.asarray(res['bkg_std_mini_new']), bkg_hdr)
+        products.small('image', base + '_bkg_mini.fits', np.asarray(res['bkg_mini_new']), bkg_hdr)
+        products.small('image', base + '_bkg_std_mini.fits', np.asarray(res['bkg_std_mini_new']), bkg_hdr)
         qc_flag = qc.run_qc_check(header, self.tel, check_key_type='full')
         if res.get('catalog') is not None:
             if qc_flag == 'red':
                 qc.run_qc_check(header, self.tel, cat_type='new', cat_dummy=base + '_cat.fits', check_key_type='full')
             else:
-                self._small('cat', res['catalog'], base + '_cat.fits', 'new', dict(header))
-            self._small('header', base + '_cat_hdr.fits', dict(header))
+                products.small('cat', res['catalog'], base + '_cat.fits', 'new', dict(header))
+            products.small('header', base + '_cat_hdr.fits', dict(header))
         if res.get('D') is not None:
             full_t = dict(header)
             full_t.update(htrans)
             tqc = qc.run_qc_check(full_t, self.tel, check_key_type='trans')
             for ext in ('D', 'Scorr', 'Fpsf'):
-                self.write_image('{}_{}.fits'.format(base, ext), res[ext], full_t)
-            self.write_limmag(base, res, full_t)
+                products.image('{}_{}.fits'.format(base, ext), res[ext], full_t)
+            self.write_limmag(base, res, full_t, products)
             if tqc == 'red' or qc_flag == 'red':
                 qc.run_qc_check(full_t, self.tel, cat_type='trans', cat_dummy=base + '_trans.fits', check_key_type='trans')
             else:
-                self._small('trans', res['transients'], base + '_trans.fits', dict(full_t))
-            self._small('header', base + '_trans_hdr.fits', dict(full_t))
+                products.small('trans', res['transients'], base + '_trans.fits', dict(full_t))
+            products.small('header', base + '_trans_hdr.fits', dict(full_t))
 
     def _limmag_is_flux(self, header):
         """one rule for the unit of `_trans_limmag`, whichever path writes it: a flux limit only when no zeropoint is known --
@@ -569,7 +592,7 @@ class Reducer:
             return False
         return not ('PC-ZP' in header and not isinstance(self.R.hval(header, 'PC-ZP'), str))
 
-    def write_limmag(self, base, res, header):
+    def write_limmag(self, base, res, header, products):
         """`_trans_limmag.fits` (set_blackbox.py:160-162): the transient detection limit per pixel,
         T-NSIGMA x Fpsferr -- in magnitudes when a zeropoint is known (--zeropoint, or PC-ZP of the header, with the
         extinction term PC-EXTCO x AIRMASSC when both are there: the photometric calibration itself is outside this
@@ -577,19 +600,17 @@ class Reducer:
         R, torch = self.R, self.torch
         if res.get('Fpsferr') is None:
             return
-        nsig = float(R.hval(header, 'T-NSIGMA')) if 'T-NSIGMA' in header else 6.0
-        zp = self.args.zeropoint
-        staged = getattr(self, '_staged', None)
-        is_staged = staged is not None and (base + '_trans_limmag.fits.fz') in staged['names']
-        # (the output stage has queued the flux limit already: only its header is made here, no image)
-        lim = None if is_staged else res['Fpsferr'] * nsig
-        if is_staged:
-            zp = None
-        elif zp is None and 'PC-ZP' in header and not isinstance(R.hval(header, 'PC-ZP'), str):
-            zp = float(R.hval(header, 'PC-ZP'))
+        nsig = float(_hval(header, 'T-NSIGMA', 6.0))
+        lim = zp = None
+        if not products.stages(base + '_trans_limmag.fits'):
+            # (else the output stage has queued the flux limit already: only its header is made here, no image)
+            lim = res['Fpsferr'] * nsig
+            zp = self.args.zeropoint
+            if zp is None and 'PC-ZP' in header and not isinstance(R.hval(header, 'PC-ZP'), str):
+                zp = float(R.hval(header, 'PC-ZP'))
         h = dict(header)
         if zp is not None:
-            exptime = float(R.hval(header, 'EXPTIME')) if 'EXPTIME' in header else 1.0
+            exptime = float(exptime_of(header))
             ext = 0.0
             if 'PC-EXTCO' in header and 'AIRMASSC' in header:
                 try:
@@ -601,27 +622,47 @@ class Reducer:
         else:
             h['LIMUNIT'] = ('e-', 'limit in flux: no zeropoint was given')
         h['LIMNSIG'] = (nsig, '[sigma] significance of the limit')
-        self.write_image(base + '_trans_limmag.fits', lim.contiguous() if lim is not None else None, h)
+        products.image(base + '_trans_limmag.fits', lim.contiguous() if lim is not None else None, h)
 
     # ---- many object frames: frames-in-flight pipeline ------------------------------------------
     def reduce_list(self, files):
-        """object frames of one geometry through FramePipeline (several frames in flight on this
-        GPU); anything else goes through blackbox_reduce one by one.  Raw frames are read and uploaded as
-        the pipeline takes them (at most its depth in HBM at a time).  With --fpack True the image products are
-        compressed on the lane that made them and written by the output stage's threads
-        (blackbox_amd/outstage.py).  -> list of output names"""
-        R, torch = self.R, self.torch
-        from blackbox_amd.pipeline import FramePipeline
-        out = {}
-        todo = []
+        """object frames of one geometry through FramePipeline (several frames in flight on this GPU); anything else goes
+        through blackbox_reduce one by one.  Raw frames are read and uploaded as the pipeline takes them (at most its depth
+        in HBM at a time).  With --fpack True the image products are compressed on the lane that made them and written by
+        the output stage's threads (blackbox_amd/outstage.py).  -> list of output names"""
+        from blackbox_amd import pipeline as _pl
+        out, todo = self._triage(files)
+        first_raw, first_hdr = self._first_readable(todo, out)
+        if not todo:
+            return [out.get(fn) for fn in files]
+        geom = self.R.geometry(first_raw.shape, self.args.ysize_chan, self.args.xsize_chan)
+        os.makedirs(self.args.red_dir, exist_ok=True)
+        run = _ListRun(self, todo, out, geom, first_raw, first_hdr)
+        del first_raw                               # (the run alone holds the first frame, and drops it when the input stage reads the list)
+        run.build(*list_run_sizes(_pl.cpu_budget(), len(todo), os.environ))
+        try:
+            try:
+                run.pipe.run(run.source, on_done=run.on_done, on_input_error=run.on_input_error)
+            except Exception:
+                run.pipeline_gave_up()
+            run.wait_for_writers()
+        finally:
+            run.close()
+        for fn, _ in todo:
+            if fn not in out:
+                out[fn] = self.reduce_logged(fn)
+        return [out.get(fn) for fn in files]
+
+    def _triage(self, files):
+        """-> out: fn -> result of the files reduced one by one here, done already or unreadable; todo: [(fn, fits_out)]"""
+        out, todo = {}, []
         for fn in files:
             try:
                 header = self.read_header(fn)
-                imgtype = str(R.hval(header, 'IMAGETYP')).lower() if 'IMAGETYP' in header else 'object'
                 if not self.args.red_dir:
                     self.args.red_dir = os.path.dirname(os.path.abspath(fn))
                 _, fits_out = self.names(header)
-                if imgtype != 'object' or self.nonlin is not None:
+                if imgtype_of(header) != 'object' or self.nonlin is not None:
                     out[fn] = self.reduce_logged(fn)
                 elif self.already_done(fits_out):
                     out[fn] = fits_out
@@ -630,225 +671,206 @@ class Reducer:
             except Exception:
                 log.exception('exception was raised while reading %s', fn)
                 out[fn] = None
-        if not todo:
-            return [out.get(fn) for fn in files]
+        return out, todo
+
+    def _first_readable(self, todo, out):
         # the list's geometry from its first readable file (one that is not fails alone, like any other: blackbox.py:948-999)
-        first_raw = None
-        while todo and first_raw is None:
+        while todo:
             try:
-                first_raw, first_hdr = self.read_raw(todo[0][0])
+                return self.read_raw(todo[0][0])
             except Exception:
                 log.exception('exception was raised while reading %s', todo[0][0])
                 out[todo.pop(0)[0]] = None
-        if not todo:
-            return [out.get(fn) for fn in files]
-        geom = R.geometry(first_raw.shape, self.args.ysize_chan, self.args.xsize_chan)
-        exptime = R.hval(first_hdr, 'EXPTIME') if 'EXPTIME' in first_hdr else 1.0
-        sub = dict(self.sub) if self.sub is not None else None
-        os.makedirs(self.args.red_dir, exist_ok=True)
-        t0 = time.time()
-        live = {}                                                  # idx -> (fn, header, fits_out)
-        stage, written, input_failed = None, {}, set()
-        import threading
-        all_written = threading.Event()
-        kw = {}
-        # threads and frames in flight from the cores this process may use (cgroup quota / affinity mask), like bench.py's
-        # files-to-files run: on the 16 cores of a one-GPU box 6 lanes, 16 frames, 12 writers, 4 readers (one process), or 4 lanes,
-        # 12 frames, 8 writers, 2 readers in each of two (list_processes)
-        from blackbox_amd import pipeline as _pl
-        cores = _pl.cpu_budget()
-        lanes = max(2, min(6, cores // 2))
-        depth = max(2, min(16 if cores >= 12 else (12 if cores >= 8 else 8), len(todo)))
-        nwriters = max(2, min(12, cores))                     # (they wait in copies and write calls: 4 per 8 cores held the RAM-disk run at 70-75 frames/s, 8 give 90-95)
-        nreaders = max(2, min(4, cores // 4))
-        # (tuning runs: BBX_LIST_LANES / BBX_LIST_DEPTH / BBX_LIST_WRITERS / BBX_LIST_READERS override the choice above)
-        lanes = int(os.environ.get('BBX_LIST_LANES', lanes))
-        depth = max(2, min(int(os.environ.get('BBX_LIST_DEPTH', depth)), len(todo)))
-        nwriters = int(os.environ.get('BBX_LIST_WRITERS', nwriters))
-        nreaders = int(os.environ.get('BBX_LIST_READERS', nreaders))
-        if self.args.fpack:
-            from blackbox_amd import outstage
-            ny, nx = 2 * geom.ysize_chan, 8 * geom.xsize_chan
-            stage = outstage.OutputStage(self.ctx.device, ny, nx, nwriters=nwriters)
-
-            def header_hook(f, hdrs):
-                """the frame's scalars are in: complete the headers (bookkeeping, QC flags, subtraction keywords) through
-                the very code of the serial path; its image writes only hand their headers to the stage"""
-                fn, header, fits_out = live[f.idx]
-                self._staged = dict(names=set(f.out_names.values()), headers={}, wanted=set(), deferred=[])
-                try:
-                    self._finish_from_pipeline(f, fn, header, fits_out, t0)
-                    f.staged_wanted = set(self._staged['wanted'])
-                    res = dict(hdrs)
-                    res.update(self._staged['headers'])
-                    jobs = self._staged['deferred']
-                    if jobs:
-                        # the frame's small files: one task of the host pool (a worker process formats and writes them);
-                        # they count among the frame's files -- on_written fires when they and the images are on disk
-                        g = f.out_group
-                        with g.lock:
-                            g.left += 1
-                        from blackbox_amd import catalogs
-                        pipe.pool.pool.apply_async(catalogs.write_small_products, (jobs,), callback=lambda r, g=g: g.file_done(None),
-                                                   error_callback=lambda e, g=g: g.file_done(None, e))
-                    return res
-                finally:
-                    self._staged = None
-
-            def on_written(f, group):
-                # products the frame's QC decided against (red flag: no subtraction products) were queued before the flag
-                # was known: take them away again
-                for p in group.paths:
-                    if p not in getattr(f, 'staged_wanted', set(group.paths)):
-                        try:
-                            os.unlink(p)
-                        except OSError:
-                            pass
-                written[f.idx] = group.error
-                _FILES_DONE.append(time.time())
-                if len(written) + len(input_failed) >= len(todo):
-                    all_written.set()
-            kw = dict(outstage=stage, out_base=lambda idx, h: todo[idx][1].replace('.fits', ''), on_written=on_written,
-                      header_hook=header_hook, stage_limmag=self._limmag_is_flux)
-        self._pipe_exptime = exptime
-        pipe = FramePipeline(self.ctx, self.tel, geom, mflat=self.mflat, mbias=self.mbias, bpm=self.bpm,
-                             xtalk_coeffs=self.xtalk, exptime=exptime, depth=depth, lanes=min(lanes, depth),
-                             do_finish=True, detect_sats=True, keep_outputs=True, subtract=sub, log=log, **kw)
-
-        from blackbox_amd import instage
-
-        class _Serial:
-            """read + upload a frame when the pipeline asks for the next one (raw frames that are not unsigned 16-bit); a file
-            that cannot be read fails alone (instage.InputError in its place)"""
-
-            def __init__(self_):
-                self_.k = 0
-
-            def __iter__(self_):
-                return self_
-
-            def __next__(self_):
-                idx = self_.k
-                if idx >= len(todo):
-                    raise StopIteration
-                self_.k += 1
-                fn, fits_out = todo[idx]
-                try:
-                    d_raw, header = (first_raw, first_hdr) if idx == 0 else self.read_raw(fn)
-                    if tuple(d_raw.shape) != (geom.ny_raw, geom.nx_raw):
-                        raise ValueError('frames of different shapes in one --image_list: {} vs {}'.format(
-                            tuple(d_raw.shape), (geom.ny_raw, geom.nx_raw)))
-                except Exception as e:
-                    raise instage.InputError(idx, fn, e)
-                live[idx] = (fn, header, fits_out)
-                return d_raw, header
-
-        # unsigned 16-bit raw frames (plain or fpacked: what the telescopes deliver) come through the input stage: reader
-        # threads, one upload per file, the Rice decode on the device, nothing of it on the orchestrating thread
-        src = None
-        if first_raw.dtype == self.torch.uint16 and len(todo) > 1:
-            del first_raw
-            src = instage.InputStage(self.ctx, [fn for fn, _ in todo], (geom.ny_raw, geom.nx_raw), nreaders=nreaders,
-                                     nbuf=pipe.depth + 4, ahead=max(2, min(4, nreaders)))
-
-            class _Source:
-                """the input stage's frames with the bookkeeping this run keeps per frame"""
-                has_next = staticmethod(src.has_next)
-
-                def __iter__(self_):
-                    return self_
-
-                def __next__(self_):
-                    raw, header, ev = next(src)
-                    idx = src.taken - 1
-                    live[idx] = (todo[idx][0], dict(header), todo[idx][1])
-                    return raw, live[idx][1], ev
-
-        def on_done(idx, f):
-            if src is not None:
-                src.release(f.raw)
-            fn, header, fits_out = live[idx]
-            try:
-                if stage is None:
-                    self._finish_from_pipeline(f, fn, header, fits_out, t0)
-                out[fn] = getattr(f, 'written_name', None)
-            except Exception:
-                log.exception('exception was raised during [blackbox_reduce] of %s', fn)
-                out[fn] = None
-            if stage is None:
-                live.pop(idx, None)
-                _FILES_DONE.append(time.time())
-
-        def on_input_error(idx, e):
-            # this file fails (blackbox.py:948-999: exception logged, None for the file), the list goes on
-            log.error('exception was raised while reading %s: %r', todo[idx][0], e.cause)
-            out[todo[idx][0]] = None
-            input_failed.add(idx)
-            if stage is not None and len(written) + len(input_failed) >= len(todo):
-                all_written.set()
-        try:
-            try:
-                pipe.run(_Source() if src is not None else _Serial(), on_done=on_done, on_input_error=on_input_error)
-            except Exception:
-                # the pipeline itself gave up (not a file's fault): what it finished stands, the rest goes one by one below
-                log.exception('pipelined run failed; the files without products are reduced one by one')
-                for idx, (fn, fits_out) in enumerate(todo):
-                    if fn not in out and idx not in written:
-                        input_failed.add(idx)                        # (no product of the stage will come for it)
-                all_written.set()
-            if stage is not None and not all_written.wait(600.0):
-                log.error('output stage: %d of %d frames written', len(written), len(todo))
-            for idx, err in written.items():
-                if err is not None:
-                    log.error('writing the products of %s failed: %r', todo[idx][0], err)
-                    out[todo[idx][0]] = None
-        finally:
-            n = max(1, pipe.t_stats[3])
-            _PIPE_STATS.update(frames=pipe.t_stats[3], lanes=len(pipe.lane_thread), depth=pipe.depth,
-                               ms_start_to_strip_statistics=round(1e3 * pipe.t_stats[0] / n, 2), ms_overscan_fits=round(1e3 * pipe.t_stats[1] / n, 2),
-                               ms_device_stage_and_lane_queue=round(1e3 * pipe.t_stats[2] / n, 2))
-            pipe.close()
-            if stage is not None:
-                stage.close()
-            if src is not None:
-                src.close()
-        for fn, _ in todo:
-            if fn not in out:
-                out[fn] = self.reduce_logged(fn)
-        return [out.get(fn) for fn in files]
-
-    def _finish_from_pipeline(self, f, fn, header, fits_out, t0):
-        """header completion + products of a frame that came out of the pipeline"""
-        R = self.R
-        # the pipeline works with one exposure time; NCOSMICS follows the frame's own
-        et = R.hval(header, 'EXPTIME') if 'EXPTIME' in header else 1.0
-        if et != f_exptime(self, f) and not isinstance(R.hval(header, 'NCOSMICS'), str):
-            header['NCOSMICS'] = (R.hval(header, 'NCOSMICS') * float(f_exptime(self, f)) / float(et), header['NCOSMICS'][1])
-        if 'zogy' in f.failed:
-            header['Z-P'] = (False, 'successfully processed by ZOGY?')
-        fh = self.open_image_log(fits_out)                    # the per-image log (blackbox.py:1311-1318) of a pipelined frame:
-        try:                                                  # what its completion has to say (QC flags, failed steps)
-            for step in f.failed:
-                log.error('step [%s] failed for %s', step, fn)
-            f.written_name = self.finish_object(fn, f.data, f.mask, header, f.hm, fits_out, t0, sub_result=f.sub)
-        finally:
-            self.close_image_log(fh)
+        return None, None
 
     def read_header(self, filename):
         """the header of a raw frame without its pixels"""
         if filename.endswith('.fz'):
-            h = self.fitsio.read_hdus(filename, headers_only=True)[1][0]
-        else:
-            h = self.fitsio.read_hdus(filename, headers_only=True)[0][0]
-        header = dict(h)
-        for k in ('BZERO', 'BSCALE', 'BITPIX', 'NAXIS', 'NAXIS1', 'NAXIS2', 'SIMPLE', 'EXTEND'):
-            header.pop(k, None)
-        return header
+            return _frame_header(self.fitsio.read_hdus(filename, headers_only=True)[1][0])
+        return _frame_header(self.fitsio.read_hdus(filename, headers_only=True)[0][0])
 
 
-def f_exptime(reducer, f):
-    """the exposure time the pipeline of this run works with"""
-    return getattr(reducer, '_pipe_exptime', 1.0)
+# threads and frames in flight from the cores this process may use (cgroup quota / affinity mask), like bench.py's
+# files-to-files run: on the 16 cores of a one-GPU box 6 lanes, 16 frames, 12 writers, 4 readers (one process), or 4 lanes,
+# 12 frames, 8 writers, 2 readers in each of two (list_processes)
+def list_run_sizes(cores, nfiles, environ):
+    """-> (lanes, depth, nwriters, nreaders) of a list run of [nfiles] frames on [cores] cores"""
+    lanes = max(2, min(6, cores // 2))
+    depth = max(2, min(16 if cores >= 12 else (12 if cores >= 8 else 8), nfiles))
+    nwriters = max(2, min(12, cores))                     # (they wait in copies and write calls: 4 per 8 cores held the RAM-disk run at 70-75 frames/s, 8 give 90-95)
+    nreaders = max(2, min(4, cores // 4))
+    # (tuning runs: BBX_LIST_LANES / BBX_LIST_DEPTH / BBX_LIST_WRITERS / BBX_LIST_READERS override the choice above)
+    lanes = int(environ.get('BBX_LIST_LANES', lanes))
+    depth = max(2, min(int(environ.get('BBX_LIST_DEPTH', depth)), nfiles))
+    nwriters = int(environ.get('BBX_LIST_WRITERS', nwriters))
+    nreaders = int(environ.get('BBX_LIST_READERS', nreaders))
+    return lanes, depth, nwriters, nreaders
+
+
+class _SerialSource:
+    """read + upload a frame when the pipeline asks for the next one (raw frames that are not unsigned 16-bit); a file
+    that cannot be read fails alone (instage.InputError in its place)"""
+
+    def __init__(self, run):
+        self.run, self.k = run, 0
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        run, idx = self.run, self.k
+        if idx >= len(run.todo):
+            raise StopIteration
+        self.k += 1
+        fn = run.todo[idx][0]
+        try:
+            d_raw, header = (run.first_raw, run.first_hdr) if idx == 0 else run.r.read_raw(fn)
+            if tuple(d_raw.shape) != (run.geom.ny_raw, run.geom.nx_raw):
+                raise ValueError('frames of different shapes in one --image_list: {} vs {}'.format(
+                    tuple(d_raw.shape), (run.geom.ny_raw, run.geom.nx_raw)))
+        except Exception as e:
+            from blackbox_amd.instage import InputError
+            raise InputError(idx, fn, e)
+        return d_raw, header
+
+
+class _ListRun:
+    """one pipelined --image_list run of a Reducer: the state its callbacks share.  Three kinds of thread call them (see
+    blackbox_amd/pipeline.py): the orchestrating thread (the one inside pipe.run), the pipeline's finisher thread and the
+    output stage's writer threads; each method says which"""
+
+    def __init__(self, reducer, todo, out, geom, first_raw, first_hdr):
+        self.r, self.todo, self.out, self.geom = reducer, todo, out, geom      # todo: [(fn, fits_out)]; out: fn -> result
+        self.first_raw, self.first_hdr = first_raw, first_hdr
+        self.exptime = exptime_of(first_hdr)                       # the one exposure time the pipeline works with
+        self.t0 = time.time()
+        self.written, self.input_failed = {}, set()                # idx -> error of its files or None; idx that failed on input
+        self.all_written = threading.Event()
+        self.stage = self.src = self.pipe = None
+
+    def build(self, lanes, depth, nwriters, nreaders):            # output stage (--fpack True), pipeline, input stage
+        from blackbox_amd import instage, outstage, pipeline
+        r, geom = self.r, self.geom
+        kw = {}
+        self.source = _SerialSource(self)
+        if r.args.fpack:
+            self.stage = outstage.OutputStage(r.ctx.device, 2 * geom.ysize_chan, 8 * geom.xsize_chan, nwriters=nwriters)
+            kw = dict(outstage=self.stage, out_base=self.out_base, on_written=self.on_written,
+                      header_hook=self.header_hook, stage_limmag=r._limmag_is_flux)
+        self.pipe = pipeline.FramePipeline(r.ctx, r.tel, geom, mflat=r.mflat, mbias=r.mbias, bpm=r.bpm, xtalk_coeffs=r.xtalk,
+                                           exptime=self.exptime, depth=depth, lanes=min(lanes, depth), do_finish=True, detect_sats=True,
+                                           keep_outputs=True, subtract=dict(r.sub) if r.sub is not None else None, log=log, **kw)
+        # unsigned 16-bit raw frames (plain or fpacked: what the telescopes deliver) come through the input stage: reader
+        # threads, one upload per file, the Rice decode on the device, nothing of it on the orchestrating thread
+        if self.first_raw.dtype == r.torch.uint16 and len(self.todo) > 1:
+            self.first_raw = None                                  # (the stage reads it again: not twice in HBM)
+            self.source = self.src = instage.InputStage(r.ctx, [fn for fn, _ in self.todo], (geom.ny_raw, geom.nx_raw),
+                                                        nreaders=nreaders, nbuf=self.pipe.depth + 4, ahead=max(2, min(4, nreaders)))
+
+    def out_base(self, idx, header):                               # orchestrating thread
+        return self.todo[idx][1].replace('.fits', '')
+
+    def finish(self, f, products):
+        """header completion + products of a frame that came out of the pipeline (header_hook's or on_done's thread)"""
+        R, r = self.r.R, self.r
+        (fn, fits_out), header = self.todo[f.idx], f.header        # (the dict the source handed to the pipeline: the frame's own)
+        # the pipeline works with one exposure time; NCOSMICS follows the frame's own
+        et = exptime_of(header)
+        if et != self.exptime and not isinstance(R.hval(header, 'NCOSMICS'), str):
+            header['NCOSMICS'] = (R.hval(header, 'NCOSMICS') * float(self.exptime) / float(et), header['NCOSMICS'][1])
+        if 'zogy' in f.failed:
+            header['Z-P'] = (False, 'successfully processed by ZOGY?')
+        fh = r.open_image_log(fits_out)                       # the per-image log (blackbox.py:1311-1318) of a pipelined frame:
+        try:                                                  # what its completion has to say (QC flags, failed steps)
+            for step in f.failed:
+                log.error('step [%s] failed for %s', step, fn)
+            f.written_name = r.finish_object(fn, f.data, f.mask, header, f.hm, fits_out, self.t0, products, sub_result=f.sub)
+        finally:
+            r.close_image_log(fh)
+
+    def header_hook(self, f, hdrs):
+        """finisher thread: the frame's scalars are in: complete the headers (bookkeeping, QC flags, subtraction keywords)
+        through the very code of the serial path; its image writes only hand their headers to the stage"""
+        products = _Products(self.r, staged=f.out_names.values())
+        self.finish(f, products)
+        f.staged_wanted = set(products.headers)
+        res = {**hdrs, **products.headers}
+        if products.deferred:
+            # the frame's small files: one task of the host pool (a worker process formats and writes them);
+            # they count among the frame's files -- on_written fires when they and the images are on disk
+            g = f.out_group
+            g.add_task()
+            from blackbox_amd import catalogs
+            self.pipe.pool.apply_async(catalogs.write_small_products, (products.deferred,), callback=lambda r: g.file_done(None),
+                                       error_callback=lambda e: g.file_done(None, e))
+        return res
+
+    def on_written(self, f, group):                                # a writer thread: the last file of the frame is on disk
+        # products the frame's QC decided against (red flag: no subtraction products) were queued before the flag
+        # was known: take them away again
+        for p in group.paths:
+            if p not in getattr(f, 'staged_wanted', set(group.paths)):
+                try:
+                    os.unlink(p)
+                except OSError:
+                    pass
+        self.written[f.idx] = group.error
+        _FILES_DONE.append(time.time())
+        self.check_complete()
+
+    def on_done(self, idx, f):                                     # orchestrating thread
+        if self.src is not None:
+            self.src.release(f.raw)
+        fn = self.todo[idx][0]
+        try:
+            if self.stage is None:
+                self.finish(f, _Products(self.r))
+            self.out[fn] = getattr(f, 'written_name', None)
+        except Exception:
+            log.exception('exception was raised during [blackbox_reduce] of %s', fn)
+            self.out[fn] = None
+        if self.stage is None:
+            _FILES_DONE.append(time.time())
+
+    def on_input_error(self, idx, e):                              # orchestrating thread
+        # this file fails (blackbox.py:948-999: exception logged, None for the file), the list goes on
+        log.error('exception was raised while reading %s: %r', self.todo[idx][0], e.cause)
+        self.out[self.todo[idx][0]] = None
+        self.input_failed.add(idx)
+        self.check_complete()
+
+    def check_complete(self):                                      # (on_written's, on_input_error's, pipeline_gave_up's thread)
+        # every frame of todo has either been written or failed on input: wait_for_writers may go on
+        if len(self.written) + len(self.input_failed) >= len(self.todo):
+            self.all_written.set()
+
+    def pipeline_gave_up(self):                                    # orchestrating thread, in the handler of pipe.run's exception
+        # the pipeline itself gave up (not a file's fault): what it finished stands, the rest goes one by one.  No product
+        # of the stage is waited for any more: every frame not written yet counts as failed on input
+        log.exception('pipelined run failed; the files without products are reduced one by one')
+        self.input_failed.update(idx for idx in range(len(self.todo)) if idx not in self.written)
+        self.check_complete()
+
+    def wait_for_writers(self):                                    # orchestrating thread; -> None for the files that were not written
+        if self.stage is not None and not self.all_written.wait(600.0):
+            log.error('output stage: %d of %d frames written', len(self.written), len(self.todo))
+        for idx, err in self.written.items():
+            if err is not None:
+                log.error('writing the products of %s failed: %r', self.todo[idx][0], err)
+                self.out[self.todo[idx][0]] = None
+
+    def close(self):                              # the pipeline's BBX_TIMING figures; then pipeline, output stage (joins the writers), input stage
+        pipe = self.pipe
+        n = max(1, pipe.t_stats[3])
+        _PIPE_STATS.update(frames=pipe.t_stats[3], lanes=len(pipe.lane_thread), depth=pipe.depth,
+                           ms_start_to_strip_statistics=round(1e3 * pipe.t_stats[0] / n, 2), ms_overscan_fits=round(1e3 * pipe.t_stats[1] / n, 2),
+                           ms_device_stage_and_lane_queue=round(1e3 * pipe.t_stats[2] / n, 2))
+        pipe.close()
+        if self.stage is not None:
+            self.stage.close()
+        if self.src is not None:
+            self.src.close()
+        self.pipe = None                             # (it holds this run's callbacks: no reference cycle left behind, the pool's semaphores go now)
 
 
 def list_processes(args, nfiles):

@@ -82,6 +82,11 @@ class FrameGroup:
                 self.error = err if err is not None else GroupCancelled('frame cancelled')
         self.header_ready.set()
 
+    def add_task(self):
+        """one more file (or task that ends in file_done) belongs to this frame"""
+        with self.lock:
+            self.left += 1
+
     def seal(self):
         """no more files will be submitted for this frame"""
         self.file_done(None)

@@ -89,6 +89,10 @@ class HostPool:
         # ~14k tasks/s; BBX_HOST_CHUNK overrides
         return self.pool.map_async(fn, tasks, chunksize=self.chunk)
 
+    def apply_async(self, fn, args, callback=None, error_callback=None):
+        """one call of fn(*args) in a worker (a caller's own task, e.g. a frame's small files)"""
+        return self.pool.apply_async(fn, args, callback=callback, error_callback=error_callback)
+
     def close(self):
         self.pool.close()                   # workers exit after their queue drains (no SIGTERM)
         self.pool.join()

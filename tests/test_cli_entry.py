@@ -117,3 +117,62 @@ def test_list_split_over_processes(monkeypatch, tmp_path, capsys):
     assert printed[:7] == [str(w) for w in want]
     tm = json.loads([ln for ln in printed if ln.startswith('BBX_TIMING ')][-1][len('BBX_TIMING '):])
     assert tm['list_processes'] == 3 and len(tm['files_done_unix']) == 5 and tm['hbm_peak_GB_tensors'] == 100.0
+
+
+def test_list_run_sizes():
+    """lanes, frames in flight, writer and reader threads of a list run from the core budget (16 cores -> 6 / 16 /
+    12 / 4, 8 cores -> 4 / 12 / 8 / 2), and the BBX_LIST_* overrides: each its own value only, the depth within [2, files]"""
+    sizes = load_cli().list_run_sizes
+    assert sizes(16, 96, {}) == (6, 16, 12, 4)
+    assert sizes(8, 48, {}) == (4, 12, 8, 2)
+    assert sizes(4, 96, {}) == (2, 8, 4, 2)
+    assert sizes(16, 3, {})[1] == 3
+    assert sizes(16, 96, {'BBX_LIST_DEPTH': '200'}) == (6, 96, 12, 4)
+    assert sizes(16, 96, {'BBX_LIST_DEPTH': '1'}) == (6, 2, 12, 4)
+    assert sizes(16, 96, {'BBX_LIST_LANES': '3'}) == (3, 16, 12, 4)
+    assert sizes(16, 96, {'BBX_LIST_WRITERS': '5'}) == (6, 16, 5, 4)
+    assert sizes(16, 96, {'BBX_LIST_READERS': '1'}) == (6, 16, 12, 1)
+
+
+def test_staged_product_writer(tmp_path):
+    """the product writer of a list-run frame whose images the output stage writes: a staged image leaves only its header,
+    any other image is written at once, small products are collected in order, the staged limit image is a header alone
+    (flux limit: no image computed, no zeropoint looked up)"""
+    import argparse
+    import numpy as np
+    import torch
+    from blackbox_amd import fitsio, reduce as R
+    cli = load_cli()
+    red = object.__new__(cli.Reducer)                             # (no GPU context: only what the writers read)
+    red.args, red.torch, red.fitsio, red.R = argparse.Namespace(fpack=False, zeropoint=25.0), torch, fitsio, R
+    base = str(tmp_path / 'ML1_20240102_030405_red')
+    img = np.arange(12, dtype=np.float32).reshape(3, 4)
+    p = cli._Products(red, staged=[base + '.fits.fz', base + '_trans_limmag.fits.fz'])
+    hdr = {'EXPTIME': (60.0, 'exposure')}
+    assert p.image(base + '.fits', img, hdr) == base + '.fits.fz'
+    hdr['LATER'] = 1                                              # (the writer keeps a copy of the header)
+    assert p.headers == {base + '.fits.fz': {'EXPTIME': (60.0, 'exposure')}}
+    assert os.listdir(str(tmp_path)) == []
+    assert p.image(base + '_D.fits', img, hdr) == base + '_D.fits'               # not staged: on disk at once
+    back, hback = fitsio.read_image(base + '_D.fits', get_header=True)
+    assert np.array_equal(back, img) and R.hval(hback, 'EXPTIME') == 60.0
+    p.small('header', base + '_hdr.fits', {'A': 1})
+    p.small('image', base + '_bkg_mini.fits', img, {'BKG-SIZE': 60})
+    assert [(k, a[0]) for k, a in p.deferred] == [('header', base + '_hdr.fits'), ('image', base + '_bkg_mini.fits')]
+    assert os.listdir(str(tmp_path)) == [os.path.basename(base) + '_D.fits']
+
+    class NoImage:                                                # stands in for Fpsferr: any arithmetic on it fails
+        def __mul__(self, other):
+            raise AssertionError('the staged limit image must not be computed')
+    for header, nsig in (({'PC-ZP': (24.1, 'zeropoint')}, 6.0), ({'T-NSIGMA': (5.0, 'sigma'), 'PC-ZP': (24.1, 'zeropoint')}, 5.0)):
+        red.write_limmag(base, {'Fpsferr': NoImage()}, header, p)
+        h = p.headers[base + '_trans_limmag.fits.fz']
+        assert R.hval(h, 'LIMUNIT') == 'e-' and R.hval(h, 'LIMNSIG') == nsig and 'PC-ZP' in h
+    red.write_limmag(base, {'Fpsferr': None}, {}, cli._Products(red, staged=[base + '_trans_limmag.fits.fz']))   # returns at once
+    assert set(p.headers) == {base + '.fits.fz', base + '_trans_limmag.fits.fz'}
+    assert os.listdir(str(tmp_path)) == [os.path.basename(base) + '_D.fits']
+    # the direct writer: the same calls write at once
+    d = cli._Products(red)
+    assert d.image(base + '.fits', img, hdr) == base + '.fits' and os.path.isfile(base + '.fits')
+    d.small('header', base + '_hdr.fits', {'A': 1})
+    assert os.path.isfile(base + '_hdr.fits') and d.deferred == [] and d.headers == {}
