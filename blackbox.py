@@ -370,7 +370,34 @@ class Reducer:
         elif a.trans_extract:
             log.info('no reference image given: processing the new image only, without comparison to a reference '
                      '(blackbox.py:2338-2354)')
+        # thumbnails of the transient candidates: command line over settings; the keywords are only passed when switched on
+        from blackbox_amd import settings as S
+
+        def par(value, name):
+            return S.get_par(getattr(S, name), self.tel) if value is None else value
+        self.thumbnails_dir = par(a.thumbnails_dir, 'thumbnails_dir')
+        if sub['ref'] is not None:
+            if par(a.save_thumbnails, 'save_thumbnails'):
+                sub['thumbnails'] = True
+            if par(a.save_thumbnails_pngs, 'save_thumbnails_pngs'):
+                sub['thumbnail_pngs'] = True
         return sub
+
+    def _thumbnail_products(self, res, base):
+        """what the transient table's writer needs for the thumbnails of a frame, on the host: the float cut-outs only when
+        they become columns, the uint8 display planes only when PNG files are made; None when neither is switched on"""
+        def host(name):
+            t = res.get(name + '_host', res.get(name))           # (the list run has copied them on the frame's lane already)
+            if t is None:
+                return None
+            return t.cpu().numpy() if self.torch.is_tensor(t) else np.asarray(t)
+        th, png = host('thumbnails'), host('thumbnail_png8')
+        if th is None and png is None:
+            return None
+        name = os.path.basename(base)
+        name = name[:-len('_red')] if name.endswith('_red') else name
+        root = self.thumbnails_dir or os.path.join(os.path.dirname(base), 'thumbnails')
+        return dict(thumbnails=th, png8=png, png_dir=os.path.join(root, name))
 
     # ------------------------------------------------------------------------------------
     def try_blackbox_reduce(self, filename):
@@ -582,7 +609,8 @@ class Reducer:
             if tqc == 'red' or qc_flag == 'red':
                 qc.run_qc_check(full_t, self.tel, cat_type='trans', cat_dummy=base + '_trans.fits', check_key_type='trans')
             else:
-                products.small('trans', res['transients'], base + '_trans.fits', dict(full_t))
+                thumbs = self._thumbnail_products(res, base)
+                products.small('trans', res['transients'], base + '_trans.fits', dict(full_t), *([thumbs] if thumbs else []))
             products.small('header', base + '_trans_hdr.fits', dict(full_t))
 
     def _limmag_is_flux(self, header):
@@ -1044,6 +1072,13 @@ def build_parser():
                     help='y0:y1,x0:x1: flat normalisation / statistics section (default set_bb.flat_norm_sec of the telescope)')
     ap.add_argument('--subimage_border', type=int, default=None)
     ap.add_argument('--bkg_boxsize', type=int, default=None)
+    # transient thumbnails (set_blackbox.py:62-66, 90): unset = blackbox_amd.settings (both switches off there)
+    ap.add_argument('--save_thumbnails', type=str2bool, default=None,
+                    help='THUMBNAIL_RED/_REF/_D/_SCORR and FLAGS_MASK columns in _trans.fits')
+    ap.add_argument('--save_thumbnails_pngs', type=str2bool, default=None,
+                    help='{NUMBER}_{RED,REF,D,SCORR}.png of every transient under --thumbnails_dir')
+    ap.add_argument('--thumbnails_dir', type=str, default=None,
+                    help='root of the PNG thumbnails: <thumbnails_dir>/<image base name>/ (default: thumbnails/ next to the products)')
     ap.add_argument('--zeropoint', type=float, default=None,
                     help='[mag] photometric zeropoint for 1 e-/s (else header PC-ZP): _trans_limmag in magnitudes')
     ap.add_argument('--nproc', type=int, default=1, help='worker processes for --image_list (one GPU context each)')

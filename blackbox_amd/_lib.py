@@ -126,6 +126,8 @@ SIGNATURES = {
     'bbx_psf_optflux_sigma': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'bbx_find_peaks': (_i, [_vp, _i, _i, _vp, _f, _i, _vp, _vp, _vp, _vp]),
     'bbx_count_objects': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    'bbx_thumbnails': (_i, [_vp, _i, _i, C.POINTER(_vp), _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    'bbx_thumb_png8': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError if the export is missing

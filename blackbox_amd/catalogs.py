@@ -5,9 +5,20 @@ versions for red-flagged images (qc.py:451-503 -> zogy.format_cat).
 [EXT] zogy.format_cat is not part of /root/reference; the column names follow the BlackGEM /
 MeerLICHT catalogue conventions for the quantities the hot path produces (pixel positions,
 PSF-weighted optimal fluxes, ZOGY significance and PSF flux); everything that needs astrometry,
-photometric calibration or the real-bogus classifier (RA/DEC, MAG_*, CLASS_REAL, thumbnails) is
-out of scope and absent.
+photometric calibration or the real-bogus classifier (RA/DEC, MAG_*, CLASS_REAL) is out of scope
+and absent.
+
+Thumbnails (settings.save_thumbnails / save_thumbnails_pngs, both off by default): a transient
+table that carries them is written with THUMBNAIL_RED, THUMBNAIL_REF, THUMBNAIL_D, THUMBNAIL_SCORR
+(qc.py:480-485; 100 x 100 float32 cells, TDIM '(100,100)') and FLAGS_MASK after the six columns
+above; save_png_thumbnails writes the reference's {NUMBER}_{RED,REF,D,SCORR}.png files
+(blackbox.py:2674-2826) from the display planes the GPU made (zogy.thumbnail_stamps).
 """
+import os
+import shutil
+import struct
+import zlib
+
 import numpy as np
 
 from . import fitsio
@@ -20,6 +31,8 @@ COLUMNS = {
               ('SNR_ZOGY', np.float32, ''), ('E_FLUX_ZOGY', np.float32, 'e-'), ('E_FLUXERR_ZOGY', np.float32, 'e-')),
 }
 COLUMNS['ref'] = COLUMNS['new']
+THUMBNAILS = ('RED', 'REF', 'D', 'SCORR')                     # plane order of zogy.thumbnail_stamps; blackbox.py:2701
+THUMBNAIL_COLUMNS = tuple('THUMBNAIL_' + c for c in THUMBNAILS)
 
 
 def format_cat(table, cat_output, cat_type='new', header2add=None):
@@ -37,25 +50,85 @@ def format_cat(table, cat_output, cat_type='new', header2add=None):
         else:
             cols[name] = np.zeros(n, dtype=dt)
         units[name] = unit
+    if cat_type == 'trans' and table is not None and THUMBNAIL_COLUMNS[0] in table:
+        for name in THUMBNAIL_COLUMNS:
+            cols[name] = np.asarray(table[name]).astype(np.float32)
+            units[name] = 'e-' if name != 'THUMBNAIL_SCORR' else ''
+        cols['FLAGS_MASK'] = np.asarray(table['FLAGS_MASK']).astype(np.uint8) if 'FLAGS_MASK' in table else np.zeros(n, np.uint8)
+        units['FLAGS_MASK'] = ''
     fitsio.write_table(cat_output, cols, header2add, units=units)
     return cat_output
 
 
-def transient_table(transients):
-    """list of dict(y, x, scorr, fpsf, fpsferr) (zogy.optimal_subtraction) -> column dict (FITS
-    pixel coordinates, 1-based)"""
+def transient_table(transients, thumbnails=None):
+    """list of dict(y, x, scorr, fpsf, fpsferr[, flags]) (zogy.optimal_subtraction) -> column dict (FITS
+    pixel coordinates, 1-based); thumbnails: float32 [n, 4, S, S] (res['thumbnails'] on the host) -> the four
+    THUMBNAIL_* columns and FLAGS_MASK as well"""
     t = transients or []
+    tab = _transient_columns(t)
+    if thumbnails is not None:
+        th = np.asarray(thumbnails, np.float32)
+        if th.ndim != 4 or th.shape[0] != len(t) or th.shape[1] != 4:
+            raise ValueError('thumbnails of shape {} for {} transients'.format(th.shape, len(t)))
+        for k, name in enumerate(THUMBNAIL_COLUMNS):
+            tab[name] = th[:, k]
+        tab['FLAGS_MASK'] = np.array([d.get('flags', 0) for d in t], np.uint8)
+    return tab
+
+
+def _transient_columns(t):
     return dict(X_PEAK=np.array([d['x'] + 1 for d in t], np.int32), Y_PEAK=np.array([d['y'] + 1 for d in t], np.int32),
                 SNR_ZOGY=np.array([d['scorr'] for d in t], np.float32),
                 E_FLUX_ZOGY=np.array([d['fpsf'] for d in t], np.float32),
                 E_FLUXERR_ZOGY=np.array([d['fpsferr'] for d in t], np.float32))
 
 
+def _png_gray8(plane):
+    """8-bit grayscale PNG file of a uint8 [h, w] array (row 0 on top), with zlib and struct only"""
+    plane = np.ascontiguousarray(plane, np.uint8)
+    h, w = plane.shape
+    raw = np.empty((h, w + 1), np.uint8)
+    raw[:, 0] = 0                                             # filter type 0 (None) in front of every scanline
+    raw[:, 1:] = plane
+
+    def chunk(tag, body):
+        return struct.pack('>I', len(body)) + tag + body + struct.pack('>I', zlib.crc32(tag + body) & 0xffffffff)
+    return (b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 0, 0, 0, 0)) +
+            chunk(b'IDAT', zlib.compress(raw.tobytes(), 6)) + chunk(b'IEND', b''))
+
+
+def save_png_thumbnails(png8, numbers, dir_dest):
+    """blackbox.py:2674-2782 for a local destination: {dir_dest}/{NUMBER}_{RED,REF,D,SCORR}.png, one 8-bit grayscale file per
+    plane of png8 (uint8 [n, 4, S, S]: res['thumbnail_png8'] on the host, already flipped and scaled like save_thumbs_row's
+    arrays).  An existing dir_dest is emptied first, so that two reductions of an image do not mix (2725-2735); zero rows:
+    nothing is made, not even the directory (2775-2777).  -> the files written"""
+    png8 = np.asarray(png8)
+    numbers = np.asarray(numbers).reshape(-1)
+    if png8.shape[0] != numbers.size:
+        raise ValueError('{} thumbnail rows for {} catalogue numbers'.format(png8.shape[0], numbers.size))
+    if numbers.size == 0:
+        return []
+    if png8.ndim != 4 or png8.shape[1] != len(THUMBNAILS) or png8.dtype != np.uint8:
+        raise ValueError('png8 must be uint8 [n, 4, S, S]')
+    if os.path.isdir(dir_dest):
+        shutil.rmtree(dir_dest)
+    os.makedirs(dir_dest)
+    written = []
+    for row, number in zip(png8, numbers.tolist()):
+        for plane, col in zip(row, THUMBNAILS):
+            fn = os.path.join(dir_dest, '{}_{}.png'.format(int(number), col))
+            with open(fn, 'wb') as f:
+                f.write(_png_gray8(plane))
+            written.append(fn)
+    return written
+
+
 def write_small_products(jobs):
     """the small files of a frame in one call (a worker process of the host pool runs it for blackbox.py's list run, so
     that their formatting does not hold the interpreter lock of the process that drives the GPU): jobs = [(kind, args)],
     kind in 'image' (fitsio.write_image), 'header' (fitsio.write_header), 'cat' (format_cat), 'trans' (format_cat of
-    transient_table(args[0]))"""
+    transient_table(args[0]); an optional fourth argument dict(thumbnails=float32 [n, 4, S, S] or None, png8=uint8 [n, 4, S, S] or
+    None, png_dir=) adds the thumbnail columns and / or writes the PNG files of the rows, NUMBER = 1..n)"""
     done = []
     for kind, args in jobs:
         if kind == 'image':
@@ -65,7 +138,10 @@ def write_small_products(jobs):
         elif kind == 'cat':
             format_cat(args[0], args[1], cat_type=args[2], header2add=args[3])
         elif kind == 'trans':
-            format_cat(transient_table(args[0]), args[1], cat_type='trans', header2add=args[2])
+            extra = args[3] if len(args) > 3 and args[3] else {}
+            format_cat(transient_table(args[0], extra.get('thumbnails')), args[1], cat_type='trans', header2add=args[2])
+            if extra.get('png8') is not None:
+                save_png_thumbnails(extra['png8'], np.arange(1, len(args[0] or []) + 1), extra['png_dir'])
         else:
             raise ValueError('unknown small product {!r}'.format(kind))
         done.append(args[1] if kind in ('cat', 'trans') else args[0])

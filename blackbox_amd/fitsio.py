@@ -254,12 +254,14 @@ _TFORM = {'f4': 'E', 'f8': 'D', 'i2': 'I', 'i4': 'J', 'i8': 'K', 'u1': 'B', 'b1'
 
 def write_table(path, columns, header=None, units=None):
     """binary-table FITS file (empty primary HDU + one BINTABLE): columns = {name: 1-D or 2-D
-    array}; what zogy.format_cat writes for `_cat.fits` / `_trans.fits`.  Zero rows is valid
-    (the dummy catalogues of qc.py:451-503)."""
+    array, or one with multidimensional cells [nrow, d1, d2, ...], which gets a TDIMn card (the
+    100 x 100 thumbnails of `_trans.fits`: TFORM '10000E', TDIM '(100,100)')}; what
+    zogy.format_cat writes for `_cat.fits` / `_trans.fits`.  Zero rows is valid (the dummy
+    catalogues of qc.py:451-503)."""
     names = list(columns)
     arrs = [np.asarray(columns[n]) for n in names]
     nrow = arrs[0].shape[0] if arrs else 0
-    fields, forms = [], []
+    fields, forms, tdims = [], [], []
     for n, a in zip(names, arrs):
         if a.shape[0] != nrow:
             raise ValueError('column {} has {} rows, expected {}'.format(n, a.shape[0], nrow))
@@ -269,6 +271,7 @@ def write_table(path, columns, header=None, units=None):
         rep = int(np.prod(a.shape[1:])) if a.ndim > 1 else 1
         fields.append((n, '>' + code if code != 'b1' else 'u1', (rep,) if rep > 1 else ()))
         forms.append(('%d' % rep if rep > 1 else '') + _TFORM[code])
+        tdims.append('({})'.format(','.join(str(d) for d in reversed(a.shape[1:]))) if a.ndim > 2 else None)
     rec = np.zeros(nrow, dtype=[(n, t, s) for n, t, s in fields]) if fields else np.zeros(0, 'u1')
     for (n, _, _), a in zip(fields, arrs):
         if a.dtype == np.bool_:
@@ -284,6 +287,8 @@ def write_table(path, columns, header=None, units=None):
         cards.append(_card('TFORM%d' % (i + 1), form))
         if units and units.get(n):
             cards.append(_card('TUNIT%d' % (i + 1), units[n]))
+        if tdims[i]:
+            cards.append(_card('TDIM%d' % (i + 1), tdims[i]))
     cards += _user_cards(header)
     prim = [_card('SIMPLE', True, 'conforms to FITS standard'), _card('BITPIX', 8), _card('NAXIS', 0),
             _card('EXTEND', True)]
@@ -297,7 +302,8 @@ def write_table(path, columns, header=None, units=None):
 
 def read_table(path, ext=1):
     """-> (columns dict name -> native-endian array, header) of a BINTABLE HDU written with
-    fixed-width columns (L B I J K E D with repeat counts)"""
+    fixed-width columns (L B I J K E D with repeat counts); a column with a TDIMn card of more than
+    one dimension comes back as [nrow, ..., d2, d1]"""
     h, data = read_hdus(path)[ext]
     nf = int(_hv(h, 'TFIELDS', 0))
     nrow = int(_hv(h, 'NAXIS2', 0))
@@ -314,6 +320,10 @@ def read_table(path, ext=1):
         a = rec[n]
         cols[n] = (a == ord('T')) if t == 'u1' and str(_hv(h, 'TFORM%d' % (1 + [f[0] for f in fields].index(n)))).strip().endswith('L') \
             else a.astype(a.dtype.newbyteorder('='))
+    for i, (n, _, s) in enumerate(fields):
+        dims = str(_hv(h, 'TDIM%d' % (i + 1), '') or '').strip('() ').split(',')
+        if len(dims) > 1 and s and int(np.prod([int(d) for d in dims])) == s[0]:
+            cols[n] = cols[n].reshape((nrow,) + tuple(int(d) for d in reversed(dims)))
     return cols, h
 
 

@@ -675,6 +675,11 @@ class FramePipeline:
                     # comes first (its stream has finished with it before any other lane can pick it up: see below)
                     check(lib.bbx_wait(ctx.h, ctx.sp), 'bbx_wait', ctx.h)
                     self.ref_bkg_std = sub['bkg_std_ref']
+                for k in ('thumbnails', 'thumbnail_png8'):
+                    # the thumbnails of the transient candidates leave the GPU on this lane, behind the kernels that made them
+                    # (float cut-outs / uint8 display planes: whichever was asked for); the frame's completion reads them
+                    if sub.get(k) is not None:
+                        sub[k + '_host'] = torch.empty(sub[k].shape, dtype=sub[k].dtype, pin_memory=True).copy_(sub[k], non_blocking=True)
                 f.sub = sub
             except (_lib.BBXError, ValueError) as e:
                 f.failed.append('zogy')

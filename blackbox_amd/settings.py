@@ -71,6 +71,15 @@ subimage_size = 1320
 subimage_border = 40
 transient_nsigma = 6
 
+# ---- transient thumbnails (set_blackbox.py:62-66, 90; size_thumbnails: set_zogy, qc.py:484-485) ----
+# The reference's default for save_thumbnails_pngs is True; here both switches are off by default so
+# that existing product sets do not change.
+save_thumbnails = False        # THUMBNAIL_RED/_REF/_D/_SCORR + FLAGS_MASK columns in `_trans.fits`
+save_thumbnails_pngs = False   # {NUMBER}_{RED,REF,D,SCORR}.png per transient (blackbox.py:2674-2826)
+size_thumbnails = 100          # [pix] side of the square cut-outs
+thumbnails_dir = None          # PNGs go to {thumbnails_dir}/{image base name}/; None: `thumbnails/` next to the products
+trans_flags_window = 5         # [pix] side of the window around the peak whose mask values make FLAGS_MASK (this project's own)
+
 # calibration files of a reduction (explicit paths; the date-based master selection
 # of master_prep, blackbox.py:4625-4905, is blackbox_amd.masters, run by --master_date)
 bad_pixel_mask = None      # path containing 'bpm' -> 'bpm_{filt}' (blackbox.py:4386)

@@ -537,7 +537,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          subimage_size=None, subimage_border=None, bkg_boxsize=None, nsigma=None,
                          ref_is_bkgsub=False, ref_bkg_std_mini=None, ref_grid=None, ref_grid_step=32,
                          cat_extract=False, cat_nsigma=5.0, trans_extract=True, frame_stats=True, max_sources=200000,
-                         zogy_gate=None, ref_bkg_std=None, sigma_frames=False):
+                         zogy_gate=None, ref_bkg_std=None, sigma_frames=False, thumbnails=False, thumbnail_size=None,
+                         thumbnail_pngs=False):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -557,6 +558,11 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       another pixel grid: it is remapped with the LANCZOS3 kernel (zogy runs SWarp)
       psf_new/ref   : PSF stamps [nsub, S, S] / [S, S] (unit sum) or a PSFEx model dict
                       (subimage_psfs) -- running PSFEx itself is out of scope
+      thumbnails    : True: res['thumbnails'], device float32 [n, 4, S, S]: the cut-outs RED / REF / D / SCORR of every
+                      transient candidate (qc.py:480-485), S = thumbnail_size (settings.size_thumbnails)
+      thumbnail_pngs: True: res['thumbnail_png8'], device uint8 [n, 4, S, S]: their display planes (blackbox.py:2786-2826)
+                      either switch adds 'flags' (FLAGS_MASK: the masks under the peak) to each transient; both off: no
+                      kernel of bbx_thumb.hip is launched and the result has none of these keys
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
             header (= header_new additions), header_trans)"""
     size = subimage_size or settings.subimage_size
@@ -758,21 +764,34 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             ntrans = 'None'
         break
     # the fluxes at the candidates and the frame statistics of the header: queued together, one copy back, one host wait
-    d_fe = d_st = None
+    d_fe = d_st = d_fl = None
+    want_thumbs = bool(thumbnails or thumbnail_pngs)
+    tsize = int(thumbnail_size or settings.size_thumbnails)
     if tys.size:
         d_ys, d_xs = push(ctx, tys.astype(np.int64), txs.astype(np.int64))
         d_fe = torch.stack([res['Fpsf'][d_ys, d_xs], res['Fpsferr'][d_ys, d_xs]])
+    if want_thumbs:
+        # the cut-outs of the four frames, which are all still in HBM, and the mask flags under each peak in one pass; the
+        # display planes from the cut-outs.  The reference's mask counts only where it shares the new frame's grid
+        d_fl = thumbnail_stamps(ctx, res, (res['data_bkgsub'], res['ref_bkgsub'], res['D'], res['Scorr']), tys, txs, tsize, new_mask,
+                                ref_mask if ref_grid is None else None, floats=thumbnails, pngs=thumbnail_pngs)
     if frame_stats:
         # statistics over the unmasked pixels (new frame's mask), clipped like zogy's header values
         d_st = torch.stack([frame_clipped_stats_enqueue(ctx, res['Scorr'], new_mask),
                             frame_clipped_stats_enqueue(ctx, res['Fpsferr'], new_mask)])
-    back = [t for t in (d_fe, d_st) if t is not None]
+    if d_fl is not None and not d_fl.numel():
+        d_fl = None
+    back = [t for t in (d_fe, d_st, d_fl) if t is not None]
     got = (fetch(ctx, *back) if len(back) > 1 else [fetch(ctx, back[0])]) if back else []
     fe = got.pop(0) if d_fe is not None else None
     st = got.pop(0) if d_st is not None else None
+    fl = got.pop(0) if d_fl is not None else None
     if tys.size:
         res['transients'] = [dict(y=y, x=x, scorr=sc, fpsf=f, fpsferr=e)
                              for y, x, sc, f, e in zip(tys.tolist(), txs.tolist(), tsc.tolist(), fe[0].tolist(), fe[1].tolist())]
+        if fl is not None:
+            for d, v in zip(res['transients'], fl.tolist()):
+                d['flags'] = v
     else:
         res['transients'] = []
     hdr['Z-P'] = (True, 'successfully processed by ZOGY?')
@@ -793,6 +812,40 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     res['header_new'], res['header_trans'] = hdr, hdr_t
     res['scal'] = scal
     return res
+
+
+def thumbnail_stamps(ctx, res, frames, ys, xs, size, new_mask, ref_mask=None, floats=True, pngs=False, flag_win=None):
+    """bbx_thumbnails (+ bbx_thumb_png8) at the integer positions (ys, xs) of the four frames (RED, REF, D, SCORR): puts
+    'thumbnails' (device float32 [n, 4, size, size], when [floats]) and 'thumbnail_png8' (device uint8, same shape, when [pngs])
+    into [res] and returns the device flags [n] (uint8: OR of the masks over the flag window); n = 0 gives empty tensors and
+    launches nothing.  No host wait"""
+    n = int(len(ys))
+    dev = ctx.device
+    out = torch.empty((n, 4, size, size), dtype=torch.float32, device=dev)
+    d_fl = torch.empty(n, dtype=torch.uint8, device=dev)
+    png = torch.empty((n, 4, size, size), dtype=torch.uint8, device=dev) if pngs else None
+    if n:
+        frames = [f.contiguous() for f in frames]
+        ny, nx = frames[0].shape
+        for f in frames:
+            if f.dtype != torch.float32 or tuple(f.shape) != (ny, nx):
+                raise ValueError('thumbnail frames must be float32 of one shape')
+        for m in (new_mask, ref_mask):
+            if m is not None and (m.dtype != torch.uint8 or tuple(m.shape) != (ny, nx) or not m.is_contiguous()):
+                raise ValueError('thumbnail masks must be contiguous uint8 frames of the image shape')
+        d_y32, d_x32 = push(ctx, np.asarray(ys, np.int32), np.asarray(xs, np.int32))
+        planes = (C.c_void_p * 4)(*[f.data_ptr() for f in frames])
+        win = int(settings.trans_flags_window if flag_win is None else flag_win)
+        check(lib.bbx_thumbnails(ctx.h, ny, nx, planes, n, _p(d_y32), _p(d_x32), size, _p(new_mask),
+                                 _p(ref_mask) if ref_mask is not None else None, win, _p(out), _p(d_fl), ctx.stream()),
+              'bbx_thumbnails', ctx.h)
+        if pngs:
+            check(lib.bbx_thumb_png8(ctx.h, 4 * n, size, _p(out), _p(png), None, ctx.stream()), 'bbx_thumb_png8', ctx.h)
+    if floats:
+        res['thumbnails'] = out
+    if pngs:
+        res['thumbnail_png8'] = png
+    return d_fl
 
 
 class _HeaderView(dict):

@@ -631,6 +631,35 @@ int bbx_find_peaks(bbx_ctx *ctx, int ny, int nx, const float *d_img, float thr, 
 int bbx_count_objects(bbx_ctx *ctx, int ny, int nx, const uint8_t *d_mask,
                       int bit, int32_t *d_count, void *stream);
 
+/* ---- a17: transient thumbnails (THUMBNAIL_RED / _REF / _D / _SCORR of the transient catalogue, qc.py:480-485;
+ * [EXT] zogy.get_trans cuts them) and FLAGS_MASK.  d_img: HOST array of the four device frames [ny][nx] f32 in the
+ * order RED (background-subtracted new frame), REF (background-subtracted reference on the new frame's grid), D,
+ * SCORR; d_ys / d_xs: n integer peak positions (0-based).  d_out[n][4][size][size] f32: cut-out k covers rows
+ * y - size/2 ... y - size/2 + size - 1 and the columns likewise, so the peak is pixel [size/2][size/2].
+ * d_flags[n] u8 (NULL: not wanted): OR of d_new_mask, and of d_ref_mask when not NULL, over the flag_win x flag_win
+ * window centred on the peak.
+ * zogy's own footprint of the flags and its padding at the frame edge are [EXT] without a source in the reference
+ * tree.  The two conventions here are THIS PROJECT'S OWN: pixels off the frame are 0 in the cut-outs and contribute
+ * nothing to the flags; the flag window is a square of flag_win (settings.trans_flags_window) pixels.            */
+int bbx_thumbnails(bbx_ctx *ctx, int ny, int nx, const float *const *d_img, int n, const int32_t *d_ys,
+                   const int32_t *d_xs, int size, const uint8_t *d_new_mask, const uint8_t *d_ref_mask,
+                   int flag_win, float *d_out, uint8_t *d_flags, void *stream);
+
+/* ---- the 8-bit display planes of the thumbnail PNG files: per stamp what save_thumbs_row does
+ * (blackbox.py:2786-2808): np.flipud, astropy ZScaleInterval().get_limits (1000 strided samples of the finite
+ * values in C order, sorted; iterative line fit with 0/1 weights, krej 2.5, max_reject 0.5, min_npixels 5, at most 5
+ * iterations, rejections grown by max(1, int(npix * 0.01)) with numpy.convolve's 'same' alignment; contrast 0.25;
+ * sample minimum / maximum when too few samples survive) in float64, the weighted least-squares line in closed
+ * form; then scale_data (blackbox.py:2814-2826) in float32 as numpy does it: x - f32(vmin), / f32(vmax - vmin)
+ * (difference formed in float64), * 255, three separately rounded operations, clipped to [0, 255], truncated.
+ * d_stamps[n_stamps][size][size] f32 -> d_out_u8[n_stamps][size][size] (row 0 = top row of the PNG; 4-byte aligned),
+ * d_limits[n_stamps][2] f64 = (vmin, vmax) (NULL: not wanted).  A stamp with vmax == vmin or without a finite value
+ * gives zeros (limits (0, 0) in the second case) -- our convention: the reference divides by zero there; NaN
+ * pixels give 0.  One workgroup per stamp, the stamp in LDS: BBX_ERR_ARG when size * size * 4 bytes plus the
+ * kernel's 5.4 KB of sample buffers exceed the 64 KB of a workgroup (size <= 122).                                */
+int bbx_thumb_png8(bbx_ctx *ctx, int n_stamps, int size, const float *d_stamps, uint8_t *d_out_u8,
+                   double *d_limits, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
