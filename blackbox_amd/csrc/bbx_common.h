@@ -68,6 +68,10 @@ struct bbx_ctx {
     float  zcand_thr;          // bbx_zogy_candidates: > 0: bbx_zogy_frame lists the pixels with |Scorr| >= thr (WS_ZCAND, CNT_ZCAND)
     const float* zcand_img;    // the Scorr frame the list in WS_ZCAND belongs to (NULL: none); consumed by bbx_find_peaks
     float  zcand_thr_used; size_t zcand_npix;
+    const float2* zrows;       // bbx_zogy_refrows: the reference's prepared row transforms (caller's buffer; NULL: none) and what they
+    const void* zrows_ref;     // were made of: the reference frame, its sigma frame or spline coefficients, (ny, nx, size, border)
+    const void* zrows_sig;
+    int    zrows_geom[4];
     const float* bcand_med;    // bbx_zoom_candidates: device scalar m; the next bbx_spline_zoom_sub lists |out| >= (float)(m * bcand_nsig) (WS_BCAND, CNT_BCAND)
     double bcand_nsig;
     const float* bcand_img;    // the frame the list in WS_BCAND belongs to (consumed by bbx_find_peaks), its median scalar and factor

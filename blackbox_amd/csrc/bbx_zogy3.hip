@@ -384,11 +384,6 @@ template <class P> __device__ __forceinline__ void load_t_lines(const float2* T,
         }
     }
 }
-// entry e (= l * L + p) of the workgroup's scratch in its own, already consumed T tiles
-template <class P> __device__ __forceinline__ float2* park_ptr(float2* T, int sub, int g, int e) {
-    constexpr int TS = P::NL * P::NL;
-    return T + (size_t)sub * P::UNIT + (size_t)(e / TS) * P::HP * P::NL + (size_t)g * TS + e % TS;
-}
 template <class P> __device__ __forceinline__ void pack_store(float2* line, const unsigned short* pp, int kx, float2 a, float2 b) {
     if (kx >= P::H) return;
     line[pp[kx]] = make_float2(a.x - b.y, a.y + b.x);
@@ -815,16 +810,63 @@ __global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_img_rows(fr
     store_t_split<P>(s, aux.pp, Ta, Tb, sub, yb);
 }
 
-// The same for both pairs in one launch (frames whose groups of four pixels are aligned): the four frames are read once;
-// the variance pair (max(N, 0) + sigma_N^2, max(R, 0) + sigma_R^2) waits in registers behind the first transform.
-// SPL (round 5, bbx_zogy_frame_mini): the sigma images do not exist as frames -- the kernel reads them off their mini images
-// (bbx_spline.h): a table of the cubics of every frame row on every box interval (k_spl_polytable, 96 MB for both maps,
-// mostly L2 hits here: the ~15 groups of four pixels of an interval read the same entry) instead of the two frames (2 x 4N
-// written, 2 x 4N x 1.125 read); a pixel costs a share of a 16-byte load and three multiply-adds per map.
+// One frame of a pair and its variance image (frames whose groups of four pixels are aligned).  The two-for-one transforms
+// pair neighbouring rows of the same image: of the NL rows of a block, lines 0 .. NL/2 - 1 carry a[2j] + i a[2j + 1], lines
+// NL/2 .. NL - 1 carry V[2j] + i V[2j + 1], V = max(a, 0) + sigma^2 -- one transform of NL lines, split into the rows of
+// (a^, V^) by store_t_rows.  A packed transform rounds each partner in the presence of the other; partners of the same image
+// share their units, so frames, sigma maps and noise scalars times a power of two still scale S and Fpsf exactly (V is not
+// a multiple of its unscaled self -- max(a, 0) grows with the factor, sigma^2 with its square -- and must not ride with a).
+// The new frame goes into (T0, T2), the reference into (T1, T3): two launches of this kernel.  The reference's launch depends
+// on the reference and its sigma map alone, so a caller whose reference stays the same from frame to frame runs it once
+// (bbx_zogy_refrows) and bbx_zogy_frame then launches the new frame's only.
+// SPL (round 5, bbx_zogy_frame_mini): the sigma image does not exist as a frame -- the kernel reads it off its mini image
+// (bbx_spline.h): a table of the cubics of every frame row on every box interval (k_spl_polytable, 48 MB per map,
+// mostly L2 hits here: the ~15 groups of four pixels of an interval read the same entry) instead of the frame (4N
+// written, 4N x 1.125 read); a pixel costs a share of a 16-byte load and three multiply-adds.
+struct frame1_args {
+    const float* a; const float* sa;         // the frame; its sigma image (NULL with SPL)
+    int ny, nx, size, border, nsx;
+};
+// sigma of the four pixels (Y, X .. X + 3) of one patch off the cubic table (patch widths, X multiples of 4): interval and
+// remainder of the first, steps for the others; the group lies in one interval or in two neighbouring ones: both cubics are loaded
+__device__ __forceinline__ float4 spl_sigma4(const bbx_spl& sp, int Y, int X) {
+    int c, r;
+    bbx_spl_axis(X, sp.pw, sp.rpw, sp.px, sp.npad, sp.nx1, sp.dx, sp.rdx, c, r);
+    const float4* t = sp.poly + (size_t)Y * sp.cnx + c;
+    const int step = (r + 3 * sp.nx1 >= sp.dx) ? 1 : 0;
+    const float4 p0 = t[0], p1 = t[step];
+    float sg[4];
+    bool w = false;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        sg[k] = bbx_spl_horner(w ? p1 : p0, (float)r * sp.rdx);
+        r += sp.nx1; if (r >= sp.dx) { r -= sp.dx; w = true; }
+    }
+    return make_float4(sg[0], sg[1], sg[2], sg[3]);
+}
+__device__ __forceinline__ float4 var4(float4 v, float4 p) {
+    return make_float4(fmaxf(v.x, 0.f) + p.x * p.x, fmaxf(v.y, 0.f) + p.y * p.y, fmaxf(v.z, 0.f) + p.z * p.z, fmaxf(v.w, 0.f) + p.w * p.w);
+}
+// Hermitian split of the packed row pairs (LDS, spectrum order) -> the rows of two half spectra, T tiles of row block yb:
+// line j holds rows 2j, 2j + 1 of Ta, line NL/2 + j those of Tb
+template <class P> __device__ __forceinline__ void store_t_rows(const float2* s, const unsigned short* pp, float2* __restrict__ Ta, float2* __restrict__ Tb, int sub,
+                                                                 int yb) {
+    const size_t base = (size_t)sub * P::UNIT + (size_t)yb * P::HP * P::NL;
+    for (int kx = threadIdx.x; kx < P::H; kx += blockDim.x) {
+        const int pk = pp[kx], pm = pp[kx ? P::L - kx : 0];
+        float4* ta = reinterpret_cast<float4*>(Ta + base + (size_t)kx * P::NL);
+        float4* tb = reinterpret_cast<float4*>(Tb + base + (size_t)kx * P::NL);
+#pragma unroll
+        for (int j = 0; j < P::NL / 2; j++) {
+            const float2 ak = s[j * P::LS + pk], am = s[j * P::LS + pm], bk = s[(P::NL / 2 + j) * P::LS + pk], bm = s[(P::NL / 2 + j) * P::LS + pm];
+            st_nt(ta + j, make_float4(0.5f * (ak.x + am.x), 0.5f * (ak.y - am.y), 0.5f * (ak.y + am.y), 0.5f * (am.x - ak.x)));
+            st_nt(tb + j, make_float4(0.5f * (bk.x + bm.x), 0.5f * (bk.y - bm.y), 0.5f * (bk.y + bm.y), 0.5f * (bm.x - bk.x)));
+        }
+    }
+}
 template <class P, bool SPL>
-__global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_img_rows_both(frame_args f, const float2* __restrict__ twg, float2* __restrict__ Ta,
-                                                                                float2* __restrict__ Tb, float2* __restrict__ Tva, float2* __restrict__ Tvb, int nsub,
-                                                                                bbx_spl spn, bbx_spl spr) {
+__global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_img_rows_one(frame1_args f, const float2* __restrict__ twg, float2* __restrict__ Ta,
+                                                                               float2* __restrict__ Tva, int nsub, bbx_spl sp) {
     extern __shared__ float2 s[];
     WG_TASK_ROWS(P::LB, nsub, yb, sub);
     ZSTAMP_HEAD(2);
@@ -833,21 +875,24 @@ __global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_img_rows_bo
     const int y0 = yb * P::NL;
     const int sy = sub / f.nsx, sx = sub - sy * f.nsx;
     const int Y0 = sy * f.size - f.border, X0 = sx * f.size - f.border;
-    constexpr int NV = P::NL * P::L / 4, NP = (NV + P::LIGHT_THREADS - 1) / P::LIGHT_THREADS;
-    float4 pa[NP], pb[NP];
+    // an item: the same group of four pixels of the two rows of a pair
+    constexpr int XG = P::L / 4, NI = (P::NL / 2) * XG, NP = (NI + P::LIGHT_THREADS - 1) / P::LIGHT_THREADS;
     {
-        float4 va[NP], vb[NP];
+        float4 va[NP][2], pa[NP][2];
 #pragma unroll
         for (int i = 0; i < NP; i++) {
             const int e = (int)threadIdx.x + i * P::LIGHT_THREADS;
-            va[i] = vb[i] = pa[i] = pb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < NV) {
-                const int q = 4 * e, ll = q / P::L, x = q - ll * P::L;
-                const int Y = Y0 + y0 + ll, X = X0 + x;
-                if (y0 + ll < P::L && Y >= 0 && Y < f.ny && X >= 0 && X < f.nx) {
-                    const size_t o = (size_t)Y * f.nx + X;
-                    va[i] = ld_nt(reinterpret_cast<const float4*>(f.a + o)); vb[i] = ld_nt(reinterpret_cast<const float4*>(f.b + o));
-                    if (!SPL) { pa[i] = ld_nt(reinterpret_cast<const float4*>(f.sa + o)); pb[i] = ld_nt(reinterpret_cast<const float4*>(f.sb + o)); }
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                va[i][h] = pa[i][h] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (e < NI) {
+                    const int j = e / XG, x = 4 * (e - j * XG), ll = 2 * j + h;
+                    const int Y = Y0 + y0 + ll, X = X0 + x;
+                    if (y0 + ll < P::L && Y >= 0 && Y < f.ny && X >= 0 && X < f.nx) {
+                        const size_t o = (size_t)Y * f.nx + X;
+                        va[i][h] = ld_nt(reinterpret_cast<const float4*>(f.a + o));
+                        if (!SPL) pa[i][h] = ld_nt(reinterpret_cast<const float4*>(f.sa + o));
+                    }
                 }
             }
         }
@@ -855,29 +900,12 @@ __global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_img_rows_bo
 #pragma unroll
             for (int i = 0; i < NP; i++) {
                 const int e = (int)threadIdx.x + i * P::LIGHT_THREADS;
-                if (e < NV) {
-                    const int q = 4 * e, ll = q / P::L, x = q - ll * P::L;
-                    const int Y = Y0 + y0 + ll, X = X0 + x;
-                    if (y0 + ll < P::L && Y >= 0 && Y < f.ny && X >= 0 && X < f.nx) {
-                        // four pixels of one patch (patch widths, X0 multiples of 4): interval and remainder of the first, steps
-                        // for the others; the group lies in one interval or in two neighbouring ones: both cubics are loaded
-                        int cn, rn, cr, rr;
-                        bbx_spl_axis(X, spn.pw, spn.rpw, spn.px, spn.npad, spn.nx1, spn.dx, spn.rdx, cn, rn);
-                        bbx_spl_axis(X, spr.pw, spr.rpw, spr.px, spr.npad, spr.nx1, spr.dx, spr.rdx, cr, rr);
-                        const float4* tn = spn.poly + (size_t)Y * spn.cnx + cn;
-                        const float4* tr = spr.poly + (size_t)Y * spr.cnx + cr;
-                        const int stepn = (rn + 3 * spn.nx1 >= spn.dx) ? 1 : 0, stepr = (rr + 3 * spr.nx1 >= spr.dx) ? 1 : 0;
-                        const float4 pn0 = tn[0], pn1 = tn[stepn], pr0 = tr[0], pr1 = tr[stepr];
-                        float sgn[4], sgr[4];
-                        bool wn = false, wr = false;
 #pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            sgn[k] = bbx_spl_horner(wn ? pn1 : pn0, (float)rn * spn.rdx);
-                            sgr[k] = bbx_spl_horner(wr ? pr1 : pr0, (float)rr * spr.rdx);
-                            rn += spn.nx1; if (rn >= spn.dx) { rn -= spn.dx; wn = true; }
-                            rr += spr.nx1; if (rr >= spr.dx) { rr -= spr.dx; wr = true; }
-                        }
-                        pa[i] = make_float4(sgn[0], sgn[1], sgn[2], sgn[3]); pb[i] = make_float4(sgr[0], sgr[1], sgr[2], sgr[3]);
+                for (int h = 0; h < 2; h++) {
+                    if (e < NI) {
+                        const int j = e / XG, x = 4 * (e - j * XG), ll = 2 * j + h;
+                        const int Y = Y0 + y0 + ll, X = X0 + x;
+                        if (y0 + ll < P::L && Y >= 0 && Y < f.ny && X >= 0 && X < f.nx) pa[i][h] = spl_sigma4(sp, Y, X);
                     }
                 }
             }
@@ -885,16 +913,14 @@ __global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_img_rows_bo
 #pragma unroll
         for (int i = 0; i < NP; i++) {
             const int e = (int)threadIdx.x + i * P::LIGHT_THREADS;
-            if (e < NV) {
-                const int q = 4 * e, ll = q / P::L, x = q - ll * P::L;
-                float2* line = s + ll * P::LS;
-                line[npos(x)] = make_float2(va[i].x, vb[i].x); line[npos(x + 1)] = make_float2(va[i].y, vb[i].y);
-                line[npos(x + 2)] = make_float2(va[i].z, vb[i].z); line[npos(x + 3)] = make_float2(va[i].w, vb[i].w);
-                const float4 p = pa[i], q4 = pb[i];
-                pa[i] = make_float4(fmaxf(va[i].x, 0.f) + p.x * p.x, fmaxf(va[i].y, 0.f) + p.y * p.y, fmaxf(va[i].z, 0.f) + p.z * p.z,
-                                    fmaxf(va[i].w, 0.f) + p.w * p.w);
-                pb[i] = make_float4(fmaxf(vb[i].x, 0.f) + q4.x * q4.x, fmaxf(vb[i].y, 0.f) + q4.y * q4.y, fmaxf(vb[i].z, 0.f) + q4.z * q4.z,
-                                    fmaxf(vb[i].w, 0.f) + q4.w * q4.w);
+            if (e < NI) {
+                const int j = e / XG, x = 4 * (e - j * XG);
+                float2 *la = s + j * P::LS, *lv = s + (P::NL / 2 + j) * P::LS;
+                const float4 a0 = va[i][0], a1 = va[i][1], v0 = var4(a0, pa[i][0]), v1 = var4(a1, pa[i][1]);
+                la[npos(x)] = make_float2(a0.x, a1.x); la[npos(x + 1)] = make_float2(a0.y, a1.y);
+                la[npos(x + 2)] = make_float2(a0.z, a1.z); la[npos(x + 3)] = make_float2(a0.w, a1.w);
+                lv[npos(x)] = make_float2(v0.x, v1.x); lv[npos(x + 1)] = make_float2(v0.y, v1.y);
+                lv[npos(x + 2)] = make_float2(v0.z, v1.z); lv[npos(x + 3)] = make_float2(v0.w, v1.w);
             }
         }
     }
@@ -902,25 +928,8 @@ __global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_img_rows_bo
     ZSTAMP(2, 1);
     fft_fwd<P>(s, tw);
     ZSTAMP(2, 2);
-    store_t_split<P>(s, aux.pp, Ta, Tb, sub, yb);
-    __syncthreads();
+    store_t_rows<P>(s, aux.pp, Ta, Tva, sub, yb);
     ZSTAMP(2, 3);
-#pragma unroll
-    for (int i = 0; i < NP; i++) {
-        const int e = (int)threadIdx.x + i * P::LIGHT_THREADS;
-        if (e < NV) {
-            const int q = 4 * e, ll = q / P::L, x = q - ll * P::L;
-            float2* line = s + ll * P::LS;
-            line[npos(x)] = make_float2(pa[i].x, pb[i].x); line[npos(x + 1)] = make_float2(pa[i].y, pb[i].y);
-            line[npos(x + 2)] = make_float2(pa[i].z, pb[i].z); line[npos(x + 3)] = make_float2(pa[i].w, pb[i].w);
-        }
-    }
-    __syncthreads();
-    ZSTAMP(2, 4);
-    fft_fwd<P>(s, tw);
-    ZSTAMP(2, 5);
-    store_t_split<P>(s, aux.pp, Tva, Tvb, sub, yb);
-    ZSTAMP(2, 6);
 }
 
 // column pass of the image pair: D^ = A N^ - B R^, Sn^ = kn^ N^, Sr^ = kr^ R^ and back (U tiles)
@@ -1277,12 +1286,73 @@ static int chunk_plan(bbx_ctx* ctx, zogy_chunk_plan* pl, int yb0, int nyb, int n
     return BBX_OK;
 }
 namespace z3 {
+#ifndef Z3_LDS_PAD
+#define Z3_LDS_PAD 0           // experiments: extra dynamic LDS per workgroup (forces one workgroup per CU)
+#endif
+template <class P> constexpr size_t lds_bytes() { return (size_t)P::NL * P::LS * sizeof(float2) + aux_bytes<P>() + Z3_LDS_PAD; }
+template <class P> constexpr size_t lds_fin_bytes() { return (size_t)(P::NL + 1) * P::LS * sizeof(float2) + aux_bytes<P>() + Z3_LDS_PAD; }
+// dynamic-LDS attribute of the kernels, once per context (= per device and issuing thread) and sub-image side
+template <class P> static int lds_attrs(bbx_ctx* ctx) {
+    if (ctx->zogy3_attr_L == P::L) return BBX_OK;
+    const int lds = (int)lds_bytes<P>();
+    BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_psf_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_cols_fwd<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows_one<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows_one<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_var_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_final_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fin_bytes<P>()));
+    ctx->zogy3_attr_L = P::L;
+    return BBX_OK;
+}
+// frames whose groups of four pixels are aligned and never straddle a sub-image edge: the 16-byte paths of the row kernels
+template <class P> static bool rows_vec4(int nx, int size, int border, const void* a, const void* b, const void* c, const void* d) {
+    return size % 4 == 0 && border % 4 == 0 && nx % 4 == 0 && P::L % 4 == 0 && ((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) % 16 == 0;
+}
+// can a mini sigma image be read in aligned groups of four pixels inside one patch, at most one interval step inside a group
+// (boxes wider than 3 pixels)?
+static inline bool spl_vec4(const bbx_spl& sp) { return sp.pw % 4 == 0 && 3 * sp.nx1 < sp.dx; }
+// cut + row pass of one frame and its variance image -> (Ta, Tva); sigma: a frame (d_sig) or a mini image (sp: its cubic
+// table is made first, in [tab])
+template <class P>
+static void rows_one(bbx_ctx* ctx, const float2* tw, int ny, int nx, int size, int border, const float* d_img, const float* d_sig, const bbx_spl* sp, float4* tab,
+                     float2* Ta, float2* Tva, hipStream_t s) {
+    const int nsx = nx / size, nsub = (ny / size) * nsx;
+    frame1_args fa; fa.a = d_img; fa.sa = d_sig; fa.ny = ny; fa.nx = nx; fa.size = size; fa.border = border; fa.nsx = nsx;
+    const dim3 grow = grid8(P::LB, nsub);
+    if (sp) {
+        bbx_spl t = *sp;
+        t.poly = tab;
+        hipLaunchKernelGGL(k_spl_polytable, dim3((t.cnx + 255) / 256, ny), dim3(256), 0, s, t, ny, tab);
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, (k_img_rows_one<P, true>), grow, dim3(P::LIGHT_THREADS), lds_bytes<P>(), s, fa, tw, Ta, Tva, nsub, t);
+    } else
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, (k_img_rows_one<P, false>), grow, dim3(P::LIGHT_THREADS), lds_bytes<P>(), s, fa, tw, Ta, Tva, nsub, bbx_spl{});
+}
+static inline size_t spl_table_bytes(const bbx_spl& sp, int ny) { return ((size_t)ny * sp.cnx * sizeof(float4) + 255) & ~(size_t)255; }
+// the reference's half of the row pass into a caller's buffer [2][nsub][UNIT] (R rows, then Vr rows): bbx_zogy_refrows_fill
+template <class P>
+static int fill_ref_rows(bbx_ctx* ctx, const float2* d_tw, int ny, int nx, int size, int border, const float* d_ref, const float* d_sig_ref, const bbx_spl* spr,
+                         float2* rows, hipStream_t s) {
+    if (!rows_vec4<P>(nx, size, border, d_ref, d_sig_ref, rows, nullptr) || (spr && !spl_vec4(*spr))) return BBX_ERR_ARG;
+    int rc = lds_attrs<P>(ctx); if (rc) return rc;
+    float4* tab = nullptr;
+    if (spr) { tab = (float4*)bbx_ws(ctx, WS_ZSPL, spl_table_bytes(*spr, ny), &rc); if (rc) return rc; }
+    const size_t unit = (size_t)(ny / size) * (nx / size) * P::UNIT;
+    rows_one<P>(ctx, d_tw, ny, nx, size, border, d_ref, d_sig_ref, spr, tab, rows, rows + unit, s);
+    BBX_LAUNCH_CHECK();
+    return BBX_OK;
+}
 template <class P>
 static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, int nx, int size, int border, const float* d_new, const float* d_ref,
                const float* d_sig_new, const float* d_sig_ref, const bbx_spl* spn, const bbx_spl* spr, const float* d_psf_n, const float* d_psf_r, int S, const float* h_scal,
                float* d_D, float* d_S, float* d_Scorr, float* d_Fpsf, float* d_Fpsferr, hipStream_t s) {
     const int nsy = ny / size, nsx = nx / size, nsub = nsy * nsx;
     int rc;
+    const bool vec4 = rows_vec4<P>(nx, size, border, d_new, d_ref, d_sig_new, d_sig_ref);
+    const float2* ref_rows = ctx->zrows;                    // prepared reference rows (checked by zogy_frame_entry)
+    if (ref_rows && !vec4) return BBX_ERR_ARG;
     // chunks of the final kernel (chunk_plan; cached with the twiddle table)
     const int yb0 = border / P::NL, yb1 = (border + size - 1) / P::NL, nyb = yb1 - yb0 + 1;
     const int nslots = 2 * (ctx->num_cus > 0 ? ctx->num_cus : 256);
@@ -1307,23 +1377,8 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
     float4* cP = (float4*)arr[8];                            // arr[8], arr[9]
     float2 *cK2n = arr[10], *cK2r = arr[11];
     BBX_HIP(hipMemcpyAsync(d_sc, h_scal, (size_t)nsub * sizeof(zscal), hipMemcpyHostToDevice, s));      // pageable source: staged before the call returns
-#ifndef Z3_LDS_PAD
-#define Z3_LDS_PAD 0           // experiments: extra dynamic LDS per workgroup (forces one workgroup per CU)
-#endif
-    const size_t lds = (size_t)P::NL * P::LS * sizeof(float2) + aux_bytes<P>() + Z3_LDS_PAD,
-                 lds_fin = (size_t)(P::NL + 1) * P::LS * sizeof(float2) + aux_bytes<P>() + Z3_LDS_PAD;
-    if (ctx->zogy3_attr_L != P::L) {                       // per context (= per device and issuing thread)
-        BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        BBX_HIP(hipFuncSetAttribute((const void*)k_psf_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        BBX_HIP(hipFuncSetAttribute((const void*)k_cols_fwd<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows_both<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows_both<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        BBX_HIP(hipFuncSetAttribute((const void*)k_var_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        BBX_HIP(hipFuncSetAttribute((const void*)k_final_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fin));
-        ctx->zogy3_attr_L = P::L;
-    }
+    const size_t lds = lds_bytes<P>(), lds_fin = lds_fin_bytes<P>();
+    rc = lds_attrs<P>(ctx); if (rc) return rc;
     const float inv_n2 = 1.0f / ((float)P::L * (float)P::L);
     const dim3 gcol = grid8(P::G, nsub), grow = grid8(P::LB, nsub), blk(P::THREADS);
     const float2* tw = d_tw;
@@ -1343,33 +1398,32 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
     float2 *TK2r = cK2r, *TK2n = cK2n;                      // row-transformed (kr^2)^, (kn^2)^: T layout, column pass inside k_var_cols
     BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_ROWS, k_psf_rows<P>, grid8(nyb_psf, nsub), dim3(P::LIGHT_THREADS), lds, s, U1, U0, inv_n2, tw, TK2r, TK2n, nsub,
                      nyb_psf, wb, d_sc, fs_partial, sub_sc, ctx->d_err);
-    frame_args fa; fa.a = d_new; fa.b = d_ref; fa.sa = nullptr; fa.sb = nullptr; fa.ny = ny; fa.nx = nx; fa.size = size; fa.border = border; fa.nsx = nsx;
-    fa.vec4 = (size % 4 == 0 && border % 4 == 0 && nx % 4 == 0 && P::L % 4 == 0 && ((uintptr_t)d_new | (uintptr_t)d_ref | (uintptr_t)d_sig_new | (uintptr_t)d_sig_ref) % 16 == 0) ? 1 : 0;
+    const float2 *TR = T1, *TVr = T3;
+    if (ref_rows) { TR = ref_rows; TVr = ref_rows + unit; }
     if (spn) {
-        // sigma maps read off their mini images: aligned groups of four pixels inside one patch, at most one interval step
-        // inside a group (boxes wider than 3 pixels)
-        if (!fa.vec4 || spn->pw % 4 || spr->pw % 4 || 3 * spn->nx1 >= spn->dx || 3 * spr->nx1 >= spr->dx) return BBX_ERR_ARG;
-        bbx_spl tn = *spn, tr = *spr;
-        const size_t nbn = (size_t)ny * tn.cnx * sizeof(float4), nbr = (size_t)ny * tr.cnx * sizeof(float4);
-        char* tab = (char*)bbx_ws(ctx, WS_ZSPL, nbn + nbr + 256, &rc); if (rc) return rc;
-        tn.poly = (const float4*)tab; tr.poly = (const float4*)(tab + ((nbn + 255) & ~(size_t)255));
-        hipLaunchKernelGGL(k_spl_polytable, dim3((tn.cnx + 255) / 256, ny), dim3(256), 0, s, tn, ny, (float4*)tn.poly);
-        hipLaunchKernelGGL(k_spl_polytable, dim3((tr.cnx + 255) / 256, ny), dim3(256), 0, s, tr, ny, (float4*)tr.poly);
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, (k_img_rows_both<P, true>), grow, dim3(P::LIGHT_THREADS), lds, s, fa, tw, T0, T1, T2, T3, nsub, tn, tr);
+        // sigma maps read off their mini images
+        if (!vec4 || !spl_vec4(*spn) || (!ref_rows && !spl_vec4(*spr))) return BBX_ERR_ARG;
+        const size_t nbn = spl_table_bytes(*spn, ny);
+        char* tab = (char*)bbx_ws(ctx, WS_ZSPL, nbn + (ref_rows ? 0 : spl_table_bytes(*spr, ny)), &rc); if (rc) return rc;
+        rows_one<P>(ctx, tw, ny, nx, size, border, d_new, nullptr, spn, (float4*)tab, T0, T2, s);
+        if (!ref_rows) rows_one<P>(ctx, tw, ny, nx, size, border, d_ref, nullptr, spr, (float4*)(tab + nbn), T1, T3, s);
     } else
 #ifndef Z3_ROWS_SPLIT
-    if (fa.vec4) {
-        fa.sa = d_sig_new; fa.sb = d_sig_ref;
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, (k_img_rows_both<P, false>), grow, dim3(P::LIGHT_THREADS), lds, s, fa, tw, T0, T1, T2, T3, nsub, bbx_spl{}, bbx_spl{});
+    if (vec4) {
+        rows_one<P>(ctx, tw, ny, nx, size, border, d_new, d_sig_new, nullptr, nullptr, T0, T2, s);
+        if (!ref_rows) rows_one<P>(ctx, tw, ny, nx, size, border, d_ref, d_sig_ref, nullptr, nullptr, T1, T3, s);
     } else
 #endif
     {
+        if (ref_rows) return BBX_ERR_ARG;
+        frame_args fa; fa.a = d_new; fa.b = d_ref; fa.sa = nullptr; fa.sb = nullptr; fa.ny = ny; fa.nx = nx; fa.size = size; fa.border = border; fa.nsx = nsx;
+        fa.vec4 = vec4 ? 1 : 0;
         BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, k_img_rows<P>, grow, dim3(P::LIGHT_THREADS), lds, s, fa, tw, T0, T1, nsub);
         fa.sa = d_sig_new; fa.sb = d_sig_ref;
         BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, k_img_rows<P>, grow, dim3(P::LIGHT_THREADS), lds, s, fa, tw, T2, T3, nsub);
     }
-    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, k_img_cols<P>, gcol, blk, lds, s, T0, T1, cP, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch);      // D, Sn, Sr
-    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_VAR_COLS, k_var_cols<P>, gcol, dim3(P::VAR_THREADS), lds, s, T2, T3, TK2n, TK2r, tw, U3, sub_sc, nsub, wh, &ctx->d_counters[CNT_TICKET]);            // V_S
+    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, k_img_cols<P>, gcol, blk, lds, s, T0, TR, cP, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch);      // D, Sn, Sr
+    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_VAR_COLS, k_var_cols<P>, gcol, dim3(P::VAR_THREADS), lds, s, T2, TVr, TK2n, TK2r, tw, U3, sub_sc, nsub, wh, &ctx->d_counters[CNT_TICKET]);            // V_S
     out_args oa; oa.D = d_D; oa.S = d_S; oa.Scorr = d_Scorr; oa.Fpsf = d_Fpsf; oa.Fpsferr = d_Fpsferr;
     oa.ny = ny; oa.nx = nx; oa.size = size; oa.border = border; oa.nsx = nsx; oa.vec4 = 0;
     const dim3 gfin = grid8(plan->ntasks < nslots ? plan->ntasks : nslots, 1);
@@ -1410,6 +1464,30 @@ static int bbx_zogy3_run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan
     return BBX_ERR_ARG;
 }
 
+static int bbx_zogy3_fill_ref_rows(bbx_ctx* ctx, const float2* d_tw, int L, int ny, int nx, int size, int border, const float* d_ref, const float* d_sig_ref,
+                                   const bbx_spl* spr, float2* rows, hipStream_t s) {
+#define Z3_FILL(...) return z3::fill_ref_rows<z3::Plan<__VA_ARGS__>>(ctx, d_tw, ny, nx, size, border, d_ref, d_sig_ref, spr, rows, s)
+    switch (L) {
+        case 1400: Z3_FILL(Z3_PLAN1400);
+        case 140: Z3_FILL(5, 7, 4);
+        case 128: Z3_FILL(8, 16);
+        case 100: Z3_FILL(5, 5, 4);
+        case 64: Z3_FILL(8, 8);
+    }
+    return BBX_ERR_ARG;
+}
+static size_t bbx_zogy3_unit(int L) {
+#define Z3_UNIT(...) return z3::Plan<__VA_ARGS__>::UNIT
+    switch (L) {
+        case 1400: Z3_UNIT(Z3_PLAN1400);
+        case 140: Z3_UNIT(5, 7, 4);
+        case 128: Z3_UNIT(8, 16);
+        case 100: Z3_UNIT(5, 5, 4);
+        case 64: Z3_UNIT(8, 8);
+    }
+    return 0;
+}
+
 // ---- entry points (include/bbx.h) ------------------------------------------------------------------------------------
 struct zogy_tw_state { float2* d_tw; int L; zogy_chunk_plan plan; };
 
@@ -1440,21 +1518,8 @@ extern "C" int bbx_zogy_candidates(bbx_ctx* ctx, float thr) {
     return BBX_OK;
 }
 
-static int zogy_frame_entry(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_new, const float* d_ref,
-                            const float* d_sig_new, const float* d_sig_ref, const bbx_spline_image* sig_new, const bbx_spline_image* sig_ref,
-                            const float* d_psf_n, const float* d_psf_r, int S,
-                            const float* h_scal, float* d_D, float* d_S, float* d_Scorr, float* d_Fpsf, float* d_Fpsferr, void* stream) {
-    if (!ctx || !d_new || !d_ref || !d_psf_n || !d_psf_r || !h_scal || !d_D || !d_Scorr || !d_Fpsf || !d_Fpsferr) return BBX_ERR_ARG;
-    if (size < 1 || border < 0 || ny < size || nx < size || ny % size || nx % size || S < 1) return BBX_ERR_ARG;
-    const int L = size + 2 * border;
-    if (!bbx_zogy_frame_supported(L) || S > L || (ny / size) * (nx / size) > 4096) return BBX_ERR_ARG;
-    bbx_spl spn, spr;
-    const bool spl = sig_new != nullptr;
-    if (spl) {
-        int rc = bbx_spl_make(sig_new, ny, nx, &spn); if (rc) return rc;
-        rc = bbx_spl_make(sig_ref, ny, nx, &spr); if (rc) return rc;
-    }
-    hipStream_t s = (hipStream_t)stream;
+// the context's twiddle table for sub-images of side L
+static int zogy_tw(bbx_ctx* ctx, int L, zogy_tw_state** out) {
     if (!ctx->zogy2_state) {
         ctx->zogy2_state = calloc(1, sizeof(zogy_tw_state));
         if (!ctx->zogy2_state) return BBX_ERR_NOMEM;
@@ -1475,6 +1540,31 @@ static int zogy_frame_entry(bbx_ctx* ctx, int ny, int nx, int size, int border, 
         if (e != hipSuccess) return bbx_hip_fail(ctx, e, "twiddle table", __LINE__);
         st->L = L;
     }
+    *out = st;
+    return BBX_OK;
+}
+
+static int zogy_frame_entry(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_new, const float* d_ref,
+                            const float* d_sig_new, const float* d_sig_ref, const bbx_spline_image* sig_new, const bbx_spline_image* sig_ref,
+                            const float* d_psf_n, const float* d_psf_r, int S,
+                            const float* h_scal, float* d_D, float* d_S, float* d_Scorr, float* d_Fpsf, float* d_Fpsferr, void* stream) {
+    if (!ctx || !d_new || !d_ref || !d_psf_n || !d_psf_r || !h_scal || !d_D || !d_Scorr || !d_Fpsf || !d_Fpsferr) return BBX_ERR_ARG;
+    if (size < 1 || border < 0 || ny < size || nx < size || ny % size || nx % size || S < 1) return BBX_ERR_ARG;
+    const int L = size + 2 * border;
+    if (!bbx_zogy_frame_supported(L) || S > L || (ny / size) * (nx / size) > 4096) return BBX_ERR_ARG;
+    bbx_spl spn, spr;
+    const bool spl = sig_new != nullptr;
+    if (spl) {
+        int rc = bbx_spl_make(sig_new, ny, nx, &spn); if (rc) return rc;
+        rc = bbx_spl_make(sig_ref, ny, nx, &spr); if (rc) return rc;
+    }
+    // prepared reference rows (bbx_zogy_refrows): only for the very reference, sigma map and geometry they were made of
+    if (ctx->zrows && (d_ref != ctx->zrows_ref || (spl ? (const void*)sig_ref->d_coef : (const void*)d_sig_ref) != ctx->zrows_sig || ny != ctx->zrows_geom[0] ||
+                       nx != ctx->zrows_geom[1] || size != ctx->zrows_geom[2] || border != ctx->zrows_geom[3]))
+        return BBX_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    zogy_tw_state* st;
+    int rc = zogy_tw(ctx, L, &st); if (rc) return rc;
     return bbx_zogy3_run(ctx, st->d_tw, &st->plan, L, ny, nx, size, border, d_new, d_ref, d_sig_new, d_sig_ref, spl ? &spn : nullptr, spl ? &spr : nullptr,
                          d_psf_n, d_psf_r, S, h_scal, d_D, d_S, d_Scorr, d_Fpsf, d_Fpsferr, s);
 }
@@ -1495,6 +1585,50 @@ extern "C" int bbx_zogy_frame_mini(bbx_ctx* ctx, int ny, int nx, int size, int b
     if (!sig_new || !sig_ref) return BBX_ERR_ARG;
     return zogy_frame_entry(ctx, ny, nx, size, border, d_new, d_ref, nullptr, nullptr, sig_new, sig_ref, d_psf_n, d_psf_r, S, h_scal, d_D, d_S, d_Scorr,
                             d_Fpsf, d_Fpsferr, stream);
+}
+
+// ---- prepared reference rows ---------------------------------------------------------------------------------------
+static bool refrows_geom_ok(int ny, int nx, int size, int border) {
+    if (size < 1 || border < 0 || ny < size || nx < size || ny % size || nx % size) return false;
+    const int L = size + 2 * border;
+    return bbx_zogy_frame_supported(L) && (ny / size) * (nx / size) <= 4096 && size % 4 == 0 && border % 4 == 0 && nx % 4 == 0 && L % 4 == 0;
+}
+
+extern "C" size_t bbx_zogy_refrows_bytes(int ny, int nx, int size, int border) {
+    if (!refrows_geom_ok(ny, nx, size, border)) return 0;
+    return 2 * (size_t)(ny / size) * (nx / size) * bbx_zogy3_unit(size + 2 * border) * sizeof(float2);
+}
+
+static int refrows_fill_entry(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_ref, const float* d_sig_ref, const bbx_spline_image* sig_ref,
+                              void* d_rows, void* stream) {
+    if (!ctx || !d_ref || !d_rows || (!d_sig_ref && !sig_ref) || !refrows_geom_ok(ny, nx, size, border)) return BBX_ERR_ARG;
+    bbx_spl spr;
+    if (sig_ref) { int rc = bbx_spl_make(sig_ref, ny, nx, &spr); if (rc) return rc; }
+    const int L = size + 2 * border;
+    zogy_tw_state* st;
+    int rc = zogy_tw(ctx, L, &st); if (rc) return rc;
+    return bbx_zogy3_fill_ref_rows(ctx, st->d_tw, L, ny, nx, size, border, d_ref, d_sig_ref, sig_ref ? &spr : nullptr, (float2*)d_rows, (hipStream_t)stream);
+}
+
+extern "C" int bbx_zogy_refrows_fill(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_ref, const float* d_sig_ref, void* d_rows, void* stream) {
+    if (!d_sig_ref) return BBX_ERR_ARG;
+    return refrows_fill_entry(ctx, ny, nx, size, border, d_ref, d_sig_ref, nullptr, d_rows, stream);
+}
+
+extern "C" int bbx_zogy_refrows_fill_mini(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_ref, const bbx_spline_image* sig_ref, void* d_rows,
+                                          void* stream) {
+    if (!sig_ref) return BBX_ERR_ARG;
+    return refrows_fill_entry(ctx, ny, nx, size, border, d_ref, nullptr, sig_ref, d_rows, stream);
+}
+
+extern "C" int bbx_zogy_refrows(bbx_ctx* ctx, const void* d_rows, int ny, int nx, int size, int border, const float* d_ref, const void* ref_sigma) {
+    if (!ctx) return BBX_ERR_ARG;
+    ctx->zrows = nullptr; ctx->zrows_ref = nullptr; ctx->zrows_sig = nullptr;
+    if (!d_rows) return BBX_OK;
+    if (!d_ref || !ref_sigma || !refrows_geom_ok(ny, nx, size, border) || (uintptr_t)d_rows % 16) return BBX_ERR_ARG;
+    ctx->zrows = (const float2*)d_rows; ctx->zrows_ref = d_ref; ctx->zrows_sig = ref_sigma;
+    ctx->zrows_geom[0] = ny; ctx->zrows_geom[1] = nx; ctx->zrows_geom[2] = size; ctx->zrows_geom[3] = border;
+    return BBX_OK;
 }
 
 // bbx_build_flags (bbx_ctx.hip): any timing / diagnostic switch of this file compiled in?

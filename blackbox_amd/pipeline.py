@@ -329,6 +329,8 @@ class FramePipeline:
         self.subtract = dict(subtract) if subtract else None
         # one lane at a time inside bbx_zogy_frame (BBX_ZOGY_GATE=0 switches the gate off)
         self.ref_bkg_std = None
+        self.ref_rows = None                                         # zogy.RefRows of the run's reference (made with ref_bkg_std)
+        self._ref_lock = threading.Lock()                            # one lane makes the two and hands them over
         self.zogy_gate = None
         self.fpack_in_gate = os.environ.get('BBX_FPACK_GATE', '0') == '1'
         if self.subtract and os.environ.get('BBX_ZOGY_GATE', '1') != '0':
@@ -453,6 +455,7 @@ class FramePipeline:
                 lib.bbx_event_destroy(sl[k])
         self.slots = []
         self.lane_out = None
+        self.ref_rows = self.ref_bkg_std = None
         self.arena.close()
         for c in self.own_ctx:
             c.close()
@@ -668,13 +671,21 @@ class FramePipeline:
             from . import zogy as G
             try:
                 sub = G.optimal_subtraction(ctx, data, new_mask=mask, zogy_gate=self.zogy_gate, ref_bkg_std=self.ref_bkg_std,
-                                            **self.subtract)
+                                            ref_rows=self.ref_rows, **self.subtract)
                 if (self.ref_bkg_std is None and self.subtract.get('ref_is_bkgsub') and self.subtract.get('ref_bkg_std_mini') is not None
                         and self.subtract.get('ref_grid') is None and 'bkg_std_ref' in sub):
-                    # the reference's sigma image is the same for every frame of the run: made once, on whichever lane
-                    # comes first (its stream has finished with it before any other lane can pick it up: see below)
-                    check(lib.bbx_wait(ctx.h, ctx.sp), 'bbx_wait', ctx.h)
-                    self.ref_bkg_std = sub['bkg_std_ref']
+                    with self._ref_lock:
+                        if self.ref_bkg_std is None:
+                            # the reference's sigma image is the same for every frame of the run: made once, on whichever lane
+                            # comes first (its stream has finished with it before any other lane can pick it up: see below);
+                            # and so are the row transforms of the reference and of its variance image inside bbx_zogy_frame:
+                            # one buffer (1 GB at full size) for all lanes, where the geometry has the aligned row path
+                            rows = None
+                            zsize, zborder = sub['header_new']['Z-SIZE'][0], sub['header_new']['Z-BSIZE'][0]
+                            if G.frame_path_supported(zsize + 2 * zborder) and G.RefRows.supported(data.shape, zsize, zborder):
+                                rows = G.RefRows(ctx, sub['ref_bkgsub'], sub['bkg_std_ref'], zsize, zborder)
+                            check(lib.bbx_wait(ctx.h, ctx.sp), 'bbx_wait', ctx.h)
+                            self.ref_rows, self.ref_bkg_std = rows, sub['bkg_std_ref']
                 for k in ('thumbnails', 'thumbnail_png8'):
                     # the thumbnails of the transient candidates leave the GPU on this lane, behind the kernels that made them
                     # (float cut-outs / uint8 display planes: whichever was asked for); the frame's completion reads them

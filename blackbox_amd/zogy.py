@@ -255,10 +255,56 @@ def zogy_frame_outputs(new, want_S=False):
     return [torch.empty_like(new) if (k != 1 or want_S) else None for k in range(5)]
 
 
-def run_zogy_frame(ctx, new, ref, sig_new, sig_ref, psf_n, psf_r, scal, size, border, want_S=False, outs=None):
+class RefRows:
+    """The reference's half of bbx_zogy_frame's row pass (include/bbx.h, bbx_zogy_refrows): the row transforms of the
+    reference frame and of its variance image, made once for a reference that stays the same over many frames.  Holds the
+    buffer and what it was made of (the reference and its sigma map: a frame or a MiniImage); run_zogy_frame uses it for
+    calls with that very reference, sigma map and geometry.  Made on ctx's current stream: a caller that hands the object to
+    other streams or contexts waits for that stream first."""
+    fills = 0                                    # row passes of a reference made so far (tests: once per run, not per frame)
+
+    def __init__(self, ctx, ref, sig_ref, size, border):
+        ny, nx = ref.shape
+        nbytes = int(lib.bbx_zogy_refrows_bytes(ny, nx, int(size), int(border)))
+        if not nbytes or not ref.is_contiguous() or ref.dtype != torch.float32:
+            raise ValueError('no prepared reference rows for this geometry')
+        self.ref, self.sig_ref, self.geom = ref, sig_ref, (ny, nx, int(size), int(border))
+        self.buf = torch.empty(nbytes // 4, dtype=torch.float32, device=ctx.device)
+        if isinstance(sig_ref, MiniImage):
+            check(lib.bbx_zogy_refrows_fill_mini(ctx.h, ny, nx, int(size), int(border), _p(ref), sig_ref.ref(), _p(self.buf), ctx.stream()),
+                  'bbx_zogy_refrows_fill_mini', ctx.h)
+        else:
+            check(lib.bbx_zogy_refrows_fill(ctx.h, ny, nx, int(size), int(border), _p(ref), _p(sig_ref), _p(self.buf), ctx.stream()),
+                  'bbx_zogy_refrows_fill', ctx.h)
+        RefRows.fills += 1
+
+    @staticmethod
+    def supported(shape, size, border):
+        return bool(lib.bbx_zogy_refrows_bytes(int(shape[0]), int(shape[1]), int(size), int(border)))
+
+    def sigma_id(self):
+        return self.sig_ref.coef.data_ptr() if isinstance(self.sig_ref, MiniImage) else self.sig_ref.data_ptr()
+
+    def matches(self, ref, sig_ref, size, border):
+        """made of these very tensors, for this geometry?"""
+        return (ref is self.ref or (ref.data_ptr() == self.ref.data_ptr() and ref.shape == self.ref.shape)) and sig_ref is self.sig_ref \
+            and (ref.shape[0], ref.shape[1], int(size), int(border)) == self.geom
+
+
+def run_zogy_frame(ctx, new, ref, sig_new, sig_ref, psf_n, psf_r, scal, size, border, want_S=False, outs=None, ref_rows=None):
     """ZOGY of whole frames (bbx_zogy_frame): background-subtracted frames + sigma images + PSF
     stamps [nsub, S, S] -> D, S (or None), Scorr, Fpsf, Fpsferr full frames.  sig_new, sig_ref: frames, or both
-    MiniImage (bbx_zogy_frame_mini: the sigma maps are read off their mini images, no frames exist)"""
+    MiniImage (bbx_zogy_frame_mini: the sigma maps are read off their mini images, no frames exist).
+    ref_rows: a RefRows made of (ref, sig_ref): the call skips the reference's row pass (the library refuses rows of
+    another reference, sigma map or geometry)"""
+    if ref_rows is not None:
+        ny, nx = new.shape
+        check(lib.bbx_zogy_refrows(ctx.h, _p(ref_rows.buf), ny, nx, int(size), int(border), _p(ref), C.c_void_p(ref_rows.sigma_id())),
+              'bbx_zogy_refrows', ctx.h)
+        try:
+            return run_zogy_frame(ctx, new, ref, sig_new, sig_ref, psf_n, psf_r, scal, size, border, want_S=want_S, outs=outs)
+        finally:
+            lib.bbx_zogy_refrows(ctx.h, None, 0, 0, 0, 0, None, None)     # the setting never outlives the call it was made for
     ny, nx = new.shape
     nsub = (ny // size) * (nx // size)
     scal = np.ascontiguousarray(scal, dtype=np.float32)
@@ -538,7 +584,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          ref_is_bkgsub=False, ref_bkg_std_mini=None, ref_grid=None, ref_grid_step=32,
                          cat_extract=False, cat_nsigma=5.0, trans_extract=True, frame_stats=True, max_sources=200000,
                          zogy_gate=None, ref_bkg_std=None, sigma_frames=False, thumbnails=False, thumbnail_size=None,
-                         thumbnail_pngs=False):
+                         thumbnail_pngs=False, ref_rows=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -552,6 +598,9 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       ref_bkg_std_mini: its `_bkg_std_mini` image (else measured here);
                       ref_bkg_std: what an earlier call made from it (res['bkg_std_ref']: a MiniImage, or the
                       full-frame sigma image), when the caller keeps it for many frames of the same field
+      ref_rows      : a RefRows made of the reference and of ref_bkg_std by the caller that keeps both for many frames: the
+                      subtraction skips the reference's row transforms (used only where it was made of this call's very
+                      reference, sigma map and geometry; same result bit for bit)
       sigma_frames  : True: the two sigma images are made as full frames (rounds 1-4; bbx_zogy_frame) instead of
                       being read off their mini images inside the kernels (bbx_zogy_frame_mini)
       ref_grid      : projection lattice (coadd.projection_grid) when the reference lives on
@@ -719,12 +768,13 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         outs = zogy_frame_outputs(work)                           # allocated on the caller's stream, filled inside the gate
         sub_pn, sub_pr = sub_pn.contiguous(), sub_pr.contiguous()
         nsig_cand = float(settings.transient_nsigma if nsigma is None else nsigma)
+        rows = ref_rows if ref_rows is not None and ref_rows.matches(rwork, rbstd, size, border) else None
 
         def zogy_frame_call():
             # the kernel that writes Scorr lists the pixels above the transient threshold for the peak search below
             check(lib.bbx_zogy_candidates(ctx.h, nsig_cand), 'bbx_zogy_candidates', ctx.h)
             with (zogy_gate or _NoGate()):
-                return run_zogy_frame(ctx, work, rwork, bstd, rbstd, sub_pn, sub_pr, scal, size, border, outs=outs)
+                return run_zogy_frame(ctx, work, rwork, bstd, rbstd, sub_pn, sub_pr, scal, size, border, outs=outs, ref_rows=rows)
         D, _, Scorr, Fpsf, Fpsferr = zogy_frame_call()
         res['D'], res['Scorr'], res['Fpsf'], res['Fpsferr'] = D, Scorr, Fpsf, Fpsferr
     else:

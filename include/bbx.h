@@ -173,7 +173,7 @@ int  bbx_copy_async(void *dst, const void *src, size_t nbytes, int kind, void *s
 #define BBX_PROF_ZOGY_FINAL 7  /* k_final_rows of bbx_zogy_frame (1 launch / frame) */
 #define BBX_PROF_Z_PSF_COLS 8  /* the other kernels of bbx_zogy_frame (LDS-pass core), one slot each: k_psf_cols, */
 #define BBX_PROF_Z_PSF_ROWS 9  /*   k_psf_rows, */
-#define BBX_PROF_Z_IMG_ROWS 10 /*   k_img_rows (2 launches / frame), */
+#define BBX_PROF_Z_IMG_ROWS 10 /*   k_img_rows_one (2 launches / frame; 1 with prepared reference rows), */
 #define BBX_PROF_Z_IMG_COLS 11 /*   k_img_cols, */
 #define BBX_PROF_Z_VAR_COLS 12 /*   k_var_cols, */
 #define BBX_PROF_Z_PSF_DFT 13  /*   k_psf_rowdft (the stamps' row DFTs, in front of k_psf_cols) */
@@ -592,6 +592,32 @@ int bbx_zogy_frame_mini(bbx_ctx *ctx, int ny, int nx, int size, int border, cons
                         const float *d_psf_n, const float *d_psf_r, int S, const float *h_scal,
                         float *d_D, float *d_S, float *d_Scorr, float *d_Fpsf, float *d_Fpsferr,
                         void *stream);
+
+/* Prepared reference rows.  The row pass of bbx_zogy_frame transforms each side on its own: the new frame and its variance
+ * image in one launch, the reference and its variance image in another (the two-for-one transforms pair neighbouring rows
+ * of one image).  The reference's half depends on d_ref, its sigma map and the geometry alone; a caller whose
+ * reference stays the same from frame to frame (one --ref per image list) makes it once, into a buffer of its own, and
+ * tells the contexts that run its frames.  The library keeps no copy and cannot see whether the reference's pixels changed:
+ * the buffer, and the promise that it still belongs to d_ref, are the caller's.
+ *   bbx_zogy_refrows_bytes      : size of the buffer for this geometry (2 half spectra per sub-image, 1.01 GB for 64
+ *                                 sub-images of 1400^2); 0 where the geometry has no aligned row path (size, border, nx
+ *                                 multiples of 4, a supported sub-image side)
+ *   bbx_zogy_refrows_fill[_mini]: the reference's row pass into d_rows (16-byte aligned) on the stream, with the sigma map
+ *                                 as a frame or as its mini image -- the same kernel on the same data as an unprepared
+ *                                 bbx_zogy_frame[_mini] call runs, so the results with and without are equal bit for bit
+ *   bbx_zogy_refrows            : sticky, per context (like bbx_zogy_candidates): the following bbx_zogy_frame[_mini] calls
+ *                                 of this context skip the reference's row pass and read d_rows instead.  ref_sigma is the
+ *                                 reference sigma's identity: d_sig_ref, or sig_ref->d_coef of the mini form.  A frame call
+ *                                 with another d_ref, reference sigma, ny, nx, size or border returns BBX_ERR_ARG rather than
+ *                                 use rows of another reference.  d_rows = NULL clears the setting (the other arguments are
+ *                                 then ignored).  One buffer may serve several contexts once its fill has completed. */
+size_t bbx_zogy_refrows_bytes(int ny, int nx, int size, int border);
+int bbx_zogy_refrows_fill(bbx_ctx *ctx, int ny, int nx, int size, int border, const float *d_ref,
+                          const float *d_sig_ref, void *d_rows, void *stream);
+int bbx_zogy_refrows_fill_mini(bbx_ctx *ctx, int ny, int nx, int size, int border, const float *d_ref,
+                               const bbx_spline_image *sig_ref, void *d_rows, void *stream);
+int bbx_zogy_refrows(bbx_ctx *ctx, const void *d_rows, int ny, int nx, int size, int border,
+                     const float *d_ref, const void *ref_sigma);
 
 /* ---- a17: PSFEx model evaluation [EXT: zogy.get_psf / psfex poly] ----------------------
  * stamp[s][p] = sum_k terms[s][k] * basis[k][p]: terms [nsrc][ncoef] f32 = the polynomial

@@ -31,11 +31,11 @@ outs = G.run_zogy_frame(ctx, new, ref, sn, sr, psf, psf, scal, 1320, 40)
 torch.cuda.synchronize()
 lib.bbx_z3_stamps(C.c_void_p(0))
 a = buf.cpu().numpy().reshape(6, NWG, 16)
-names = ['k_psf_cols', 'k_psf_rows', 'k_img_rows_both', 'k_img_cols', 'k_var_cols', 'k_final_rows']
+names = ['k_psf_cols', 'k_psf_rows', 'k_img_rows_one', 'k_img_cols', 'k_var_cols', 'k_final_rows']
 phases = {
     'k_psf_cols': ['aux+zero', 'stampDFT_n', 'fft_n', 'park+zero', 'stampDFT_r', 'fft_r', 'coef loop(write A,B,Sd)', 'inv kr', 'store_win+unpark', 'inv kn', 'store_win+reduce'],
     'k_psf_rows': ['aux', 'load_u_pair', 'inv', 'square', 'fwd', 'store_t'],
-    'k_img_rows_both': ['aux+load4frames+lds', 'fwd(N,R)', 'store_t', 'unpark V', 'fwd(V)', 'store_t'],
+    'k_img_rows_one': ['aux+load frame+sigma+lds', 'fwd(a,V)', 'store_t'],      # (the reference's launch: the last to write)
     'k_img_cols': ['aux+load TN(+fetch TR)', 'fwd N', 'park+pack TR', 'fwd R', 'coef loop(read A,B,Sd)', 'inv Sr', 'store+unpark', 'inv Sn', 'store+unpark', 'inv D', 'store'],
     'k_var_cols': ['aux+load k2n win', 'fwd k2n', 'coef+load TVn', 'fwd Vn', 'mul+load k2r win', 'fwd k2r', 'coef+load TVr', 'fwd Vr', 'combine', 'inv', 'store'],
     'k_final_rows': ['aux + first loads issued', 'the chunk of row blocks'],
