@@ -64,6 +64,7 @@ struct bbx_ctx {
     void*  zogy_state;         // per-context FFT plans / work buffer of bbx_zogy.hip (NULL until first use)
     void*  zogy2_state;        // twiddle table of bbx_zogy_frame (bbx_zogy3.hip)
     int    zogy_kwin_off;      // BBX_OPT_ZOGY_KWIN_OFF: full-size transforms of the matched-filter kernels (no row window)
+    int    zogy_ksmall_off;    // BBX_OPT_ZOGY_KSMALL_OFF: k_n, k_r through the full grid even where a small grid exists
     int    sat_attr_set;       // dynamic-LDS attribute of k_trail_segment set through this context
     float  zcand_thr;          // bbx_zogy_candidates: > 0: bbx_zogy_frame lists the pixels with |Scorr| >= thr (WS_ZCAND, CNT_ZCAND)
     const float* zcand_img;    // the Scorr frame the list in WS_ZCAND belongs to (NULL: none); consumed by bbx_find_peaks

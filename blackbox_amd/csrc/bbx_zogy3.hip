@@ -117,6 +117,13 @@ template <int R0_, int R1_, int R2_ = 1, int R3_ = 1> struct Plan {
     static constexpr int MINW = L >= 512 ? Z3_MINW : 1, FIN_MINW = L >= 512 ? Z3_FIN_MINW : 1;
 };
 
+// The matched-filter kernels on a small grid: a plan of side M = L / F with its own line count, and
+// which sub-image sides have one.  Of a PlanN only L, H, LP, LS, the radices and NL are used.
+template <int NL_, int... R> struct PlanN : Plan<R...> { static constexpr int NL = NL_; };
+template <class P> struct small_of { static constexpr bool ok = false; static constexpr int F = 1; typedef P type; };
+template <> struct small_of<Plan<5, 7, 5, 8>> { static constexpr bool ok = true; static constexpr int F = 5; typedef PlanN<8, 5, 7, 8> type; };
+#define Z3_KS_THREADS 256      // k_ks_cols: 8 lines of 280 points
+
 typedef bbx_v2f __attribute__((may_alias)) v2f_a;     // a float2 of the line buffers read / written as one (re, im) pair
 __device__ __forceinline__ bbx_v2f to_v(float2 a) { return bbx_v2f{a.x, a.y}; }
 __device__ __forceinline__ float2 from_v(bbx_v2f a) { return make_float2(a.x, a.y); }
@@ -137,6 +144,13 @@ typedef float z3_v2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float4 ld_nt(const float4* p) {
 #if Z3_NT
     const z3_v4 v = __builtin_nontemporal_load(reinterpret_cast<const z3_v4*>(p)); return make_float4(v.x, v.y, v.z, v.w);
+#else
+    return *p;
+#endif
+}
+__device__ __forceinline__ float2 ld_nt(const float2* p) {
+#if Z3_NT
+    const z3_v2 v = __builtin_nontemporal_load(reinterpret_cast<const z3_v2*>(p)); return make_float2(v.x, v.y);
 #else
     return *p;
 #endif
@@ -164,6 +178,15 @@ template <class P> __device__ __forceinline__ int ppos(int k) {
     if (P::R2 > 1) { p += (k % P::R2) * (P::L / (P::R0 * P::R1 * P::R2)); k /= P::R2; }
     if (P::R3 > 1) p += k;
     return npos(p);
+}
+// spectral index at position p of a line (before the padding): the inverse of ppos
+template <class P> __device__ __forceinline__ int kofp(int p) {
+    constexpr int S0 = P::L / P::R0, S1 = S0 / P::R1, S2 = S1 / P::R2;
+    int k = p / S0; p -= k * S0;
+    k += P::R0 * (p / S1); p %= S1;
+    if (P::R2 > 1) { k += P::R0 * P::R1 * (p / S2); p %= S2; }
+    if (P::R3 > 1) k += P::R0 * P::R1 * P::R2 * p;
+    return k;
 }
 
 // one radix-R pass over blocks of B entries of NLINES lines (B / R = M butterflies per block).  (A thread taking the same
@@ -587,7 +610,10 @@ __global__ __launch_bounds__(256) void k_psf_rowdft(const float* __restrict__ ps
         if (j0 + jj < S) Q[(((size_t)which * nsub + sub) * S + (j0 + jj)) * P::HP + kx] = acc[jj];
 }
 
-template <class P>
+// KS (small grid): k_n^, k_r^ are not taken back to real space here.  Their entries with ky and kx multiples of F go to the
+// half spectra of the small grid, Ukr[sub][which][kx / F][ky / F] (which: 0 k_r^, 1 k_n^; Ukn then holds the cells of the window
+// check, zeroed here); k_ks_cols and k_ks_rows take them from there.
+template <class P, bool KS>
 __global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_psf_cols(const float2* __restrict__ Q, int S,
                                                          const zscal* __restrict__ sc, const float2* __restrict__ twg,
                                                          float4* __restrict__ cP,
@@ -595,6 +621,10 @@ __global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_psf_cols(const floa
                                                          double* __restrict__ fs_partial, int nsub, int wh) {
     extern __shared__ float2 s[];
     __shared__ double red[5][P::THREADS / 64];
+    if (KS && blockIdx.x == 0) {
+        float* kchk = reinterpret_cast<float*>(Ukn);
+        for (int i = threadIdx.x; i < 4 * nsub; i += blockDim.x) kchk[i] = 0.f;
+    }
     WG_TASK(P::G, nsub, g, sub);
     ZSTAMP_HEAD(0);
     const aux_t aux = aux_setup<P>(s + P::NL * P::LS, twg);
@@ -650,15 +680,25 @@ __global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_psf_cols(const floa
         // k_img_cols gets the two spectra themselves (16 bytes per entry, one load) and forms 1 / sqrt(den) and the
         // coefficients of D^, S_n^, S_r^ from them again (rounds 3-4: A, B and sqrt(den), 20 bytes in three loads)
         st_nt(cP + cbase + e, cp);
-        s[l * P::LS + npos(p)] = kr;
-        park[k] = kn;
+        if constexpr (KS) {
+            constexpr int F = small_of<P>::F, M = P::L / F, HM = M / 2 + 1;
+            const int ky = kofp<P>(p);
+            if (kx < P::H && kx % F == 0 && ky % F == 0) {
+                const size_t o = ((size_t)sub * 2 * HM + kx / F) * M + ky / F;
+                Ukr[o] = kr; Ukr[o + (size_t)HM * M] = kn;
+            }
+        } else {
+            s[l * P::LS + npos(p)] = kr;
+            park[k] = kn;
+        }
     }
+    const bool win = !KS && 2 * wh < P::L;
+    double e_all = 0.0, e_out = 0.0;
+    if constexpr (!KS) {
     __syncthreads();
     ZSTAMP(0, 7);
     fft_inv<P>(s, tw);
     ZSTAMP(0, 8);
-    const bool win = 2 * wh < P::L;
-    double e_all = 0.0, e_out = 0.0;
     if (win) store_u_win<P>(s, Ukr, sub, g, wh, e_all, e_out); else store_u<P>(s, Ukr, sub, g);
     __syncthreads();
     R_LOOP(k, e, l, p) s[l * P::LS + npos(p)] = park[k];
@@ -667,6 +707,7 @@ __global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_psf_cols(const floa
     fft_inv<P>(s, tw);
     ZSTAMP(0, 10);
     if (win) store_u_win<P>(s, Ukn, sub, g, wh, e_all, e_out); else store_u<P>(s, Ukn, sub, g);
+    }
     fs = wave_sum_f64(fs); sk2n = wave_sum_f64(sk2n); sk2r = wave_sum_f64(sk2r);
     e_all = wave_sum_f64(e_all); e_out = wave_sum_f64(e_out);
     if ((threadIdx.x & 63) == 0) {
@@ -722,6 +763,103 @@ __global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_psf_rows(co
     store_t_split<P>(s, aux.pp, Tkr2, Tkn2, sub, yb);
     ZSTAMP(1, 6);
 }
+
+// ---- k_n, k_r on the small grid ------------------------------------------------------------------------------------------
+// A function supported inside +-wh is given exactly by its spectrum sampled at every F-th frequency: the inverse transform of
+// k^[F i][F j] on the M x M grid (M = L / F) returns k with whatever lies beyond +-M/2 folded in.  The window check therefore
+// measures, per sub-image and kernel, the energy the small grid holds in the rows and columns the window drops (cells
+// kchk[sub][which][all, dropped], in units of sum_x k^2 M^3; float atomics, tested by k_var_cols).
+// Inverse column pass of the small half spectra K[sub][which][jx][i] -> rows Us[sub][which][y][jx] (window rows only)
+template <class P, class PK>
+__global__ __launch_bounds__(Z3_KS_THREADS) void k_ks_cols(const float2* __restrict__ K, const float2* __restrict__ twg, float2* __restrict__ Us,
+                                                           float* __restrict__ kchk, int nsub, int wh) {
+    constexpr int F = P::L / PK::L, M = PK::L, HM = PK::H, HMP = (HM + 7) / 8 * 8, NG = (HM + PK::NL - 1) / PK::NL;
+    extern __shared__ float2 s[];
+    __shared__ double red[2][Z3_KS_THREADS / 64];
+    const int task = (int)blockIdx.x;
+    if (task >= NG * 2 * nsub) return;
+    const int cg = task % NG, ws = task / NG;                      // column group; (sub, which)
+    float2* tws = s + PK::NL * PK::LS;
+    unsigned short* pps = reinterpret_cast<unsigned short*>(tws + M);
+    for (int e = threadIdx.x; e < M; e += blockDim.x) { tws[e] = twg[F * e]; pps[e] = (unsigned short)ppos<PK>(e); }
+    __syncthreads();
+    const float2* src = K + ((size_t)ws * HM + (size_t)cg * PK::NL) * M;
+    for (int e = threadIdx.x; e < PK::NL * M; e += blockDim.x) {
+        const int l = e / M, i = e - l * M;
+        s[l * PK::LS + pps[i]] = (cg * PK::NL + l < HM) ? src[e] : make_float2(0.f, 0.f);
+    }
+    __syncthreads();
+    fft_inv<PK>(s, tws);
+    float2* dst = Us + (size_t)ws * M * HMP;
+    double ea = 0.0, eo = 0.0;
+    for (int e = threadIdx.x; e < PK::NL * M; e += blockDim.x) {
+        const int y = e / PK::NL, l = e - y * PK::NL, jx = cg * PK::NL + l;
+        if (jx >= HM) continue;
+        const float2 v = s[l * PK::LS + npos(y)];
+        const float en = ((jx == 0 || 2 * jx == M) ? 1.f : 2.f) * (v.x * v.x + v.y * v.y);      // Parseval along x
+        ea += (double)en;
+        if (y < wh || y >= M - wh) dst[(size_t)y * HMP + jx] = v; else eo += (double)en;
+    }
+    ea = wave_sum_f64(ea); eo = wave_sum_f64(eo);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = ea; red[1][threadIdx.x >> 6] = eo; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double tot = 0.0;
+        for (int i = 0; i < (int)blockDim.x / 64; i++) tot += red[threadIdx.x][i];
+        atomicAdd(kchk + 2 * ws + threadIdx.x, (float)tot);
+    }
+}
+// NL window rows as (k_r, k_n) pairs: inverse row pass at M -> squares, placed into lines of L points (zero outside
+// [-wh, wh)) -> forward row pass at L, T tiles.  LDS: the lines and tables of side L, then NL lines and the tables of side M
+template <class P, class PK>
+__global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_ks_rows(const float2* __restrict__ Us, float inv_m2, const float2* __restrict__ twg,
+                                                         float2* __restrict__ Tkr2, float2* __restrict__ Tkn2, int nsub, int nyb, int wb,
+                                                         const zscal* __restrict__ sc, const double* __restrict__ fs_partial,
+                                                         sub_scal* __restrict__ sub_sc, int32_t* __restrict__ d_err, float* __restrict__ kchk) {
+    constexpr int F = P::L / PK::L, M = PK::L, HM = PK::H, HMP = (HM + 7) / 8 * 8;
+    extern __shared__ float2 s[];
+    __shared__ double red[2][P::LIGHT_THREADS / 64];
+    WG_TASK(nyb, nsub, ybw, sub);
+    if (ybw == 0 && threadIdx.x < 64) sub_scalars<P>(fs_partial, nsub, sub, sc[sub], false, sub_sc, d_err);
+    const int yb = ybw < wb ? ybw : P::LB - 2 * wb + ybw, wh = wb * P::NL;
+    const aux_t aux = aux_setup<P>(s + P::NL * P::LS, twg);
+    float2* ss = reinterpret_cast<float2*>(reinterpret_cast<char*>(s + P::NL * P::LS) + aux_bytes<P>());
+    float2* tws = ss + P::NL * PK::LS;
+    unsigned short* pps = reinterpret_cast<unsigned short*>(tws + M);
+    for (int e = threadIdx.x; e < M; e += blockDim.x) { tws[e] = twg[F * e]; pps[e] = (unsigned short)ppos<PK>(e); }
+    for (int e = threadIdx.x; e < P::NL * P::LS; e += blockDim.x) s[e] = make_float2(0.f, 0.f);
+    for (int e = threadIdx.x; e < P::NL * PK::LS; e += blockDim.x) ss[e] = make_float2(0.f, 0.f);
+    __syncthreads();
+    const float2 *Ur = Us + (size_t)(2 * sub) * M * HMP, *Un = Ur + (size_t)M * HMP;
+    for (int e = threadIdx.x; e < P::NL * HM; e += blockDim.x) {
+        const int r = e / HM, jx = e - r * HM, y = yb * P::NL + r, ys = y < wh ? y : y - P::L + M;
+        pack_store<PK>(ss + r * PK::LS, pps, jx, Ur[(size_t)ys * HMP + jx], Un[(size_t)ys * HMP + jx]);
+    }
+    __syncthreads();
+    fft_inv<PK, P::NL>(ss, tws);
+    float eor = 0.f, eon = 0.f;
+    for (int e = threadIdx.x; e < P::NL * M; e += blockDim.x) {
+        const int r = e / M, x = e - r * M;
+        const float2 q = ss[r * PK::LS + npos(x)];
+        if (x < wh || x >= M - wh) {
+            const float a = q.x * inv_m2, b = q.y * inv_m2;
+            s[r * P::LS + npos(x < wh ? x : x - M + P::L)] = make_float2(a * a, b * b);
+        } else { eor += q.x * q.x; eon += q.y * q.y; }
+    }
+    __syncthreads();
+    fft_fwd<P>(s, aux.tw, wh);
+    store_t_split<P>(s, aux.pp, Tkr2, Tkn2, sub, yb);
+    double er = wave_sum_f64((double)eor), en = wave_sum_f64((double)eon);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = er; red[1][threadIdx.x >> 6] = en; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double tot = 0.0;
+        for (int i = 0; i < (int)blockDim.x / 64; i++) tot += red[threadIdx.x][i];
+        atomicAdd(kchk + 4 * sub + 2 * threadIdx.x + 1, (float)(tot / (double)M));      // sum_x a^2 = M sum_kx |A|^2
+    }
+}
+template <class PK> constexpr size_t ks_tab_bytes() { return (size_t)PK::L * sizeof(float2) + (((size_t)PK::L * 2 + 15) & ~(size_t)15); }
+template <class PK> constexpr size_t lds_ks_cols_bytes() { return (size_t)PK::NL * PK::LS * sizeof(float2) + ks_tab_bytes<PK>(); }
 
 // forward column pass of one T array -> C layout
 template <class P>
@@ -933,7 +1071,10 @@ __global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_img_rows_on
 }
 
 // column pass of the image pair: D^ = A N^ - B R^, Sn^ = kn^ N^, Sr^ = kr^ R^ and back (U tiles)
-template <class P>
+// PREP (prepared reference, bbx_zogy_refrows): TR is R^ itself, column-transformed by k_cols_fwd (C layout, the order of
+// R_LOOP): a thread loads its own entries into registers behind the transform of N, N^ stays in the lines, and the load of
+// the T_R tiles, its two barriers and one forward transform are gone.
+template <class P, bool PREP>
 __global__ __launch_bounds__(P::THREADS, P::MINW) void k_img_cols(const float2* __restrict__ TN, const float2* __restrict__ TR, const float4* __restrict__ cP,
                                                          const zscal* __restrict__ sc, const float2* __restrict__ twg,
                                                          float2* __restrict__ UD, float2* __restrict__ USn, float2* __restrict__ USr,
@@ -945,6 +1086,28 @@ __global__ __launch_bounds__(P::THREADS, P::MINW) void k_img_cols(const float2* 
     const float2* tw = aux.tw;
     const size_t cbase = (size_t)(sub * P::G + g) * P::NL * P::L;
     load_t_lines<P>(TN, sub, g, s);
+    constexpr int RT = P::THREADS, NE = (P::NL * P::L + RT - 1) / RT;
+    // N^ waits in registers for R^; then one loop makes D^, S_n^ (both parked) and S_r^ (into the lines) from A, B, sqrt(den)
+    float2 park[NE], parkd[NE];
+    // the PSF spectra of this column group: the first half of a thread's entries is on its way while R is transformed, the
+    // second half goes out in one round behind it (a load inside the guarded loop below waits for its own round trip in
+    // every iteration: 8 x 2 700 cycles of this kernel's 95 000 in round 4)
+    constexpr int NC0 = NE / 2;
+    float4 c0[NC0], c1[NE - NC0];
+    float2 rh[PREP ? NE : 1];                                      // PREP: this thread's entries of R^
+    if constexpr (PREP) {
+        {
+            const int t = opaque_tid();
+#pragma unroll
+            for (int k = 0; k < NE; k++) rh[k] = ld_nt(TR + cbase + min(t + k * RT, P::NL * P::L - 1));
+#pragma unroll
+            for (int k = 0; k < NC0; k++) c0[k] = ld_nt(cP + cbase + min(t + k * RT, P::NL * P::L - 1));
+        }
+        __syncthreads();
+        ZSTAMP(3, 1);
+        fft_fwd<P>(s, tw);
+        ZSTAMP(3, 4);
+    } else {
 #ifndef Z3_NO_PREFETCH
     t_regs<P, P::THREADS> rr;                                      // T_R on its way while T_N is transformed
     fetch_t_lines<P, P::THREADS>(TR, sub, g, rr);
@@ -953,9 +1116,6 @@ __global__ __launch_bounds__(P::THREADS, P::MINW) void k_img_cols(const float2* 
     ZSTAMP(3, 1);
     fft_fwd<P>(s, tw);
     ZSTAMP(3, 2);
-    constexpr int RT = P::THREADS, NE = (P::NL * P::L + RT - 1) / RT;
-    // N^ waits in registers for R^; then one loop makes D^, S_n^ (both parked) and S_r^ (into the lines) from A, B, sqrt(den)
-    float2 park[NE], parkd[NE];
     R_LOOP(k, e, l, p) park[k] = s[l * P::LS + npos(p)];
     __syncthreads();
 #ifndef Z3_NO_PREFETCH
@@ -965,11 +1125,6 @@ __global__ __launch_bounds__(P::THREADS, P::MINW) void k_img_cols(const float2* 
 #endif
     __syncthreads();
     ZSTAMP(3, 3);
-    // the PSF spectra of this column group: the first half of a thread's entries is on its way while R is transformed, the
-    // second half goes out in one round behind it (a load inside the guarded loop below waits for its own round trip in
-    // every iteration: 8 x 2 700 cycles of this kernel's 95 000 in round 4)
-    constexpr int NC0 = NE / 2;
-    float4 c0[NC0], c1[NE - NC0];
     {
         const int t = opaque_tid();
 #pragma unroll
@@ -977,6 +1132,7 @@ __global__ __launch_bounds__(P::THREADS, P::MINW) void k_img_cols(const float2* 
     }
     fft_fwd<P>(s, tw);
     ZSTAMP(3, 4);
+    }
     {
         const int t = opaque_tid();
 #pragma unroll
@@ -987,7 +1143,7 @@ __global__ __launch_bounds__(P::THREADS, P::MINW) void k_img_cols(const float2* 
     const float kfn = z.fn * (z.fr * z.fr), kfr = z.fr * (z.fn * z.fn);
     R_LOOP(k, e, l, p) {
         float2* q = s + l * P::LS + npos(p);
-        const float2 r = *q, n = park[k];
+        const float2 r = PREP ? rh[PREP ? k : 0] : *q, n = PREP ? *q : park[k];
         const float4 c = k < NC0 ? c0[k < NC0 ? k : 0] : c1[k >= NC0 ? k - NC0 : 0];      // (Pn^, Pr^); zero in the padding columns kx >= H
         const float2 pn = make_float2(c.x, c.y), pr = make_float2(c.z, c.w);
         const float pn2 = pn.x * pn.x + pn.y * pn.y, pr2 = pr.x * pr.x + pr.y * pr.y;
@@ -1025,13 +1181,20 @@ __global__ __launch_bounds__(P::THREADS, P::MINW) void k_img_cols(const float2* 
 // column pass of the variance pair: V(S)^ = Vn^ (kn^2)^ + Vr^ (kr^2)^ and back (U tiles).  The spectra (kn^2)^, (kr^2)^
 // get their column pass here as well (their row pass is k_psf_rows): a workgroup needs exactly its own column group
 // of them, so they go from the T tiles through the transform into registers and never to HBM as coefficient arrays.
-template <class P>
+// PREP (prepared reference): TVr is Vr^ itself (C layout, k_cols_fwd): loaded into registers behind the transform of k_r^2,
+// whose spectrum then stays in the lines -- no T_Vr tiles, no fourth forward transform.
+template <class P, bool PREP>
 __global__ __launch_bounds__(P::VAR_THREADS, P::VAR_MINW) void k_var_cols(const float2* __restrict__ TVn, const float2* __restrict__ TVr, const float2* __restrict__ Tk2n,
                                                          const float2* __restrict__ Tk2r, const float2* __restrict__ twg,
                                                          float2* __restrict__ UVS, const sub_scal* __restrict__ sub_sc, int nsub, int wh,
-                                                         int32_t* __restrict__ ticket) {
+                                                         int32_t* __restrict__ ticket, const float* __restrict__ kchk, int32_t* __restrict__ d_err) {
     extern __shared__ float2 s[];
     if (blockIdx.x == 0 && threadIdx.x == 0) *ticket = 0;          // the final kernel's chunk counter (next launch on this stream)
+    if (kchk && blockIdx.x == 0) {
+        // small-grid path: what k_n, k_r of a sub-image hold in the rows and columns the window drops (k_ks_cols, k_ks_rows)
+        for (int i = threadIdx.x; i < 2 * nsub; i += blockDim.x)
+            if (!(kchk[2 * i + 1] <= (float)Z3_KWIN_TOL * kchk[2 * i])) atomicOr(d_err, BBX_DERR_PSF_WINDOW);
+    }
     WG_TASK(P::G, nsub, g, sub);
     ZSTAMP_HEAD(4);
     const aux_t aux = aux_setup<P>(s + P::NL * P::LS, twg);
@@ -1062,6 +1225,16 @@ __global__ __launch_bounds__(P::VAR_THREADS, P::VAR_MINW) void k_var_cols(const 
     R_LOOP(k, e, l, p) park[k] = cmul(coef[k], s[l * P::LS + npos(p)]);
     __syncthreads();
     if (win) load_t_lines_win<P>(Tk2r, sub, g, s, wh); else load_t_lines<P>(Tk2r, sub, g, s);
+    if constexpr (PREP) {
+        const size_t cbase = (size_t)(sub * P::G + g) * P::NL * P::L;
+        const int t = opaque_tid();
+#pragma unroll
+        for (int k = 0; k < NE; k++) coef[k] = ld_nt(TVr + cbase + min(t + k * RT, P::NL * P::L - 1));      // Vr^
+        __syncthreads();
+        ZSTAMP(4, 5);
+        fft_fwd<P>(s, tw, win ? wh : 0);
+        ZSTAMP(4, 8);
+    } else {
     constexpr int NH = t_regs<P, P::VAR_THREADS>::N / 4;          // (more of it beside the parked product: spills)
     fetch_t_lines<P, P::VAR_THREADS, 0, NH>(TVr, sub, g, rr);
     __syncthreads();
@@ -1076,10 +1249,11 @@ __global__ __launch_bounds__(P::VAR_THREADS, P::VAR_MINW) void k_var_cols(const 
     ZSTAMP(4, 7);
     fft_fwd<P>(s, tw);
     ZSTAMP(4, 8);
+    }
     const float beta = sub_sc[sub].beta;
     R_LOOP(k, e, l, p) {
         float2* q = s + l * P::LS + npos(p);
-        const float2 v = cmul(coef[k], *q);
+        const float2 v = PREP ? cmul(*q, coef[k]) : cmul(coef[k], *q);          // (kr^2)^ Vr^, the factors in the same order
         *q = make_float2((park[k].x + v.x) * beta, (park[k].y + v.y) * beta);
     }
     __syncthreads();
@@ -1290,19 +1464,27 @@ namespace z3 {
 #define Z3_LDS_PAD 0           // experiments: extra dynamic LDS per workgroup (forces one workgroup per CU)
 #endif
 template <class P> constexpr size_t lds_bytes() { return (size_t)P::NL * P::LS * sizeof(float2) + aux_bytes<P>() + Z3_LDS_PAD; }
+template <class P, class PK> constexpr size_t lds_ks_rows_bytes() { return lds_bytes<P>() + (size_t)P::NL * PK::LS * sizeof(float2) + ks_tab_bytes<PK>(); }
 template <class P> constexpr size_t lds_fin_bytes() { return (size_t)(P::NL + 1) * P::LS * sizeof(float2) + aux_bytes<P>() + Z3_LDS_PAD; }
 // dynamic-LDS attribute of the kernels, once per context (= per device and issuing thread) and sub-image side
 template <class P> static int lds_attrs(bbx_ctx* ctx) {
     if (ctx->zogy3_attr_L == P::L) return BBX_OK;
     const int lds = (int)lds_bytes<P>();
-    BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if constexpr (small_of<P>::ok) {
+        typedef typename small_of<P>::type PK;
+        BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        BBX_HIP(hipFuncSetAttribute((const void*)k_ks_rows<P, PK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ks_rows_bytes<P, PK>()));
+    }
     BBX_HIP(hipFuncSetAttribute((const void*)k_psf_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     BBX_HIP(hipFuncSetAttribute((const void*)k_cols_fwd<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows_one<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows_one<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_var_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_var_cols<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_var_cols<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     BBX_HIP(hipFuncSetAttribute((const void*)k_final_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fin_bytes<P>()));
     ctx->zogy3_attr_L = P::L;
     return BBX_OK;
@@ -1331,7 +1513,9 @@ static void rows_one(bbx_ctx* ctx, const float2* tw, int ny, int nx, int size, i
         BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, (k_img_rows_one<P, false>), grow, dim3(P::LIGHT_THREADS), lds_bytes<P>(), s, fa, tw, Ta, Tva, nsub, bbx_spl{});
 }
 static inline size_t spl_table_bytes(const bbx_spl& sp, int ny) { return ((size_t)ny * sp.cnx * sizeof(float4) + 255) & ~(size_t)255; }
-// the reference's half of the row pass into a caller's buffer [2][nsub][UNIT] (R rows, then Vr rows): bbx_zogy_refrows_fill
+// the reference's spectra into a caller's buffer [2][nsub][UNIT] (R^, then Vr^; C layout, a unit holds G NL L <= UNIT entries):
+// the row pass into the context's T1 / T3 work arrays, then the column pass of each (bbx_zogy_refrows_fill).  The two column
+// launches are not timed: the profile slots count the launches of a frame.
 template <class P>
 static int fill_ref_rows(bbx_ctx* ctx, const float2* d_tw, int ny, int nx, int size, int border, const float* d_ref, const float* d_sig_ref, const bbx_spl* spr,
                          float2* rows, hipStream_t s) {
@@ -1339,8 +1523,13 @@ static int fill_ref_rows(bbx_ctx* ctx, const float2* d_tw, int ny, int nx, int s
     int rc = lds_attrs<P>(ctx); if (rc) return rc;
     float4* tab = nullptr;
     if (spr) { tab = (float4*)bbx_ws(ctx, WS_ZSPL, spl_table_bytes(*spr, ny), &rc); if (rc) return rc; }
-    const size_t unit = (size_t)(ny / size) * (nx / size) * P::UNIT;
-    rows_one<P>(ctx, d_tw, ny, nx, size, border, d_ref, d_sig_ref, spr, tab, rows, rows + unit, s);
+    const int nsub = (ny / size) * (nx / size);
+    const size_t unit = (size_t)nsub * P::UNIT;
+    float2* ws = (float2*)bbx_ws(ctx, WS_CAND, 4 * unit * sizeof(float2), &rc); if (rc) return rc;
+    float2 *T1 = ws + unit, *T3 = ws + 3 * unit;                   // run()'s work arrays of the reference's row pass
+    rows_one<P>(ctx, d_tw, ny, nx, size, border, d_ref, d_sig_ref, spr, tab, T1, T3, s);
+    hipLaunchKernelGGL(k_cols_fwd<P>, grid8(P::G, nsub), dim3(P::THREADS), lds_bytes<P>(), s, T1, d_tw, rows, nsub);
+    hipLaunchKernelGGL(k_cols_fwd<P>, grid8(P::G, nsub), dim3(P::THREADS), lds_bytes<P>(), s, T3, d_tw, rows + unit, nsub);
     BBX_LAUNCH_CHECK();
     return BBX_OK;
 }
@@ -1364,7 +1553,7 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
     // the row DFTs of the stamps + scalars + partial sums
     constexpr int NARR = 12;
     const size_t qunit = 2 * (size_t)nsub * S * P::HP;
-    const size_t bytes = (NARR * unit + 2 * hunit + qunit) * sizeof(float2) + (size_t)nsub * sizeof(zscal) + 5 * (size_t)nsub * P::G * sizeof(double) + (size_t)nsub * sizeof(z3::sub_scal) + 4096;
+    const size_t bytes = (NARR * unit + 2 * hunit + qunit) * sizeof(float2) + (size_t)nsub * sizeof(zscal) + 5 * (size_t)nsub * P::G * sizeof(double) + (size_t)nsub * sizeof(z3::sub_scal) + 4 * (size_t)nsub * sizeof(float) + 4096;
     char* ws = (char*)bbx_ws(ctx, WS_CAND, bytes, &rc); if (rc) return rc;
     float2* arr[NARR]; for (int i = 0; i < NARR; i++) arr[i] = (float2*)ws + (size_t)i * unit;
     float2 *HSn = (float2*)ws + NARR * unit, *HSr = HSn + hunit, *Qdft = HSr + hunit;
@@ -1372,7 +1561,8 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
     zscal* d_sc = (zscal*)p; p += (size_t)nsub * sizeof(zscal);
     p = (char*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
     double* fs_partial = (double*)p; p += 5 * (size_t)nsub * P::G * sizeof(double);
-    sub_scal* sub_sc = (sub_scal*)p;
+    sub_scal* sub_sc = (sub_scal*)p; p += (size_t)nsub * sizeof(sub_scal);
+    float* kchk = (float*)p;                                 // small-grid path: [nsub][2][2] energies of the window check
     float2 *T0 = arr[0], *T1 = arr[1], *T2 = arr[2], *T3 = arr[3], *U0 = arr[4], *U1 = arr[5], *U2 = arr[6], *U3 = arr[7];
     float4* cP = (float4*)arr[8];                            // arr[8], arr[9]
     float2 *cK2n = arr[10], *cK2r = arr[11];
@@ -1394,10 +1584,30 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
     const bool win = 2 * wh < P::L;
     const int wb = win ? wh / P::NL : 0, nyb_psf = win ? 2 * wb : P::LB;
     BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_DFT, k_psf_rowdft<P>, dim3((P::H + 255) / 256, (S + ZQ_J - 1) / ZQ_J, 2 * nsub), dim3(256), 0, s, d_psf_n, d_psf_r, S, tw, Qdft, nsub);
-    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, k_psf_cols<P>, gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, U0, U1, fs_partial, nsub, wh);
     float2 *TK2r = cK2r, *TK2n = cK2n;                      // row-transformed (kr^2)^, (kn^2)^: T layout, column pass inside k_var_cols
-    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_ROWS, k_psf_rows<P>, grid8(nyb_psf, nsub), dim3(P::LIGHT_THREADS), lds, s, U1, U0, inv_n2, tw, TK2r, TK2n, nsub,
-                     nyb_psf, wb, d_sc, fs_partial, sub_sc, ctx->d_err);
+    // Small grid: inside the window k_n, k_r are given by every F-th frequency of their spectra, so their way back to real
+    // space runs at side M = L / F (1 / F^2 of the work); taken where the side has a plan and the window leaves a guard band
+    // of a row block or more below M / 2 (L = 1400: F = 5, M = 280).  BBX_OPT_ZOGY_KSMALL_OFF: the full grid, as the sides without.
+    bool ks = false;
+    if constexpr (small_of<P>::ok) ks = win && !ctx->zogy_ksmall_off && small_of<P>::type::L / 2 - wh >= P::NL;
+    if constexpr (small_of<P>::ok) if (ks) {
+        typedef typename small_of<P>::type PK;
+        constexpr int M = PK::L, HM = PK::H, HMP = (HM + 7) / 8 * 8, NG = (HM + PK::NL - 1) / PK::NL;
+        static_assert(2 * (size_t)HM * M <= P::UNIT && 2 * (size_t)M * HMP <= P::UNIT && P::L % PK::L == 0 && M % P::NL == 0, "small-grid arrays fit a unit");
+        float2 *Ksm = U1, *Us = U2;                          // free until k_img_cols writes the U arrays
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_psf_cols<P, true>), gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, (float2*)kchk, Ksm, fs_partial, nsub, wh);
+        bbx_prof_start(ctx, BBX_PROF_Z_PSF_ROWS, s);          // the two launches as one entry: the slots count frames
+        hipLaunchKernelGGL((k_ks_cols<P, PK>), dim3((unsigned)(NG * 2 * nsub)), dim3(Z3_KS_THREADS), lds_ks_cols_bytes<PK>(), s, Ksm, tw, Us, kchk, nsub, wh);
+        hipLaunchKernelGGL((k_ks_rows<P, PK>), grid8(nyb_psf, nsub), dim3(P::LIGHT_THREADS), (lds_ks_rows_bytes<P, PK>()), s, Us,
+                           1.0f / ((float)M * (float)M), tw, TK2r, TK2n, nsub, nyb_psf, wb, d_sc, fs_partial, sub_sc, ctx->d_err, kchk);
+        bbx_prof_stop(ctx, s);
+    }
+    if (!ks) {
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_psf_cols<P, false>), gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, U0, U1, fs_partial, nsub, wh);
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_ROWS, k_psf_rows<P>, grid8(nyb_psf, nsub), dim3(P::LIGHT_THREADS), lds, s, U1, U0, inv_n2, tw, TK2r, TK2n, nsub,
+                         nyb_psf, wb, d_sc, fs_partial, sub_sc, ctx->d_err);
+    }
+    const float* kchk_c = ks ? kchk : nullptr;
     const float2 *TR = T1, *TVr = T3;
     if (ref_rows) { TR = ref_rows; TVr = ref_rows + unit; }
     if (spn) {
@@ -1422,8 +1632,14 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
         fa.sa = d_sig_new; fa.sb = d_sig_ref;
         BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, k_img_rows<P>, grow, dim3(P::LIGHT_THREADS), lds, s, fa, tw, T2, T3, nsub);
     }
-    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, k_img_cols<P>, gcol, blk, lds, s, T0, TR, cP, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch);      // D, Sn, Sr
-    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_VAR_COLS, k_var_cols<P>, gcol, dim3(P::VAR_THREADS), lds, s, T2, TVr, TK2n, TK2r, tw, U3, sub_sc, nsub, wh, &ctx->d_counters[CNT_TICKET]);            // V_S
+    // D, Sn, Sr; V_S.  Prepared reference: R^, Vr^ come column-transformed (C layout)
+    if (ref_rows) {
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, true>), gcol, blk, lds, s, T0, TR, cP, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch);
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_VAR_COLS, (k_var_cols<P, true>), gcol, dim3(P::VAR_THREADS), lds, s, T2, TVr, TK2n, TK2r, tw, U3, sub_sc, nsub, wh, &ctx->d_counters[CNT_TICKET], kchk_c, ctx->d_err);
+    } else {
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, false>), gcol, blk, lds, s, T0, TR, cP, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch);
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_VAR_COLS, (k_var_cols<P, false>), gcol, dim3(P::VAR_THREADS), lds, s, T2, TVr, TK2n, TK2r, tw, U3, sub_sc, nsub, wh, &ctx->d_counters[CNT_TICKET], kchk_c, ctx->d_err);
+    }
     out_args oa; oa.D = d_D; oa.S = d_S; oa.Scorr = d_Scorr; oa.Fpsf = d_Fpsf; oa.Fpsferr = d_Fpsferr;
     oa.ny = ny; oa.nx = nx; oa.size = size; oa.border = border; oa.nsx = nsx; oa.vec4 = 0;
     const dim3 gfin = grid8(plan->ntasks < nslots ? plan->ntasks : nslots, 1);

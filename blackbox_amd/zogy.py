@@ -15,6 +15,7 @@ from scipy import ndimage
 
 from . import settings
 from ._lib import lib, check, fetch, push, BBXError as _lib_BBXError, SplineImage as _SplineImage
+from ._lib import BBX_OPT_ZOGY_KSMALL_OFF          # noqa: F401  (k_n, k_r through the full grid: tests and timings compare the paths)
 from .catalogs import format_cat, transient_table         # noqa: F401  (zogy.format_cat)
 
 BBX_ERR_OVERFLOW, BBX_ERR_PSFWIN = -4, -6          # include/bbx.h
@@ -256,8 +257,9 @@ def zogy_frame_outputs(new, want_S=False):
 
 
 class RefRows:
-    """The reference's half of bbx_zogy_frame's row pass (include/bbx.h, bbx_zogy_refrows): the row transforms of the
-    reference frame and of its variance image, made once for a reference that stays the same over many frames.  Holds the
+    """The reference's half of bbx_zogy_frame's forward transforms (include/bbx.h, bbx_zogy_refrows): the 2-D half spectra
+    of the reference frame and of its variance image (row pass, then column pass; the name dates from when the buffer held
+    the row transforms only), made once for a reference that stays the same over many frames.  Holds the
     buffer and what it was made of (the reference and its sigma map: a frame or a MiniImage); run_zogy_frame uses it for
     calls with that very reference, sigma map and geometry.  Made on ctx's current stream: a caller that hands the object to
     other streams or contexts waits for that stream first."""
@@ -295,7 +297,7 @@ def run_zogy_frame(ctx, new, ref, sig_new, sig_ref, psf_n, psf_r, scal, size, bo
     """ZOGY of whole frames (bbx_zogy_frame): background-subtracted frames + sigma images + PSF
     stamps [nsub, S, S] -> D, S (or None), Scorr, Fpsf, Fpsferr full frames.  sig_new, sig_ref: frames, or both
     MiniImage (bbx_zogy_frame_mini: the sigma maps are read off their mini images, no frames exist).
-    ref_rows: a RefRows made of (ref, sig_ref): the call skips the reference's row pass (the library refuses rows of
+    ref_rows: a RefRows made of (ref, sig_ref): the call skips the reference's row and column pass (the library refuses rows of
     another reference, sigma map or geometry)"""
     if ref_rows is not None:
         ny, nx = new.shape

@@ -124,6 +124,12 @@ int  bbx_sync(bbx_ctx *ctx, void *stream);
  * median and the list of its wing pixels, and sorts only the boxes where that does not hold (ties, constant boxes); 1: every
  * box is sorted in full (rounds 2-3).  The medians are the same order statistics either way (tests compare the two). */
 #define BBX_OPT_BKG_FULL_SORT 8
+/* BBX_OPT_ZOGY_KSMALL_OFF (default 0): where the sub-image side L has a plan for M = L / f and the row window leaves a guard
+ * band below M / 2 (L = 1400: f = 5, M = 280), bbx_zogy_frame takes k_n, k_r back to real space on the M x M grid, from every
+ * f-th frequency of their spectra: inside the window that is the same function, with whatever lies beyond +-M / 2 folded in.
+ * The window check then measures the energy of k_n and of k_r in the rows and columns of the small grid outside the window
+ * (same bound, same error bit).  1: the full grid, as for the sides without such a plan (same results to float32 rounding). */
+#define BBX_OPT_ZOGY_KSMALL_OFF 9
 int  bbx_set_option(bbx_ctx *ctx, int option, int value);
 /* Host waits that do not spin.  bbx_wait: everything queued on [stream] so far has finished (no error check: bbx_sync does
  * that); bbx_event_wait: [event] (a hipEvent_t, e.g. of bbx_event_create or a framework's) has completed.  sleep_us > 0:
@@ -593,20 +599,24 @@ int bbx_zogy_frame_mini(bbx_ctx *ctx, int ny, int nx, int size, int border, cons
                         float *d_D, float *d_S, float *d_Scorr, float *d_Fpsf, float *d_Fpsferr,
                         void *stream);
 
-/* Prepared reference rows.  The row pass of bbx_zogy_frame transforms each side on its own: the new frame and its variance
+/* Prepared reference (the names keep "rows": the buffer held the row transforms at first; it now holds the finished
+ * spectra).  The row pass of bbx_zogy_frame transforms each side on its own: the new frame and its variance
  * image in one launch, the reference and its variance image in another (the two-for-one transforms pair neighbouring rows
  * of one image).  The reference's half depends on d_ref, its sigma map and the geometry alone; a caller whose
  * reference stays the same from frame to frame (one --ref per image list) makes it once, into a buffer of its own, and
- * tells the contexts that run its frames.  The library keeps no copy and cannot see whether the reference's pixels changed:
+ * tells the contexts that run its frames.  So does the forward column pass of the two: the buffer holds the 2-D half spectra
+ * R^ (first half) and Vr^ (second half), each [sub][column group][entry] in the order the column kernels walk their lines,
+ * and the frame call's column kernels read their entries straight into registers instead of transforming the reference again.  The library keeps no copy and cannot see whether the reference's pixels changed:
  * the buffer, and the promise that it still belongs to d_ref, are the caller's.
  *   bbx_zogy_refrows_bytes      : size of the buffer for this geometry (2 half spectra per sub-image, 1.01 GB for 64
  *                                 sub-images of 1400^2); 0 where the geometry has no aligned row path (size, border, nx
  *                                 multiples of 4, a supported sub-image side)
- *   bbx_zogy_refrows_fill[_mini]: the reference's row pass into d_rows (16-byte aligned) on the stream, with the sigma map
- *                                 as a frame or as its mini image -- the same kernel on the same data as an unprepared
- *                                 bbx_zogy_frame[_mini] call runs, so the results with and without are equal bit for bit
+ *   bbx_zogy_refrows_fill[_mini]: the reference's row pass (into the context's work arrays) and column pass (into d_rows,
+ *                                 16-byte aligned) on the stream, with the sigma map as a frame or as its mini image -- the
+ *                                 same transforms on the same data as an unprepared bbx_zogy_frame[_mini] call runs, so
+ *                                 the results with and without are equal bit for bit
  *   bbx_zogy_refrows            : sticky, per context (like bbx_zogy_candidates): the following bbx_zogy_frame[_mini] calls
- *                                 of this context skip the reference's row pass and read d_rows instead.  ref_sigma is the
+ *                                 of this context skip the reference's row and column pass and read d_rows instead.  ref_sigma is the
  *                                 reference sigma's identity: d_sig_ref, or sig_ref->d_coef of the mini form.  A frame call
  *                                 with another d_ref, reference sigma, ny, nx, size or border returns BBX_ERR_ARG rather than
  *                                 use rows of another reference.  d_rows = NULL clears the setting (the other arguments are
