@@ -381,6 +381,11 @@ class Reducer:
                 sub['thumbnails'] = True
             if par(a.save_thumbnails_pngs, 'save_thumbnails_pngs'):
                 sub['thumbnail_pngs'] = True
+            # fratio, dx, dy measured from the stars matched with the reference instead of --fratio --zogy_dx --zogy_dy,
+            # which stay the fallback of a frame with too few pairs
+            if par(a.zogy_match, 'zogy_match'):
+                sub['match'] = True
+                sub['match_dist'] = par(a.match_dist, 'match_dist_pix')
         return sub
 
     def _thumbnail_products(self, res, base):
@@ -1067,6 +1072,11 @@ def build_parser():
     ap.add_argument('--fratio', type=float, default=1.0, help='flux ratio new / ref (Z-FNR)')
     ap.add_argument('--zogy_dx', type=float, default=0.0, help='[pix] astrometric scatter in x (Z-DXSTD)')
     ap.add_argument('--zogy_dy', type=float, default=0.0)
+    ap.add_argument('--zogy_match', type=str2bool, default=None,
+                    help='measure the flux ratio and dx, dy per sub-image from the stars matched with the reference (Z-FNR, '
+                         'Z-DX, Z-DY and Z-DXSTD, Z-DYSTD, Z-FNRSTD, Z-FNRERR); --fratio --zogy_dx --zogy_dy are the fallback '
+                         '(default: settings.zogy_match)')
+    ap.add_argument('--match_dist', type=float, default=None, help='[pix] largest distance of a star match (settings.match_dist_pix)')
     ap.add_argument('--subimage_size', type=int, default=None)
     ap.add_argument('--flat_norm_sec', type=section, default=None,
                     help='y0:y1,x0:x1: flat normalisation / statistics section (default set_bb.flat_norm_sec of the telescope)')

@@ -133,6 +133,9 @@ SIGNATURES = {
     'bbx_count_objects': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     'bbx_thumbnails': (_i, [_vp, _i, _i, C.POINTER(_vp), _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     'bbx_thumb_png8': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    'bbx_win_centroid': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'bbx_match_mutual': (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
+    'bbx_match_stats': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError if the export is missing

@@ -1065,7 +1065,7 @@ int bbx_spline_zoom_sub(bbx_ctx* ctx, int ny, int nx, const double* d_coef, int 
         uint32_t* clist = nullptr; uint32_t ccap = 0; int32_t* ccnt = &ctx->d_counters[CNT_BCAND];
         if (cmed && (size_t)ny * nx < 0xffffffffull) {
             int rc;
-            ccap = (uint32_t)((size_t)ny * nx / 16 + 1024);
+            ccap = (uint32_t)bbx_cand_cap((size_t)ny * nx);
             clist = (uint32_t*)bbx_ws(ctx, WS_BCAND, (size_t)ccap * sizeof(uint32_t), &rc); if (rc) return rc;
             BBX_HIP(hipMemsetAsync(ccnt, 0, sizeof(int32_t), (hipStream_t)stream));
         }

@@ -136,6 +136,13 @@ enum {
 };
 
 int bbx_hip_fail(bbx_ctx* ctx, hipError_t e, const char* what, int line);
+// entries of a candidate pixel list of a frame of npix pixels (bbx_find_peaks and the kernels that list for it: WS_CCLIST,
+// WS_ZCAND, WS_BCAND): 1/16 of the frame, as ever, for frames of a million pixels and more; a small frame gets min(npix, 65536)
+// entries, so that the star-dense toy frames of the tests fit (a 240 x 480 frame with 300 stars has 3 10^4 pixels above 5 sigma)
+static inline size_t bbx_cand_cap(size_t npix) {
+    const size_t c = npix / 16 + 1024, f = npix < 65536 ? npix : 65536;
+    return c > f ? c : f;
+}
 void bbx_zogy2_release(bbx_ctx* ctx);
 void bbx_fpack_release(bbx_ctx* ctx);     // bbx_fpack.hip: frees the per-stream hint tables (called by bbx_ctx_destroy)
 int bbx_zogy3_supported(int L);

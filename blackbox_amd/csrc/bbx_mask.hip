@@ -816,7 +816,7 @@ extern "C" int bbx_find_peaks(bbx_ctx* ctx, int ny, int nx, const float* d_img, 
     int rc;
     const size_t npix = (size_t)ny * nx;
     if (npix >= 0xffffffffull) return BBX_ERR_ARG;
-    const size_t cap = npix / 16 + 1024;
+    const size_t cap = bbx_cand_cap(npix);
     uint32_t* list = (uint32_t*)bbx_ws(ctx, WS_CCLIST, cap * sizeof(uint32_t), &rc); if (rc) return rc;
     unsigned long long* best = (unsigned long long*)bbx_ws(ctx, WS_STAGE2, cap * sizeof(unsigned long long), &rc); if (rc) return rc;
     int32_t* cnt = &ctx->d_counters[CNT_CC_N];

@@ -1648,7 +1648,7 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
     int32_t* cand_cnt = &ctx->d_counters[CNT_ZCAND];
     ctx->zcand_img = nullptr;
     if (ctx->zcand_thr > 0.f && (size_t)ny * nx < 0xffffffffull) {
-        cand_cap = (uint32_t)((size_t)ny * nx / 16 + 1024);
+        cand_cap = (uint32_t)bbx_cand_cap((size_t)ny * nx);
         cand_list = (uint32_t*)bbx_ws(ctx, WS_ZCAND, (size_t)cand_cap * sizeof(uint32_t), &rc); if (rc) return rc;
         BBX_HIP(hipMemsetAsync(cand_cnt, 0, sizeof(int32_t), s));
         cand_thr = ctx->zcand_thr;

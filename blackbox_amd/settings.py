@@ -80,6 +80,15 @@ size_thumbnails = 100          # [pix] side of the square cut-outs
 thumbnails_dir = None          # PNGs go to {thumbnails_dir}/{image base name}/; None: `thumbnails/` next to the products
 trans_flags_window = 5         # [pix] side of the window around the peak whose mask values make FLAGS_MASK (this project's own)
 
+# ---- flux ratio and dx, dy from matched stars (buildref.py:2782-3014 get_fratio; [EXT] zogy.get_fratio_dxdy) ----
+# Off by default: the subtraction then takes the caller's fratio, dx, dy (--fratio --zogy_dx --zogy_dy) as before.
+zogy_match = False             # measure fratio, dx, dy per sub-image from the stars matched between new frame and reference
+match_dist_pix = 3.5           # [pix] largest distance of a match: dist_max = 2 arcsec (buildref.py:2816) at 0.564 arcsec/px
+match_nmin = 15                # fewer pairs than this: no measurement (nmatch_min, buildref.py:2992)
+match_snr_min = 20.0           # flux / fluxerr a star needs on both sides to enter the statistics (this project's own)
+centroid_radius = 6            # [pix] the windowed centroid reads (2 * radius + 1)^2 pixels around the integer peak
+centroid_niter = 8             # iterations of the windowed centroid
+
 # calibration files of a reduction (explicit paths; the date-based master selection
 # of master_prep, blackbox.py:4625-4905, is blackbox_amd.masters, run by --master_date)
 bad_pixel_mask = None      # path containing 'bpm' -> 'bpm_{filt}' (blackbox.py:4386)

@@ -293,6 +293,175 @@ class RefRows:
             and (ref.shape[0], ref.shape[1], int(size), int(border)) == self.geom
 
 
+# ---- flux ratio and dx, dy from matched stars ---------------------------------------------
+# buildref.py:2782-3014 (get_fratio, "simplified version of zogy.get_fratio_dxdy") shows the computation; [EXT]
+# get_fratio_dxdy, get_matches, get_mean_fratio are not in the reference tree (conventions: include/bbx.h).
+MATCH_COLS = ('n_qualifying', 'n_fr', 'med_fr', 'mean_fr', 'std_fr', 'wmean_fr', 'werr_fr', 'n_dx', 'med_dx', 'mean_dx', 'std_dx',
+              'n_dy', 'med_dy', 'mean_dy', 'std_dy', 'stride')
+_MC = {k: i for i, k in enumerate(MATCH_COLS)}
+
+
+def window_sigma(stamps):
+    """window sigma of the centroid from unit-sum PSF stamps [..., S, S] (device tensor or numpy): sigma_w =
+    sqrt(1 / (4 pi sum P^2)), the sigma of the Gaussian with the stamp's effective area.  Stays where the stamps are"""
+    if torch.is_tensor(stamps):
+        return (1.0 / (4.0 * np.pi * (stamps * stamps).sum(dim=(-2, -1)))).sqrt().to(torch.float32).contiguous()
+    stamps = np.asarray(stamps, np.float64)
+    return np.sqrt(1.0 / (4.0 * np.pi * (stamps * stamps).sum(axis=(-2, -1))))
+
+
+def win_centroid(ctx, img, d_ys, d_xs, d_sigw, size, nsy, nsx, radius=None, niter=None):
+    """bbx_win_centroid: windowed centroids of the sources at the int32 device peaks (d_ys, d_xs) of the frame [img] ->
+    device float32 [n, 2] = (dy, dx) relative to the integer peak, NaN where there is none.  No host wait"""
+    radius = settings.centroid_radius if radius is None else radius
+    niter = settings.centroid_niter if niter is None else niter
+    if img.dim() != 2 or img.dtype != torch.float32 or not img.is_contiguous():
+        raise ValueError('contiguous 2-D float32 frame expected')
+    n = int(d_ys.numel())
+    off = torch.empty((n, 2), dtype=torch.float32, device=ctx.device)
+    check(lib.bbx_win_centroid(ctx.h, img.shape[0], img.shape[1], _p(img), n, _p(d_ys), _p(d_xs), _p(d_sigw), int(size), int(nsy), int(nsx),
+                               int(radius), int(niter), _p(off), ctx.stream()), 'bbx_win_centroid', ctx.h)
+    return off
+
+
+def match_mutual(ctx, a, b, dist_max):
+    """bbx_match_mutual of two lists (d_ys, d_xs, d_off), each sorted by (y, x) -> device int32 [n_a]: index into b, or -1"""
+    n_a, n_b = int(a[0].numel()), int(b[0].numel())
+    d_match = torch.empty(n_a, dtype=torch.int32, device=ctx.device)
+    d_best = torch.empty(n_b, dtype=torch.int32, device=ctx.device)
+    check(lib.bbx_match_mutual(ctx.h, n_a, _p(a[0]), _p(a[1]), _p(a[2]), n_b, _p(b[0]), _p(b[1]), _p(b[2]), float(dist_max),
+                               _p(d_best), _p(d_match), ctx.stream()), 'bbx_match_mutual', ctx.h)
+    return d_match
+
+
+def empty_match_table(nsub):
+    """the table of a frame without a pair: counts 0, stride 1, NaN elsewhere (what bbx_match_stats writes for empty segments)"""
+    t = np.full((nsub + 1, 16), np.nan)
+    t[:, [_MC['n_qualifying'], _MC['n_fr'], _MC['n_dx'], _MC['n_dy']]] = 0.0
+    t[:, _MC['stride']] = 1.0
+    return t
+
+
+def match_stats(ctx, a, b, d_match, size, nsy, nsx, snr_min):
+    """bbx_match_stats of the lists a, b = (d_ys, d_xs, d_off, d_flux, d_err) matched by d_match -> device float64
+    [nsy * nsx + 1, 16] (MATCH_COLS; last row: the whole frame)"""
+    n_a, n_b = int(a[0].numel()), int(b[0].numel())
+    if not n_a:
+        return torch.from_numpy(empty_match_table(nsy * nsx)).to(ctx.device)
+    out = torch.empty((nsy * nsx + 1, 16), dtype=torch.float64, device=ctx.device)
+    check(lib.bbx_match_stats(ctx.h, n_a, *[_p(t) for t in a], n_b, *[_p(t) for t in b], _p(d_match), int(size), int(nsy), int(nsx),
+                              float(snr_min), _p(out), ctx.stream()), 'bbx_match_stats', ctx.h)
+    return out
+
+
+_MATCH_HDR = (('Z-DX', 'med_dx', '[pix] dx median offset full image'), ('Z-DY', 'med_dy', '[pix] dy median offset full image'),
+              ('Z-DXSTD', 'std_dx', '[pix] dx sigma (STD) offset full image'), ('Z-DYSTD', 'std_dy', '[pix] dy sigma (STD) offset full image'),
+              ('Z-FNR', 'med_fr', 'median flux ratio (Fnew/Fref) full image'), ('Z-FNRSTD', 'std_fr', 'sigma (STD) flux ratio (Fnew/Fref) full image'),
+              ('Z-FNRERR', 'werr_fr', 'weighted error flux ratio (Fnew/Fref) full image'))
+
+
+def match_scalars(table, fratio, dx, dy, nmin):
+    """the table of bbx_match_stats [nsub + 1, 16] (host) -> dict(success, fratio_sub, dx_sub, dy_sub [nsub], header).
+    A tile with n_fr >= nmin takes its clipped median ratio; with n_dx >= nmin sqrt(mean_dx^2 + std_dx^2) (the scatter about
+    zero that enters V(S)), likewise dy; a tile below nmin takes the full-frame row's value.  A full-frame row with any of the
+    three counts below nmin: success False, every tile takes the caller's fratio, dx, dy (one number or one per tile).
+    header: Z-DX, Z-DY, Z-DXSTD, Z-DYSTD, Z-FNR, Z-FNRSTD, Z-FNRERR from the full-frame row (set_qc.py:370-375, 425); without
+    success the caller's medians for Z-DX, Z-DY, Z-FNR and the string 'None', set_qc's default, for the other four.  Pure numpy"""
+    table = np.asarray(table, np.float64)
+    nsub = table.shape[0] - 1
+    full = table[nsub]
+    caller = [np.broadcast_to(np.asarray(v, np.float64), (nsub,)).copy() for v in (fratio, dx, dy)]
+    success = bool(full[_MC['n_fr']] >= nmin and full[_MC['n_dx']] >= nmin and full[_MC['n_dy']] >= nmin)
+    if not success:
+        fall = {'Z-DX': float(np.median(dx)), 'Z-DY': float(np.median(dy)), 'Z-FNR': float(np.median(fratio))}
+        hdr = {key: (fall.get(key, 'None'), comment) for key, _, comment in _MATCH_HDR}
+        return dict(success=False, fratio_sub=caller[0], dx_sub=caller[1], dy_sub=caller[2], header=hdr)
+    hdr = {}
+
+    def scatter(rows, q):
+        return np.sqrt(rows[..., _MC['mean_' + q]] ** 2 + rows[..., _MC['std_' + q]] ** 2)
+    t = table[:nsub]
+    out = [np.where(t[:, _MC['n_fr']] >= nmin, t[:, _MC['med_fr']], full[_MC['med_fr']])]
+    for q in ('dx', 'dy'):
+        out.append(np.where(t[:, _MC['n_' + q]] >= nmin, scatter(t, q), scatter(full, q)))
+    for key, col, comment in _MATCH_HDR:
+        hdr[key] = (float(full[_MC[col]]), comment)
+    return dict(success=True, fratio_sub=out[0], dx_sub=out[1], dy_sub=out[2], header=hdr)
+
+
+class RefCatalog:
+    """The reference's half of the star match, made once for a reference that stays the same over many frames: the peaks of
+    the reference as the subtraction sees it (background-subtracted, on the new frame's grid) above cat_nsigma x the median
+    of its sigma mini image, those on masked pixels dropped, with their PSF-weighted fluxes (psf_optflux) and windowed
+    centroids (bbx_win_centroid), all on the device in (y, x) order.  Holds what it was made of (the reference and its sigma
+    map: a frame or a MiniImage); optimal_subtraction uses it for calls with that very reference, sigma map and geometry.
+    Made on ctx's current stream with host waits (once per run): a caller that hands the object to other streams waits for
+    that stream first."""
+    builds = 0                                   # catalogues made so far (tests: once per run, not per frame)
+
+    def __init__(self, ctx, ref, sig_ref, ref_mask, psf_ref, size, border, cat_nsigma=5.0, sigma_median=None, sub_psfs=None,
+                 max_sources=200000):
+        if ref.dim() != 2 or ref.dtype != torch.float32 or not ref.is_contiguous():
+            raise ValueError('contiguous 2-D float32 reference expected')
+        ny, nx = ref.shape
+        size, border = int(size), int(border)
+        nsy, nsx = ny // size, nx // size
+        if sigma_median is None:
+            if isinstance(sig_ref, MiniImage):
+                raise ValueError('sigma_median (median of the sigma mini image) is needed with a MiniImage')
+            sigma_median = float(np.median(fetch(ctx, sig_ref)))
+        self.ref, self.sig_ref, self.geom = ref, sig_ref, (ny, nx, size, border)
+        sub_pr = sub_psfs if sub_psfs is not None else subimage_psfs(ctx, psf_ref, nsy, nsx, size)
+        thr = float(cat_nsigma) * float(sigma_median)
+        if np.isfinite(thr) and thr > 0:
+            ys, xs, pk = find_peaks_arrays(ctx, ref, thr, max_out=max_sources)
+        else:
+            ys = xs = np.zeros(0, np.int32); pk = np.zeros(0, np.float32)
+        keep = pk > 0
+        if ref_mask is not None and ys.size:
+            d_ys, d_xs = push(ctx, ys.astype(np.int64), xs.astype(np.int64))
+            keep &= fetch(ctx, ref_mask[d_ys, d_xs]) == 0
+        ys, xs = ys[keep], xs[keep]
+        self.n = int(ys.size)
+        dev = ctx.device
+        if self.n:
+            stamps = source_psfs(ctx, psf_ref, sub_pr, ys, xs, nsx, size)
+            self.flux, self.err = psf_optflux(ctx, ref, sig_ref, stamps, ys, xs, v_is_sigma=True)
+            self.ys, self.xs = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
+            self.off = win_centroid(ctx, ref, self.ys, self.xs, window_sigma(sub_pr), size, nsy, nsx)
+        else:
+            self.ys = self.xs = torch.empty(0, dtype=torch.int32, device=dev)
+            self.flux = self.err = torch.empty(0, dtype=torch.float32, device=dev)
+            self.off = torch.empty((0, 2), dtype=torch.float32, device=dev)
+        RefCatalog.builds += 1
+
+    def lists(self):
+        return self.ys, self.xs, self.off, self.flux, self.err
+
+    def matches(self, ref, sig_ref, size, border):
+        """made of these very tensors, for this geometry?"""
+        return (ref is self.ref or (ref.data_ptr() == self.ref.data_ptr() and ref.shape == self.ref.shape)) and sig_ref is self.sig_ref \
+            and (ref.shape[0], ref.shape[1], int(size), int(border)) == self.geom
+
+
+def match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, dist_max=None, snr_min=None):
+    """queue the new frame's half of the star match behind its photometry: centroids of the peaks (ys, xs: host, sorted by
+    (y, x)) of the background-subtracted frame [work], the mutual match against the RefCatalog [rc] and the table.  Peaks
+    on masked pixels (d_mk != 0) are taken out on the device: NaN offset (matches nothing) and flux 0.
+    -> device (table float64 [nsub + 1, 16], number of pairs int64 [1]); no host wait"""
+    dist_max = settings.match_dist_pix if dist_max is None else dist_max
+    snr_min = settings.match_snr_min if snr_min is None else snr_min
+    d_y32, d_x32 = push(ctx, np.asarray(ys, np.int32), np.asarray(xs, np.int32))
+    off = win_centroid(ctx, work, d_y32, d_x32, window_sigma(sub_pn), size, nsy, nsx)
+    bad = d_mk != 0
+    off = torch.where(bad[:, None], torch.full_like(off, float('nan')), off).contiguous()
+    f_m = torch.where(bad, torch.zeros_like(f), f).contiguous()
+    a = (d_y32, d_x32, off, f_m, e)
+    d_match = match_mutual(ctx, a[:3], rc.lists()[:3], dist_max)
+    d_tab = match_stats(ctx, a, rc.lists(), d_match, size, nsy, nsx, snr_min)
+    return d_tab, (d_match >= 0).sum().reshape(1)
+
+
 def run_zogy_frame(ctx, new, ref, sig_new, sig_ref, psf_n, psf_r, scal, size, border, want_S=False, outs=None, ref_rows=None):
     """ZOGY of whole frames (bbx_zogy_frame): background-subtracted frames + sigma images + PSF
     stamps [nsub, S, S] -> D, S (or None), Scorr, Fpsf, Fpsferr full frames.  sig_new, sig_ref: frames, or both
@@ -586,7 +755,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          ref_is_bkgsub=False, ref_bkg_std_mini=None, ref_grid=None, ref_grid_step=32,
                          cat_extract=False, cat_nsigma=5.0, trans_extract=True, frame_stats=True, max_sources=200000,
                          zogy_gate=None, ref_bkg_std=None, sigma_frames=False, thumbnails=False, thumbnail_size=None,
-                         thumbnail_pngs=False, ref_rows=None):
+                         thumbnail_pngs=False, ref_rows=None, match=False, ref_catalog=None, match_dist=None, match_nmin=None,
+                         match_snr_min=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -614,6 +784,14 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
       thumbnail_pngs: True: res['thumbnail_png8'], device uint8 [n, 4, S, S]: their display planes (blackbox.py:2786-2826)
                       either switch adds 'flags' (FLAGS_MASK: the masks under the peak) to each transient; both off: no
                       kernel of bbx_thumb.hip is launched and the result has none of these keys
+      match         : True (with a reference and both PSFs): fratio, dx, dy of every sub-image are measured from the stars matched
+                      between the new frame and the reference (bbx_win_centroid, bbx_match_mutual, bbx_match_stats; match_scalars)
+                      and go into the subtraction in place of the caller's, which stay the fallback where the frame has fewer
+                      than match_nmin pairs; res['match'] = dict(success, n_new, n_ref, n_pairs, table, fratio_sub, dx_sub,
+                      dy_sub), res['ref_catalog'], and header_trans gets Z-DXSTD, Z-DYSTD, Z-FNRSTD, Z-FNRERR.  False: no kernel
+                      of bbx_match.hip is launched, no such keys.  match_dist [pix], match_nmin, match_snr_min: settings
+      ref_catalog   : a RefCatalog made of the reference and of ref_bkg_std by the caller that keeps both for many frames (used
+                      only where it was made of this call's very reference, sigma map and geometry; same result bit for bit)
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
             header (= header_new additions), header_trans)"""
     size = subimage_size or settings.subimage_size
@@ -625,11 +803,12 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     nsy, nsx = ny // size, nx // size
     nsub = nsy * nsx
     have_ref = ref is not None and trans_extract
+    do_match = bool(match) and have_ref and psf_new is not None and psf_ref is not None
 
     # ---- new frame: mesh, subtraction, sigma image, variance
     mini, mini_std = get_back(ctx, new, new_mask, bkg_boxsize=box)
     work = torch.empty_like(new)
-    want_cat = cat_extract and psf_new is not None
+    want_cat = (cat_extract or do_match) and psf_new is not None
     if want_cat:
         # the kernel that writes the background-subtracted frame lists the pixels above cat_nsigma x S-BKGSTD for the
         # catalogue's peak search; S-BKGSTD = median of the sigma mini image, taken on the device for that
@@ -678,17 +857,68 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
 
     sub_pn = subimage_psfs(ctx, psf_new, nsy, nsx, size) if psf_new is not None else None
 
+    def prepare_reference():
+        """the reference frame on the new frame's grid: background-subtracted image + sigma image (before the star match
+        where that is asked for, else where the subtraction needs it)"""
+        nonlocal bstd
+        rny, rnx = ref.shape
+        if ref_is_bkgsub:
+            rwork = ref
+            if ref_bkg_std_mini is None:
+                _, rstd_mini = get_back(ctx, ref, ref_mask, bkg_boxsize=box)
+                sdr = fetch(ctx, rstd_mini)
+            else:
+                sdr = np.asarray(ref_bkg_std_mini, np.float32)
+        else:
+            rmini, rstd_mini = get_back(ctx, ref, ref_mask, bkg_boxsize=box)
+            rwork = torch.empty_like(ref)
+            mini2back(ctx, rmini, (rny, rnx), bkg_boxsize=box, interp_Xchan=True, subtract_from=ref, subtract_into=rwork)
+            res['bkg_mini_ref'], sdr_meas = fetch(ctx, rmini, rstd_mini)
+            sdr = sdr_meas if ref_bkg_std_mini is None else np.asarray(ref_bkg_std_mini, np.float32)
+        res['bkg_std_mini_ref'] = sdr
+        if ref_grid is not None:
+            from . import coadd
+            ones = torch.ones_like(rwork)
+            rwork, _ = coadd.resample(ctx, rwork, ones, ref_grid, (ny, nx), 1.0, ref_grid_step)
+            sdr = remap_mini(sdr, np.asarray(ref_grid), (rny, rnx), box, ref_grid_step)
+        elif (rny, rnx) != (ny, nx):
+            raise ValueError('reference frame of another shape needs ref_grid')
+        # co-added reference: no channel structure in its noise -> interpolation across the frame
+        sub_pr = subimage_psfs(ctx, psf_ref, nsy, nsx, size)
+        frame_path = frame_path_supported(L) and sub_pn.shape[1] == sub_pr.shape[1]
+        if ref_bkg_std is not None and ref_grid is None and tuple(ref_bkg_std.shape) == (ny, nx) and isinstance(ref_bkg_std, MiniImage) == use_mini:
+            rbstd = ref_bkg_std
+        elif use_mini and frame_path:
+            rbstd = MiniImage(ctx, np.asarray(sdr, np.float32), box, interp_Xchan=True)
+            if not mini_path_supported((ny, nx), size, border, box, rbstd):
+                rbstd = rbstd.frame(ctx)
+        else:
+            rbstd = mini2back(ctx, sdr, (ny, nx), bkg_boxsize=box, interp_Xchan=True)
+        if isinstance(bstd, MiniImage) and not (frame_path and isinstance(rbstd, MiniImage)):
+            bstd = res['bkg_std'] = bstd.frame(ctx)                   # the other side needs frames: both as frames
+            if isinstance(rbstd, MiniImage):
+                rbstd = rbstd.frame(ctx)
+        res['ref_bkgsub'], res['bkg_std_ref'] = rwork, rbstd
+        hdr_t['S-BKGSTDR'] = (float(np.median(sdr)), '[e-] sigma (STD) background reference image')
+        return rwork, rbstd, sdr, sub_pr, frame_path
+
+    ref_side = None
     # ---- full-source catalogue (a17): peaks of the background-subtracted frame above
     # cat_nsigma x S-BKGSTD, PSF-weighted optimal flux at each (zogy.get_psfoptflux)
     res['catalog'] = None
-    if cat_extract and sub_pn is not None:
+    mtab = None
+    if (cat_extract or do_match) and sub_pn is not None:
         thr = float(cat_nsigma) * hdr['S-BKGSTD'][0]
         if np.isfinite(thr) and thr > 0:
             pending = find_peaks_enqueue(ctx, work, thr, max_out=max_sources)
+            if do_match:
+                ref_side = prepare_reference()                       # (behind the search: its zoom would drop the candidate list)
             scal_n = host_side_meanwhile()
             ys, xs, pk = find_peaks_collect(ctx, pending)
         else:                                                        # no usable noise level: nothing is significant
             lib.bbx_zoom_candidates(ctx.h, None, 0.0)
+            if do_match:
+                ref_side = prepare_reference()
             scal_n = host_side_meanwhile()
             ys = xs = np.zeros(0, np.int32); pk = np.zeros(0, np.float32)
         keep = pk > 0
@@ -700,16 +930,29 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             d_mk = new_mask[d_ys, d_xs]
             stamps = source_psfs(ctx, psf_new, sub_pn, ys, xs, nsx, size)
             f, e = psf_optflux(ctx, work, bstd, stamps, ys, xs, v_is_sigma=True)        # (bstd: frame or MiniImage)
-            mk, f, e = fetch(ctx, d_mk, f, e)
+            back = [d_mk, f, e]
+            if do_match:
+                # the star match rides on the same copy back: centroids, match against the reference's catalogue (the run's,
+                # or made here) and the table of clipped statistics are queued behind the photometry
+                rc = ref_catalog if ref_catalog is not None and ref_catalog.matches(ref_side[0], ref_side[1], size, border) else \
+                    RefCatalog(ctx, ref_side[0], ref_side[1], ref_mask if ref_grid is None else None, psf_ref, size, border,
+                               cat_nsigma=cat_nsigma, sigma_median=hdr_t['S-BKGSTDR'][0], sub_psfs=ref_side[3], max_sources=max_sources)
+                back += match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, match_dist, match_snr_min)
+                mk, f, e, mtab, npairs = fetch(ctx, *back)
+                res['ref_catalog'] = rc
+                res['match'] = dict(n_new=int((mk == 0).sum()), n_ref=rc.n, n_pairs=int(npairs[0]))
+            else:
+                mk, f, e = fetch(ctx, *back)
             ok = mk == 0
             ys, xs, pk, f, e = ys[ok], xs[ok], pk[ok], f[ok], e[ok]
         else:
             f = e = np.zeros(0, np.float32)
-        peaks = ys
-        res['catalog'] = dict(Y_POS=ys.astype(np.float32) + 1, X_POS=xs.astype(np.float32) + 1,
-                              E_FLUX_PEAK=pk.astype(np.float32), E_FLUX_OPT=f, E_FLUXERR_OPT=e,
-                              SNR_OPT=np.where(e > 0, f / np.where(e > 0, e, 1), 0).astype(np.float32))
-        hdr['NOBJECTS'] = (len(peaks), 'number of objects detected')
+        if cat_extract:
+            peaks = ys
+            res['catalog'] = dict(Y_POS=ys.astype(np.float32) + 1, X_POS=xs.astype(np.float32) + 1,
+                                  E_FLUX_PEAK=pk.astype(np.float32), E_FLUX_OPT=f, E_FLUXERR_OPT=e,
+                                  SNR_OPT=np.where(e > 0, f / np.where(e > 0, e, 1), 0).astype(np.float32))
+            hdr['NOBJECTS'] = (len(peaks), 'number of objects detected')
     if 'S-BKG' not in hdr:
         scal_n = host_side_meanwhile()
     if not have_ref:
@@ -718,53 +961,30 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         return res
 
     # ---- reference frame on the new frame's grid: background-subtracted image + sigma image
-    rny, rnx = ref.shape
-    if ref_is_bkgsub:
-        rwork = ref
-        if ref_bkg_std_mini is None:
-            _, rstd_mini = get_back(ctx, ref, ref_mask, bkg_boxsize=box)
-            sdr = fetch(ctx, rstd_mini)
-        else:
-            sdr = np.asarray(ref_bkg_std_mini, np.float32)
-    else:
-        rmini, rstd_mini = get_back(ctx, ref, ref_mask, bkg_boxsize=box)
-        rwork = torch.empty_like(ref)
-        mini2back(ctx, rmini, (rny, rnx), bkg_boxsize=box, interp_Xchan=True, subtract_from=ref, subtract_into=rwork)
-        res['bkg_mini_ref'], sdr_meas = fetch(ctx, rmini, rstd_mini)
-        sdr = sdr_meas if ref_bkg_std_mini is None else np.asarray(ref_bkg_std_mini, np.float32)
-    res['bkg_std_mini_ref'] = sdr
-    if ref_grid is not None:
-        from . import coadd
-        ones = torch.ones_like(rwork)
-        rwork, _ = coadd.resample(ctx, rwork, ones, ref_grid, (ny, nx), 1.0, ref_grid_step)
-        sdr = remap_mini(sdr, np.asarray(ref_grid), (rny, rnx), box, ref_grid_step)
-    elif (rny, rnx) != (ny, nx):
-        raise ValueError('reference frame of another shape needs ref_grid')
-    # co-added reference: no channel structure in its noise -> interpolation across the frame
-    sub_pr = subimage_psfs(ctx, psf_ref, nsy, nsx, size)
-    frame_path = frame_path_supported(L) and sub_pn.shape[1] == sub_pr.shape[1]
-    if ref_bkg_std is not None and ref_grid is None and tuple(ref_bkg_std.shape) == (ny, nx) and isinstance(ref_bkg_std, MiniImage) == use_mini:
-        rbstd = ref_bkg_std
-    elif use_mini and frame_path:
-        rbstd = MiniImage(ctx, np.asarray(sdr, np.float32), box, interp_Xchan=True)
-        if not mini_path_supported((ny, nx), size, border, box, rbstd):
-            rbstd = rbstd.frame(ctx)
-    else:
-        rbstd = mini2back(ctx, sdr, (ny, nx), bkg_boxsize=box, interp_Xchan=True)
-    if isinstance(bstd, MiniImage) and not (frame_path and isinstance(rbstd, MiniImage)):
-        bstd = res['bkg_std'] = bstd.frame(ctx)                   # the other side needs frames: both as frames
-        if isinstance(rbstd, MiniImage):
-            rbstd = rbstd.frame(ctx)
-    res['ref_bkgsub'], res['bkg_std_ref'] = rwork, rbstd
-    hdr_t['S-BKGSTDR'] = (float(np.median(sdr)), '[e-] sigma (STD) background reference image')
+    rwork, rbstd, sdr, sub_pr, frame_path = ref_side if ref_side is not None else prepare_reference()
 
     # ---- sub-images
     scal = np.zeros((nsub, 6), np.float32)
     scal[:, 0], scal[:, 1] = scal_n, tile_medians(sdr)
     # fratio, dx, dy: one number for the frame or one per sub-image (zogy measures them per sub-image from the matched stars)
-    fr = np.broadcast_to(np.asarray(fratio, np.float64), (nsub,))
+    ms = None
+    if do_match:
+        # measured here (match=True): per sub-image where it has the pairs, the frame's values elsewhere, the caller's as fallback
+        if mtab is None:
+            mtab = empty_match_table(nsub)
+            res['match'] = dict(n_new=0, n_ref=ref_catalog.n if ref_catalog is not None else 0, n_pairs=0)
+        ms = match_scalars(mtab, fratio, dx, dy, settings.match_nmin if match_nmin is None else match_nmin)
+        if not ms['success']:
+            import logging
+            logging.getLogger(__name__).warning('star match: %d qualifying pairs in the frame, fewer than the minimum: fratio, dx, dy as given '
+                                                'by the caller', int(mtab[nsub, 0]))
+        res['match'].update(success=ms['success'], table=mtab, fratio_sub=ms['fratio_sub'], dx_sub=ms['dx_sub'], dy_sub=ms['dy_sub'])
+        fratio_in, dx_in, dy_in = ms['fratio_sub'], ms['dx_sub'], ms['dy_sub']
+    else:
+        fratio_in, dx_in, dy_in = fratio, dx, dy
+    fr = np.broadcast_to(np.asarray(fratio_in, np.float64), (nsub,))
     scal[:, 2], scal[:, 3] = 1.0, np.where(fr != 0, 1.0 / np.where(fr != 0, fr, 1.0), 1.0)
-    scal[:, 4], scal[:, 5] = np.broadcast_to(np.asarray(dx, np.float64), (nsub,)), np.broadcast_to(np.asarray(dy, np.float64), (nsub,))
+    scal[:, 4], scal[:, 5] = np.broadcast_to(np.asarray(dx_in, np.float64), (nsub,)), np.broadcast_to(np.asarray(dy_in, np.float64), (nsub,))
     if frame_path:
         # hand-written FFT path: cut, variance images, ZOGY and stitching in one library call
         outs = zogy_frame_outputs(work)                           # allocated on the caller's stream, filled inside the gate
@@ -850,9 +1070,12 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     for h in (hdr, hdr_t):
         h['Z-SIZE'] = (size, '[pix] size of (square) ZOGY subimages')
         h['Z-BSIZE'] = (border, '[pix] size of ZOGY subimage borders')
-    hdr_t['Z-DX'] = (float(np.median(dx)), '[pix] dx median offset full image')
-    hdr_t['Z-DY'] = (float(np.median(dy)), '[pix] dy median offset full image')
-    hdr_t['Z-FNR'] = (float(np.median(fratio)), 'median flux ratio (Fnew/Fref) full image')
+    if ms is not None:
+        hdr_t.update(ms['header'])
+    else:
+        hdr_t['Z-DX'] = (float(np.median(dx)), '[pix] dx median offset full image')
+        hdr_t['Z-DY'] = (float(np.median(dy)), '[pix] dy median offset full image')
+        hdr_t['Z-FNR'] = (float(np.median(fratio)), 'median flux ratio (Fnew/Fref) full image')
     if frame_stats:
         hdr_t['Z-SCMED'] = (float(st[0, 1]), 'median Scorr full image')
         hdr_t['Z-SCSTD'] = (float(st[0, 3]), 'sigma (STD) Scorr full image')

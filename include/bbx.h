@@ -696,6 +696,58 @@ int bbx_thumbnails(bbx_ctx *ctx, int ny, int nx, const float *const *d_img, int 
 int bbx_thumb_png8(bbx_ctx *ctx, int n_stamps, int size, const float *d_stamps, uint8_t *d_out_u8,
                    double *d_limits, void *stream);
 
+/* ---- flux ratio and astrometric scatter of a frame against its reference from matched stars (the fratio, dx, dy that
+ * bbx_zogy_frame takes per sub-image; header keys Z-DX / Z-DY / Z-DXSTD / Z-DYSTD / Z-FNR / Z-FNRSTD / Z-FNRERR,
+ * set_qc.py:370-375, 425).  The shape of the computation is buildref.py:2782-3014 (get_fratio, "simplified version of
+ * zogy.get_fratio_dxdy"): matches within dist_max = 2 arcsec, fratio = flux_new / flux_ref over pairs with both fluxes
+ * non-zero (2965-2966), its error fratio * sqrt((e_n / f_n)^2 + (e_r / f_r)^2) (2969-2971), a minimum of 15 matches
+ * (2992), sigma-clipped statistics.  [EXT] zogy.get_fratio_dxdy, get_matches and get_mean_fratio themselves are not in
+ * the reference tree: where the statements above are silent the rules below are THIS PROJECT'S OWN.
+ * All three entries are deterministic: no float atomics, every sum in a fixed order, same input -> same bits.         */
+#define BBX_MATCH_CAP 8192      /* pairs of one segment that enter its statistics (one 32 KB LDS buffer) */
+
+/* Iterated Gaussian-windowed centroid (the SExtractor XWIN recurrence) of nsrc sources of the frame d_img[ny][nx] at the
+ * integer peaks (d_ys, d_xs): starting at the peak, w_i = exp(-r_i^2 / (2 sigma_w^2)) * I_i over the (2 radius + 1)^2
+ * pixels around the INTEGER peak (radius <= 10; pixels off the frame contribute nothing), c <- c + 2 sum w_i (p_i - c) /
+ * sum w_i, niter times, in float32.  sigma_w = d_sigw[tile] of the sub-image tile (size x size pixels, nsy x nsx
+ * tiles, indices clamped) the integer peak lies in.  d_off[nsrc][2] = (dy, dx) RELATIVE TO THE INTEGER PEAK (an absolute
+ * float32 coordinate near 10560 has an ulp of 1e-3 px).  Own conventions: the offset is (NaN, NaN) -- and the source then
+ * matches nothing -- when sigma_w is not positive and finite, when in any iteration sum w_i is not positive or a sum
+ * is not finite, or when the centroid moves further than radius / 2 from the integer peak in y or in x (it has then
+ * left the part of the window that still holds the source).  One wave per source, the window in registers, no LDS. */
+int bbx_win_centroid(bbx_ctx *ctx, int ny, int nx, const float *d_img, int nsrc, const int32_t *d_ys,
+                     const int32_t *d_xs, const float *d_sigw, int size, int nsy, int nsx, int radius, int niter,
+                     float *d_off, void *stream);
+
+/* One-to-one match of two source lists A (new) and B (reference), each given as integer peaks + float32 offsets
+ * [n][2] = (dy, dx) and SORTED BY (y, x) OF THE INTEGER PEAK ([EXT] get_matches; own rules).  distance^2 is formed in
+ * float32 as (dy_int + d off_y)^2 + (dx_int + d off_x)^2.  For each a: the nearest b with distance <= dist_max
+ * (inclusive; ties: the lower index) among the b whose integer peak is within ceil(dist_max + 1) rows and columns of
+ * a's (offsets are sub-pixel: what lies beyond that band is never a match); the same for each b; d_match[n_a] = that b
+ * where the choice is mutual, else -1.  A source with a NaN offset matches nothing.  d_best_b[n_b]: scratch of the
+ * caller (nearest a of every b).  n_a == 0: nothing is done.                                                      */
+int bbx_match_mutual(bbx_ctx *ctx, int n_a, const int32_t *d_a_ys, const int32_t *d_a_xs, const float *d_a_off,
+                     int n_b, const int32_t *d_b_ys, const int32_t *d_b_xs, const float *d_b_off, float dist_max,
+                     int32_t *d_best_b, int32_t *d_match, void *stream);
+
+/* Clipped statistics of the matched pairs per segment: the nsy x nsx sub-image tiles (size x size pixels, no border)
+ * and, last, the whole frame.  A pair (a, b = d_match[a]) qualifies for a segment when it is matched, both fluxes are
+ * > 0 (buildref.py:2965 asks != 0; a negative flux has no ratio), flux / err >= snr_min on both sides (own rule), and
+ * a's integer peak lies in the tile.  More than BBX_MATCH_CAP qualifying pairs: every s-th in list order, s = ceil(n /
+ * BBX_MATCH_CAP) (own rule: a deterministic sample over the whole segment).  Quantities, float32: fr = f_a / f_b,
+ * dx = x_a - x_b, dy = y_a - y_b (integer difference + offset difference).  Each is clipped like astropy's
+ * sigma_clipped_stats defaults (oracle/zogy_core.box_stats: 3 sigma about the exact median, population std, at most 5
+ * rounds, stop when nothing is clipped); an even count's median is the midpoint of the two float32 values formed in
+ * float64; sums are float64.  d_out[nsy * nsx + 1][16] float64 = {n_qualifying, n_fr, med_fr, mean_fr, std_fr, wmean_fr,
+ * werr_fr, n_dx, med_dx, mean_dx, std_dx, n_dy, med_dy, mean_dy, std_dy, stride s}; wmean_fr, werr_fr: the inverse-
+ * variance weighted mean of the clipped fr sample and 1 / sqrt(sum 1 / sigma_i^2), sigma_i = buildref.py:2969-2971
+ * ([EXT] get_mean_fratio(weighted=True)).  An empty segment: the four counts 0, s = 1, NaN elsewhere.
+ * n_a == 0: nothing is done (d_out is not written).  One workgroup of 1024 threads per segment, 33 KB of LDS.      */
+int bbx_match_stats(bbx_ctx *ctx, int n_a, const int32_t *d_a_ys, const int32_t *d_a_xs, const float *d_a_off,
+                    const float *d_a_flux, const float *d_a_err, int n_b, const int32_t *d_b_ys,
+                    const int32_t *d_b_xs, const float *d_b_off, const float *d_b_flux, const float *d_b_err,
+                    const int32_t *d_match, int size, int nsy, int nsx, float snr_min, double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
