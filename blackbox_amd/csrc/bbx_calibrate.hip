@@ -178,13 +178,14 @@ __global__ __launch_bounds__(256) void k_calibrate_v4(calib_args a) {
         unsigned base = 0;
         if (lane == 0) base = atomicAdd((unsigned*)&a.counters[CNT_SAT], total);
         base = __shfl(base, 0, 64) + incl - cnt;
-        if (base + cnt > a.satcap) { if (cnt) atomicOr(a.err, BBX_DERR_LIST_OVERFLOW); }
-        else {
-            unsigned b = satbits;
-            while (b) {
-                const int bit = __ffs(b) - 1; b &= b - 1;
-                a.satlist[base++] = (uint32_t)((size_t)(Y0 + (bit >> 2)) * d.nx + X + (bit & 3));
-            }
+        if (cnt && base + cnt > a.satcap) atomicOr(a.err, BBX_DERR_LIST_OVERFLOW);
+        // every entry below the capacity is written, also by the one lane whose reservation straddles it: the
+        // consumers read min(count, capacity) entries and take each for a pixel of this frame
+        unsigned b = satbits;
+        while (b) {
+            const int bit = __ffs(b) - 1; b &= b - 1;
+            if (base < a.satcap) a.satlist[base] = (uint32_t)((size_t)(Y0 + (bit >> 2)) * d.nx + X + (bit & 3));
+            base++;
         }
     }
 }

@@ -181,6 +181,17 @@ def polyfit_exact(start, n, mask, y, deg):
     return c, rank
 
 
+def dead_vos_rows(mean_vos_col):
+    """blackbox.py:6480-6490: sigma_clipped_stats(mask_value=0) raises when it masks the whole vertical overscan of
+    a channel -- every value is zero (non-finite values were set to zero before) -- and the reference then takes the
+    clipped row means without the mask value: 0.0 for every row.  The device kernel marks a row without a valid
+    value with NaN; a channel in which every row is marked is such a strip.  -> the row means to fit"""
+    m = np.asarray(mean_vos_col)
+    if m.size and np.isnan(m).all():
+        return np.zeros(m.shape)
+    return mean_vos_col
+
+
 def vos_polyfit(mean_vos_col, nrows, i_chan, poldeg=3):
     """blackbox.py:6497-6556.  -> (fit[dy] float64, coeffs low->high order,
     polyfit_ok, mean level)"""

@@ -183,7 +183,7 @@ def _shm_solve(args):
     layout, slot, c, ysz, xsz, poldeg, tel, data_limit, accum = args
     a = _arena(layout)
     try:
-        r = overscan.channel_solve((c, a.view(slot, 'mean')[c], a.view(slot, 'hos')[c], ysz, xsz, poldeg, tel,
+        r = overscan.channel_solve((c, overscan.dead_vos_rows(a.view(slot, 'mean')[c]), a.view(slot, 'hos')[c], ysz, xsz, poldeg, tel,
                                     data_limit, accum))
     except overscan.OverscanFailure as e:
         return _failed(a, slot, c, e)
@@ -204,7 +204,7 @@ def _shm_phase1(args):
     layout, slot, c, ysz, xsz, poldeg, accum = args
     a = _arena(layout)
     try:
-        r = overscan.channel_phase1(c, a.view(slot, 'mean')[c], a.view(slot, 'hos')[c], ysz, xsz, poldeg, accum)
+        r = overscan.channel_phase1(c, overscan.dead_vos_rows(a.view(slot, 'mean')[c]), a.view(slot, 'hos')[c], ysz, xsz, poldeg, accum)
     except overscan.OverscanFailure as e:
         a.view(slot, 'strip')[c] = 0.0
         return _failed(a, slot, c, e)

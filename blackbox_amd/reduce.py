@@ -244,6 +244,7 @@ def os_solve(ctx, raw, header, tel, geom, data_limit=2000, accum='f32seq'):
                                  _ptr(d_ninf), ctx.stream()), 'bbx_overscan_stats', ctx.h)
     # one device->host hop: 16*dy float64 + the hos strips (< 2 MB)
     mean_vos_col = d_mean.cpu().numpy().reshape(16, dy)
+    mean_vos_col = np.stack([overscan.dead_vos_rows(m) for m in mean_vos_col])      # an all-zero strip: row means 0.0
     hos = d_hos.cpu().numpy()
     header['N-INFNAN'] = (int(d_ninf.item()), 'number of pixels with infinite/nan values')
     vfit = np.empty((16, dy))

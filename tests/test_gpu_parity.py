@@ -371,9 +371,12 @@ def test_lacosmic_background_level(ctx, constant_sky, feed):
 @pytest.mark.gpu
 def test_saturated_frame_one_percent(ctx):
     """a frame with > 1 % saturated pixels (blobs of 3..9 px across, so that saturated-connected
-    pixels, hole filling and the object count all have work): the saturated-pixel queue takes one
-    reservation per wave in k_calibrate; mask, counts and pixels equal the oracle's mask_init bit
-    for bit (the queue's capacity is N/8 + 4096 entries: no overflow at this density)"""
+    pixels, hole filling and the object count all have work): mask, counts and pixels equal the
+    oracle's mask_init bit for bit (the queue's capacity is N/8 + 4096 entries: no overflow at this
+    density).  At this geometry (xs = 330, dx = 375: no multiple of 4) bbx_calibrate runs the scalar
+    kernel k_calibrate_s, which queues each saturated pixel with an atomic of its own; the vector
+    kernel's one reservation per wave is the business of
+    test_gpu_frontend_variants.py::test_saturated_pixel_queue_vector_variant"""
     tel, ys, xs, os_y, os_x = 'ML1', 330, 330, 20, 45
     case = synth.make_case(ys, xs, 77, tel=tel, os_y=os_y, os_x=os_x, n_stars=40, n_sat=3, n_cr=0)
     raw = case['raw'].copy()
