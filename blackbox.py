@@ -376,6 +376,9 @@ class Reducer:
         def par(value, name):
             return S.get_par(getattr(S, name), self.tel) if value is None else value
         self.thumbnails_dir = par(a.thumbnails_dir, 'thumbnails_dir')
+        if sub['cat_extract'] and par(a.cat_shapes, 'cat_shapes'):
+            # source shapes of the catalogue and the frame's seeing / elongation keys; the keyword is only passed when switched on
+            sub['shapes'] = True
         if sub['ref'] is not None:
             if par(a.save_thumbnails, 'save_thumbnails'):
                 sub['thumbnails'] = True
@@ -1043,6 +1046,9 @@ def build_parser():
     ap.add_argument('--img_reduce', type=str2bool, default=True)
     ap.add_argument('--cat_extract', type=str2bool, default=False)
     ap.add_argument('--trans_extract', type=str2bool, default=False)
+    ap.add_argument('--cat_shapes', type=str2bool, default=None,
+                    help='with --cat_extract: FWHM, ELONGATION, A, B, THETA, X2, Y2, XY, FLAGS_MASK and sub-pixel X_POS / Y_POS in '
+                         '_cat.fits, S-NOBJ S-FWHM S-FWSTD S-SEEING S-SEESTD S-ELONG S-ELOSTD in the header (default: settings.cat_shapes)')
     ap.add_argument('--force_reproc_new', type=str2bool, default=False)
     ap.add_argument('--master_date', type=str, default=None,
                     help='make the masters of this evening date yyyymmdd, or of the dates in this file (one per line, '

@@ -136,6 +136,8 @@ SIGNATURES = {
     'bbx_win_centroid': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'bbx_match_mutual': (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     'bbx_match_stats': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    'bbx_src_shapes': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'bbx_shape_stats': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError if the export is missing

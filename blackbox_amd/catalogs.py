@@ -13,6 +13,9 @@ table that carries them is written with THUMBNAIL_RED, THUMBNAIL_REF, THUMBNAIL_
 (qc.py:480-485; 100 x 100 float32 cells, TDIM '(100,100)') and FLAGS_MASK after the six columns
 above; save_png_thumbnails writes the reference's {NUMBER}_{RED,REF,D,SCORR}.png files
 (blackbox.py:2674-2826) from the display planes the GPU made (zogy.thumbnail_stamps).
+
+Source shapes (settings.cat_shapes, off by default): a 'new' table that carries them is written with FWHM, ELONGATION, A, B,
+THETA, X2, Y2, XY and FLAGS_MASK (SHAPE_COLUMNS) after the seven columns above; the dummy catalogue keeps the seven.
 """
 import os
 import shutil
@@ -31,6 +34,10 @@ COLUMNS = {
               ('SNR_ZOGY', np.float32, ''), ('E_FLUX_ZOGY', np.float32, 'e-'), ('E_FLUXERR_ZOGY', np.float32, 'e-')),
 }
 COLUMNS['ref'] = COLUMNS['new']
+# source shapes (settings.cat_shapes; zogy.optimal_subtraction(shapes=True)): appended to the 'new' columns of a table that carries them
+SHAPE_COLUMNS = (('FWHM', np.float32, 'pix'), ('ELONGATION', np.float32, ''), ('A', np.float32, 'pix'), ('B', np.float32, 'pix'),
+                 ('THETA', np.float32, 'deg'), ('X2', np.float32, 'pix2'), ('Y2', np.float32, 'pix2'), ('XY', np.float32, 'pix2'),
+                 ('FLAGS_MASK', np.uint8, ''))
 THUMBNAILS = ('RED', 'REF', 'D', 'SCORR')                     # plane order of zogy.thumbnail_stamps; blackbox.py:2701
 THUMBNAIL_COLUMNS = tuple('THUMBNAIL_' + c for c in THUMBNAILS)
 
@@ -50,6 +57,10 @@ def format_cat(table, cat_output, cat_type='new', header2add=None):
         else:
             cols[name] = np.zeros(n, dtype=dt)
         units[name] = unit
+    if cat_type != 'trans' and table is not None and SHAPE_COLUMNS[0][0] in table:
+        for name, dt, unit in SHAPE_COLUMNS:
+            cols[name] = np.asarray(table[name]).astype(dt)
+            units[name] = unit
     if cat_type == 'trans' and table is not None and THUMBNAIL_COLUMNS[0] in table:
         for name in THUMBNAIL_COLUMNS:
             cols[name] = np.asarray(table[name]).astype(np.float32)

@@ -5,31 +5,15 @@
 //   k_match_nearest: one thread per source; binary search of the other list's row band, scan of the band (two launches)
 //   k_match_stats  : one workgroup per sub-image tile + one for the frame; count, strided selection in list order, LDS sort,
 //                    sigma clipping on the sorted sample (oracle/zogy_core.box_stats), float64 sums in a fixed order
-#include "bbx_common.h"
+#include "bbx_stats.h"
 
 #define MATCH_BLOCK   256
 #define CEN_RMAX      10
 #define CEN_NREG      7                                  // ceil((2 * 10 + 1)^2 / 64)
-#define STATS_BLOCK   1024
-#define STATS_WAVES   (STATS_BLOCK / 64)
 
 // ---------------------------------------------------------------------------------------------------------------------
-// windowed centroid
+// windowed centroid (the wave sum: bbx_stats.h)
 // ---------------------------------------------------------------------------------------------------------------------
-template <int CTRL> __device__ __forceinline__ float dpp_mov_f32(float v) {
-    return __int_as_float(dpp_mov_i32<CTRL>(__float_as_int(v)));
-}
-__device__ __forceinline__ float readlane_f32(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-// wave sum in a fixed order (row rotations, then the four row totals in row order), the same value in every lane
-__device__ __forceinline__ float wave_sum_f32(float v) {
-    v += dpp_mov_f32<BBX_DPP_ROR(1)>(v);
-    v += dpp_mov_f32<BBX_DPP_ROR(2)>(v);
-    v += dpp_mov_f32<BBX_DPP_ROR(4)>(v);
-    v += dpp_mov_f32<BBX_DPP_ROR(8)>(v);
-    return (readlane_f32(v, 0) + readlane_f32(v, 16)) + (readlane_f32(v, 32) + readlane_f32(v, 48));
-}
-__device__ __forceinline__ bool match_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 __global__ __launch_bounds__(MATCH_BLOCK) void k_win_centroid(int ny, int nx, const float* __restrict__ img, int nsrc,
                                                               const int32_t* __restrict__ ys, const int32_t* __restrict__ xs,
                                                               const float* __restrict__ sigw, int size, int nsy, int nsx, int R, int niter,
@@ -96,15 +80,6 @@ extern "C" int bbx_win_centroid(bbx_ctx* ctx, int ny, int nx, const float* d_img
 // ---------------------------------------------------------------------------------------------------------------------
 struct match_list { const int32_t* ys; const int32_t* xs; const float* off; int n; };
 
-__device__ __forceinline__ int match_lower_bound(const int32_t* __restrict__ ys, int n, int y) {     // first i with ys[i] >= y
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (ys[mid] < y) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // nearest source of [o] to source i of [s] within dmax2 (float32 distance^2, inclusive), the lower index on ties; -1: none.
 // The distance of a pair is the same float whichever side forms it: every term only changes sign.
 __device__ __forceinline__ int match_nearest(const match_list& s, int i, const match_list& o, int band, float dmax2) {
@@ -169,161 +144,60 @@ struct stats_in {
     int n_a, n_b;
     float snr_min;
 };
-struct stats_seg { int i0, i1, y0, y1, x0, x1, stride; };            // list range, tile rectangle, selection stride
-
 enum { Q_COUNT = 0, Q_FR, Q_DX, Q_DY, Q_WEIGHT };
 
-// sums of two doubles over the workgroup, the same values in every thread: wave sums by DPP, the wave totals through LDS and
-// added as a fixed tree.  red[2][2][STATS_WAVES] is used alternately, so one barrier per call is enough
-__device__ __forceinline__ void stats_block_sum(double& a, double& b, double* red, int& ph) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    a = wave_sum_f64(a); b = wave_sum_f64(b);
-    if (lane == 0) { red[(ph * 2 + 0) * STATS_WAVES + wave] = a; red[(ph * 2 + 1) * STATS_WAVES + wave] = b; }
-    __syncthreads();
-    double t[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const double* r = red + (ph * 2 + k) * STATS_WAVES;
-        t[k] = (((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))) +
-               (((r[8] + r[9]) + (r[10] + r[11])) + ((r[12] + r[13]) + (r[14] + r[15])));
-    }
-    a = t[0]; b = t[1];
-    ph ^= 1;
-}
-
-// One walk over the segment's part of list A in list order: every wave takes a contiguous share, 64 sources at a time.
-// Q_COUNT: -> the wave's number of qualifying pairs.  Q_FR / Q_DX / Q_DY: the qualifying pair of rank r (list order; [base] =
-// pairs in the shares before this wave's) with r % stride == 0 puts its value into vals[r / stride].  Q_WEIGHT: the selected
-// pairs with wlo <= fr <= whi add 1 / sigma^2 and fr / sigma^2 to (acc0, acc1), float64
+// what stats_walk (bbx_stats.h) asks of list A.  Q_COUNT: only the qualification.  Q_FR / Q_DX / Q_DY: the selected pair puts
+// its value into vals[pos].  Q_WEIGHT: the selected pairs with wlo <= fr <= whi add 1 / sigma^2 and fr / sigma^2 to
+// (acc0, acc1), float64
 template <int Q>
-__device__ __forceinline__ int stats_walk(const stats_in& in, const stats_seg& sg, int base, float* __restrict__ vals, float wlo, float whi,
-                                          double& acc0, double& acc1) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int len = sg.i1 - sg.i0;
-    const int share = ((len + STATS_WAVES - 1) / STATS_WAVES + 63) / 64 * 64;
-    const long long b0 = (long long)sg.i0 + (long long)wave * share;
-    const int beg = (int)(b0 < sg.i1 ? b0 : sg.i1), end = (int)(b0 + share < sg.i1 ? b0 + share : sg.i1);
-    int run = base;
-    for (int b = beg; b < end; b += 64) {
-        const int i = b + lane;
-        bool q = false;
-        float fa = 0.f, fb = 0.f, ea = 0.f, eb = 0.f;
-        int m = -1, ya = 0, xa = 0;
-        if (i < end) {
-            m = in.match[i];
-            if (m >= 0 && m < in.n_b) {
-                ya = in.a_ys[i]; xa = in.a_xs[i];
-                fa = in.a_flux[i]; ea = in.a_err[i]; fb = in.b_flux[m]; eb = in.b_err[m];
-                q = fa > 0.f && fb > 0.f && fa / ea >= in.snr_min && fb / eb >= in.snr_min &&
-                    ya >= sg.y0 && ya < sg.y1 && xa >= sg.x0 && xa < sg.x1;
-            }
-        }
-        const unsigned long long mask = __ballot(q);
-        if (Q != Q_COUNT && q) {
-            const int rank = run + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-            const int pos = rank / sg.stride;
-            if (pos * sg.stride == rank && pos < BBX_MATCH_CAP) {
-                const float fr = fa / fb;
-                if (Q == Q_FR) vals[pos] = fr;
-                if (Q == Q_DX) vals[pos] = (float)(xa - in.b_xs[m]) + (in.a_off[2 * (size_t)i + 1] - in.b_off[2 * (size_t)m + 1]);
-                if (Q == Q_DY) vals[pos] = (float)(ya - in.b_ys[m]) + (in.a_off[2 * (size_t)i] - in.b_off[2 * (size_t)m]);
-                if (Q == Q_WEIGHT && fr >= wlo && fr <= whi) {
-                    // buildref.py:2969-2971: fratio * sqrt((e_new / f_new)^2 + (e_ref / f_ref)^2)
-                    const double ra = (double)ea / (double)fa, rb = (double)eb / (double)fb;
-                    const double s = (double)fr * sqrt(ra * ra + rb * rb);
-                    const double w = 1.0 / (s * s);
-                    acc0 += w; acc1 += w * (double)fr;
-                }
-            }
-        }
-        run += __popcll(mask);
+struct match_item {
+    const stats_in& in;
+    float* __restrict__ vals;
+    float wlo, whi;
+    double acc0, acc1;
+    float fa, fb, ea, eb;
+    int m, ya, xa;
+    __device__ __forceinline__ bool load(int i, const stats_seg& sg) {
+        m = in.match[i];
+        if (m < 0 || m >= in.n_b) return false;
+        ya = in.a_ys[i]; xa = in.a_xs[i];
+        fa = in.a_flux[i]; ea = in.a_err[i]; fb = in.b_flux[m]; eb = in.b_err[m];
+        return fa > 0.f && fb > 0.f && fa / ea >= in.snr_min && fb / eb >= in.snr_min &&
+               ya >= sg.y0 && ya < sg.y1 && xa >= sg.x0 && xa < sg.x1;
     }
-    return run - base;
-}
-
-__device__ __forceinline__ void stats_cswap(float* v, int i, int j, bool up) {
-    const float a = v[i], b = v[j];
-    const float lo = fminf(a, b), hi = fmaxf(a, b);                  // (the values are not NaN)
-    v[i] = up ? lo : hi;
-    v[j] = up ? hi : lo;
-}
-
-// vals[0..m) -> sorted (bitonic network over the next power of two, padded with +inf), then box_stats: 3 sigma about the exact
-// median, spread = population std, at most 5 rounds, stop when nothing is clipped.  On the sorted sample a clipped set is a
-// range [lo, hi).  -> n, median, mean, std (every thread), and the range's end values
-__device__ __forceinline__ void stats_clip(float* vals, int m, double* red, int& ph, double out[4], float& vlo, float& vhi) {
-    const int tid = threadIdx.x;
-    int P = 2;
-    while (P < m) P <<= 1;
-    for (int i = m + tid; i < P; i += STATS_BLOCK) vals[i] = __builtin_inff();
-    __syncthreads();
-    for (int kk = 2; kk <= P; kk <<= 1)
-        for (int j = kk >> 1; j >= 1; j >>= 1) {
-            for (int t = tid; t < P / 2; t += STATS_BLOCK) {
-                const int i = 2 * j * (t / j) + (t % j);
-                stats_cswap(vals, i, i + j, (i & kk) == 0);
-            }
-            __syncthreads();
+    __device__ __forceinline__ void put(int i, int pos) {
+        const float fr = fa / fb;
+        if (Q == Q_FR) vals[pos] = fr;
+        if (Q == Q_DX) vals[pos] = (float)(xa - in.b_xs[m]) + (in.a_off[2 * (size_t)i + 1] - in.b_off[2 * (size_t)m + 1]);
+        if (Q == Q_DY) vals[pos] = (float)(ya - in.b_ys[m]) + (in.a_off[2 * (size_t)i] - in.b_off[2 * (size_t)m]);
+        if (Q == Q_WEIGHT && fr >= wlo && fr <= whi) {
+            // buildref.py:2969-2971: fratio * sqrt((e_new / f_new)^2 + (e_ref / f_ref)^2)
+            const double ra = (double)ea / (double)fa, rb = (double)eb / (double)fb;
+            const double s = (double)fr * sqrt(ra * ra + rb * rb);
+            const double w = 1.0 / (s * s);
+            acc0 += w; acc1 += w * (double)fr;
         }
-    int lo = 0, hi = m;
-    double med = 0.0, mean = 0.0, std = 0.0;
-    for (int round = 0; round <= 5; round++) {                       // rounds 0..4 clip; the last pass only takes the statistics
-        const int n = hi - lo;
-        if (n == 0) break;
-        med = (n & 1) ? (double)vals[lo + n / 2] : ((double)vals[lo + n / 2 - 1] + (double)vals[lo + n / 2]) / 2.0;
-        double s = 0.0, z = 0.0;
-        for (int i = lo + tid; i < hi; i += STATS_BLOCK) s += (double)vals[i];
-        stats_block_sum(s, z, red, ph);
-        mean = s / (double)n;
-        double ss = 0.0;
-        for (int i = lo + tid; i < hi; i += STATS_BLOCK) { const double d = mean - (double)vals[i]; ss += d * d; }
-        stats_block_sum(ss, z, red, ph);
-        std = sqrt(ss / (double)n);
-        if (round == 5) break;
-        const double L = med - 3.0 * std, H = med + 3.0 * std;
-        double nl = 0.0, nh = 0.0;
-        for (int i = lo + tid; i < hi; i += STATS_BLOCK) {
-            const double v = (double)vals[i];
-            if (!(v >= L)) nl += 1.0;
-            else if (!(v <= H)) nh += 1.0;
-        }
-        stats_block_sum(nl, nh, red, ph);
-        if (nl == 0.0 && nh == 0.0) break;
-        lo += (int)nl; hi -= (int)nh;
     }
-    const int n = hi - lo;
-    const double nan = __builtin_nan("");
-    out[0] = (double)n;
-    out[1] = n ? med : nan; out[2] = n ? mean : nan; out[3] = n ? std : nan;
-    vlo = n ? vals[lo] : 0.f; vhi = n ? vals[hi - 1] : 0.f;
-    __syncthreads();                                                 // vals is filled again by the caller
+};
+template <int Q>
+__device__ __forceinline__ void match_walk(const stats_in& in, const stats_seg& sg, int base, float* __restrict__ vals, float wlo, float whi,
+                                           double& acc0, double& acc1) {
+    match_item<Q> it = {in, vals, wlo, whi, acc0, acc1};
+    stats_walk<false>(sg, base, it);
+    acc0 = it.acc0; acc1 = it.acc1;
 }
 
 __global__ __launch_bounds__(STATS_BLOCK) void k_match_stats(stats_in in, int size, int nsy, int nsx, double* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) float s_vals[BBX_MATCH_CAP];                         // 32 KB: one quantity at a time
     __shared__ double s_red[2 * 2 * STATS_WAVES];
     __shared__ int s_cnt[STATS_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int seg = blockIdx.x, nsub = nsy * nsx;
-    stats_seg sg;
-    if (seg < nsub) {
-        const int ty = seg / nsx, tx = seg - ty * nsx;
-        sg.y0 = ty * size; sg.y1 = sg.y0 + size; sg.x0 = tx * size; sg.x1 = sg.x0 + size;
-        sg.i0 = match_lower_bound(in.a_ys, in.n_a, sg.y0);           // list A is sorted by y: the tile's rows are one range
-        sg.i1 = match_lower_bound(in.a_ys, in.n_a, sg.y1);
-    } else {
-        sg.y0 = sg.x0 = INT32_MIN; sg.y1 = sg.x1 = INT32_MAX;
-        sg.i0 = 0; sg.i1 = in.n_a;
-    }
-    sg.stride = 1;
+    const int tid = threadIdx.x;
+    const int seg = blockIdx.x;
+    stats_seg sg = stats_segment(seg, size, nsy, nsx, in.a_ys, in.n_a);
     double z0 = 0.0, z1 = 0.0;
-    const int mine = stats_walk<Q_COUNT>(in, sg, 0, s_vals, 0.f, 0.f, z0, z1);
-    if (lane == 0) s_cnt[wave] = mine;
-    __syncthreads();
-    int n = 0, base = 0;
-#pragma unroll
-    for (int w = 0; w < STATS_WAVES; w++) { if (w < wave) base += s_cnt[w]; n += s_cnt[w]; }
-    sg.stride = n > BBX_MATCH_CAP ? (n + BBX_MATCH_CAP - 1) / BBX_MATCH_CAP : 1;
+    int base;
+    match_item<Q_COUNT> cnt = {in, s_vals, 0.f, 0.f, 0.0, 0.0};
+    const int n = stats_count(sg, cnt, s_cnt, base);
     const int m = (n + sg.stride - 1) / sg.stride;                   // <= BBX_MATCH_CAP
 
     double* o = out + (size_t)seg * 16;
@@ -339,11 +213,11 @@ __global__ __launch_bounds__(STATS_BLOCK) void k_match_stats(stats_in in, int si
     double st[4];
     float vlo, vhi;
     // ---- flux ratio, and the weighted mean over its clipped sample
-    stats_walk<Q_FR>(in, sg, base, s_vals, 0.f, 0.f, z0, z1);
+    match_walk<Q_FR>(in, sg, base, s_vals, 0.f, 0.f, z0, z1);
     __syncthreads();
     stats_clip(s_vals, m, s_red, ph, st, vlo, vhi);
     double sw = 0.0, swf = 0.0;
-    if (st[0] > 0.0) stats_walk<Q_WEIGHT>(in, sg, base, s_vals, vlo, vhi, sw, swf);
+    if (st[0] > 0.0) match_walk<Q_WEIGHT>(in, sg, base, s_vals, vlo, vhi, sw, swf);
     stats_block_sum(sw, swf, s_red, ph);
     if (tid == 0) {
         o[0] = (double)n; o[1] = st[0]; o[2] = st[1]; o[3] = st[2]; o[4] = st[3];
@@ -352,11 +226,11 @@ __global__ __launch_bounds__(STATS_BLOCK) void k_match_stats(stats_in in, int si
         o[15] = (double)sg.stride;
     }
     // ---- dx, dy
-    stats_walk<Q_DX>(in, sg, base, s_vals, 0.f, 0.f, z0, z1);
+    match_walk<Q_DX>(in, sg, base, s_vals, 0.f, 0.f, z0, z1);
     __syncthreads();
     stats_clip(s_vals, m, s_red, ph, st, vlo, vhi);
     if (tid == 0) { o[7] = st[0]; o[8] = st[1]; o[9] = st[2]; o[10] = st[3]; }
-    stats_walk<Q_DY>(in, sg, base, s_vals, 0.f, 0.f, z0, z1);
+    match_walk<Q_DY>(in, sg, base, s_vals, 0.f, 0.f, z0, z1);
     __syncthreads();
     stats_clip(s_vals, m, s_red, ph, st, vlo, vhi);
     if (tid == 0) { o[11] = st[0]; o[12] = st[1]; o[13] = st[2]; o[14] = st[3]; }

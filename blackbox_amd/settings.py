@@ -89,6 +89,15 @@ match_snr_min = 20.0           # flux / fluxerr a star needs on both sides to en
 centroid_radius = 6            # [pix] the windowed centroid reads (2 * radius + 1)^2 pixels around the integer peak
 centroid_niter = 8             # iterations of the windowed centroid
 
+# ---- source shapes of `_cat.fits` and the frame's seeing statistics (header keys S-NOBJ S-FWHM S-FWSTD S-SEEING S-SEESTD
+# S-ELONG S-ELOSTD, blackbox.py:3051-3057; [EXT] SExtractor in zogy: adaptive second moments here) ----
+# Off by default: `_cat.fits` keeps its seven columns and the header gets none of the keys.
+cat_shapes = False             # FWHM, ELONGATION, A, B, THETA, X2, Y2, XY, FLAGS_MASK columns, sub-pixel X_POS / Y_POS, the S-* keys
+shape_snr_min = 20.0           # flux / fluxerr a source needs to enter the frame's statistics (this project's own)
+shape_nmin = 15                # fewer unflagged stars than this in the frame: the six statistics are 'None' (this project's own)
+pixscale = 0.564               # [arcsec/pix] S-SEEING = S-FWHM x pixscale (finding_chart.py:502)
+# the window radius and the number of iterations are the centroid's: centroid_radius, centroid_niter
+
 # calibration files of a reduction (explicit paths; the date-based master selection
 # of master_prep, blackbox.py:4625-4905, is blackbox_amd.masters, run by --master_date)
 bad_pixel_mask = None      # path containing 'bpm' -> 'bpm_{filt}' (blackbox.py:4386)

@@ -444,15 +444,20 @@ class RefCatalog:
             and (ref.shape[0], ref.shape[1], int(size), int(border)) == self.geom
 
 
-def match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, dist_max=None, snr_min=None):
+def match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, dist_max=None, snr_min=None, peaks_off=None):
     """queue the new frame's half of the star match behind its photometry: centroids of the peaks (ys, xs: host, sorted by
     (y, x)) of the background-subtracted frame [work], the mutual match against the RefCatalog [rc] and the table.  Peaks
     on masked pixels (d_mk != 0) are taken out on the device: NaN offset (matches nothing) and flux 0.
+    peaks_off: (d_y32, d_x32, off) where the caller has the peaks on the device as int32 and their centroids already (the
+    source shapes start from the same ones); they are not changed.
     -> device (table float64 [nsub + 1, 16], number of pairs int64 [1]); no host wait"""
     dist_max = settings.match_dist_pix if dist_max is None else dist_max
     snr_min = settings.match_snr_min if snr_min is None else snr_min
-    d_y32, d_x32 = push(ctx, np.asarray(ys, np.int32), np.asarray(xs, np.int32))
-    off = win_centroid(ctx, work, d_y32, d_x32, window_sigma(sub_pn), size, nsy, nsx)
+    if peaks_off is not None:
+        d_y32, d_x32, off = peaks_off
+    else:
+        d_y32, d_x32 = push(ctx, np.asarray(ys, np.int32), np.asarray(xs, np.int32))
+        off = win_centroid(ctx, work, d_y32, d_x32, window_sigma(sub_pn), size, nsy, nsx)
     bad = d_mk != 0
     off = torch.where(bad[:, None], torch.full_like(off, float('nan')), off).contiguous()
     f_m = torch.where(bad, torch.zeros_like(f), f).contiguous()
@@ -460,6 +465,90 @@ def match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, dis
     d_match = match_mutual(ctx, a[:3], rc.lists()[:3], dist_max)
     d_tab = match_stats(ctx, a, rc.lists(), d_match, size, nsy, nsx, snr_min)
     return d_tab, (d_match >= 0).sum().reshape(1)
+
+
+# ---- source shapes of the catalogue and the frame's seeing / elongation statistics ---------
+# header keys S-NOBJ S-FWHM S-FWSTD S-SEEING S-SEESTD S-ELONG S-ELOSTD (blackbox.py:3051-3057; ranges set_qc.py:256-266).
+# [EXT] zogy takes them from SExtractor; here: adaptive second moments (include/bbx.h), parity unpinned.
+SHAPE_COLS = ('c_y', 'c_x', 'Tyy', 'Txx', 'Txy', 'FWHM', 'ELONGATION', 'THETA')
+SHAPE_STAT_COLS = ('n_qualifying', 'stride', 'n_fwhm', 'med_fwhm', 'std_fwhm', 'n_elong', 'med_elong', 'std_elong')
+_SC = {k: i for i, k in enumerate(SHAPE_STAT_COLS)}
+
+
+def src_shapes(ctx, img, mask, d_ys, d_xs, d_off, d_sigw, size, nsy, nsx, radius=None, niter=None):
+    """bbx_src_shapes: adaptive second moments of the sources at the int32 device peaks (d_ys, d_xs) of the frame [img],
+    starting at the centroid offsets d_off [n, 2] (win_centroid) -> device (float32 [n, 8] (SHAPE_COLS), NaN rows where a source
+    fails; uint8 [n]: OR of [mask] (or None) over each window).  No host wait"""
+    radius = settings.centroid_radius if radius is None else radius
+    niter = settings.centroid_niter if niter is None else niter
+    if img.dim() != 2 or img.dtype != torch.float32 or not img.is_contiguous():
+        raise ValueError('contiguous 2-D float32 frame expected')
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(img.shape) or not mask.is_contiguous()):
+        raise ValueError('the mask must be a contiguous uint8 frame of the image shape')
+    n = int(d_ys.numel())
+    if d_off.dtype != torch.float32 or tuple(d_off.shape) != (n, 2) or not d_off.is_contiguous():
+        raise ValueError('contiguous float32 offsets [n, 2] expected')
+    out = torch.empty((n, 8), dtype=torch.float32, device=ctx.device)
+    flags = torch.empty(n, dtype=torch.uint8, device=ctx.device)
+    check(lib.bbx_src_shapes(ctx.h, img.shape[0], img.shape[1], _p(img), _p(mask) if mask is not None else None, n, _p(d_ys), _p(d_xs),
+                             _p(d_off), _p(d_sigw), int(size), int(nsy), int(nsx), int(radius), int(niter), _p(out), _p(flags),
+                             ctx.stream()), 'bbx_src_shapes', ctx.h)
+    return out, flags
+
+
+def empty_shape_table(nsub):
+    """the table of a frame without a qualifying source: counts 0, stride 1, NaN elsewhere (bbx_shape_stats's empty segments)"""
+    t = np.full((nsub + 1, 8), np.nan)
+    t[:, [_SC['n_qualifying'], _SC['n_fwhm'], _SC['n_elong']]] = 0.0
+    t[:, _SC['stride']] = 1.0
+    return t
+
+
+def shape_stats(ctx, d_ys, d_xs, d_shapes, d_flags, d_flux, d_err, size, nsy, nsx, snr_min=None):
+    """bbx_shape_stats of the (y, x)-sorted list -> device float64 [nsy * nsx + 1, 8] (SHAPE_STAT_COLS; last row: the whole
+    frame).  No host wait"""
+    snr_min = settings.shape_snr_min if snr_min is None else snr_min
+    n = int(d_ys.numel())
+    if not n:
+        return torch.from_numpy(empty_shape_table(nsy * nsx)).to(ctx.device)
+    out = torch.empty((nsy * nsx + 1, 8), dtype=torch.float64, device=ctx.device)
+    check(lib.bbx_shape_stats(ctx.h, n, _p(d_ys), _p(d_xs), _p(d_shapes), _p(d_flags), _p(d_flux), _p(d_err), int(size), int(nsy), int(nsx),
+                              float(snr_min), _p(out), ctx.stream()), 'bbx_shape_stats', ctx.h)
+    return out
+
+
+def shape_columns(ys, xs, shp, flags):
+    """the catalogue columns made of the rows of bbx_src_shapes (host, float32 [n, 8]) and its flags: X_POS / Y_POS = peak + 1 +
+    offset (the integer peak where the source has no shape), FWHM, ELONGATION, A, B = sqrt of the eigenvalues of T, THETA,
+    X2 = Txx, Y2 = Tyy, XY = Txy, FLAGS_MASK"""
+    shp = np.asarray(shp, np.float32).reshape(-1, 8)
+    F = np.float32
+    cy, cx, Tyy, Txx, Txy = (shp[:, k] for k in range(5))
+    with np.errstate(invalid='ignore'):
+        tr, df = Tyy + Txx, Txx - Tyy
+        rad = np.sqrt(df * df + F(4) * (Txy * Txy))
+        A, B = np.sqrt((tr + rad) / F(2)), np.sqrt((tr - rad) / F(2))
+    return dict(Y_POS=(np.asarray(ys).astype(F) + F(1)) + np.where(np.isnan(cy), F(0), cy),
+                X_POS=(np.asarray(xs).astype(F) + F(1)) + np.where(np.isnan(cx), F(0), cx),
+                FWHM=shp[:, 5].copy(), ELONGATION=shp[:, 6].copy(), A=A.astype(F), B=B.astype(F), THETA=shp[:, 7].copy(),
+                X2=Txx.copy(), Y2=Tyy.copy(), XY=Txy.copy(), FLAGS_MASK=np.asarray(flags, np.uint8).copy())
+
+
+_SHAPE_HDR = (('S-FWHM', 'med_fwhm', 1, '[pix] median FWHM of the unflagged stars'), ('S-FWSTD', 'std_fwhm', 1, '[pix] sigma (STD) FWHM'),
+              ('S-SEEING', 'med_fwhm', 0, '[arcsec] median seeing of the unflagged stars'), ('S-SEESTD', 'std_fwhm', 0, '[arcsec] sigma (STD) seeing'),
+              ('S-ELONG', 'med_elong', 1, 'median elongation of the unflagged stars'), ('S-ELOSTD', 'std_elong', 1, 'sigma (STD) elongation'))
+
+
+def shape_header(table, nobj, nmin, pixscale):
+    """the table of bbx_shape_stats [nsub + 1, 8] (host) -> {S-NOBJ, S-FWHM, S-FWSTD, S-SEEING, S-SEESTD, S-ELONG, S-ELOSTD:
+    (value, comment)} from the full-frame row; S-SEEING, S-SEESTD = the FWHM values x pixscale.  With fewer than nmin clipped
+    values of either quantity in that row the six statistics are the string 'None' (set_qc's default).  Pure numpy"""
+    full = np.asarray(table, np.float64)[-1]
+    hdr = {'S-NOBJ': (int(nobj), 'number of objects in the catalogue')}
+    good = bool(full[_SC['n_fwhm']] >= nmin and full[_SC['n_elong']] >= nmin)
+    for key, col, plain, comment in _SHAPE_HDR:
+        hdr[key] = ((float(full[_SC[col]]) if plain else float(full[_SC[col]]) * float(pixscale)) if good else 'None', comment)
+    return hdr
 
 
 def run_zogy_frame(ctx, new, ref, sig_new, sig_ref, psf_n, psf_r, scal, size, border, want_S=False, outs=None, ref_rows=None):
@@ -756,7 +845,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          cat_extract=False, cat_nsigma=5.0, trans_extract=True, frame_stats=True, max_sources=200000,
                          zogy_gate=None, ref_bkg_std=None, sigma_frames=False, thumbnails=False, thumbnail_size=None,
                          thumbnail_pngs=False, ref_rows=None, match=False, ref_catalog=None, match_dist=None, match_nmin=None,
-                         match_snr_min=None):
+                         match_snr_min=None, shapes=False, shape_snr_min=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -790,6 +879,13 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       than match_nmin pairs; res['match'] = dict(success, n_new, n_ref, n_pairs, table, fratio_sub, dx_sub,
                       dy_sub), res['ref_catalog'], and header_trans gets Z-DXSTD, Z-DYSTD, Z-FNRSTD, Z-FNRERR.  False: no kernel
                       of bbx_match.hip is launched, no such keys.  match_dist [pix], match_nmin, match_snr_min: settings
+      shapes        : True (with cat_extract and psf_new): every catalogue source gets its adaptive second moments (bbx_src_shapes,
+                      started at the windowed centroids, which the star match shares when it is on too) and the frame its
+                      clipped FWHM / elongation statistics (bbx_shape_stats), both riding the photometry's copy back:
+                      res['catalog'] gains FWHM, ELONGATION, A, B, THETA, X2, Y2, XY, FLAGS_MASK and sub-pixel X_POS / Y_POS,
+                      res['shapes'] = dict(table, n_good), header_new gets S-NOBJ, S-FWHM, S-FWSTD, S-SEEING, S-SEESTD,
+                      S-ELONG, S-ELOSTD (shape_header).  False: no kernel of bbx_shapes.hip is launched, no such keys or columns.
+                      shape_snr_min: settings
       ref_catalog   : a RefCatalog made of the reference and of ref_bkg_std by the caller that keeps both for many frames (used
                       only where it was made of this call's very reference, sigma map and geometry; same result bit for bit)
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
@@ -804,6 +900,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     nsub = nsy * nsx
     have_ref = ref is not None and trans_extract
     do_match = bool(match) and have_ref and psf_new is not None and psf_ref is not None
+    do_shapes = bool(shapes) and bool(cat_extract) and psf_new is not None
 
     # ---- new frame: mesh, subtraction, sigma image, variance
     mini, mini_std = get_back(ctx, new, new_mask, bkg_boxsize=box)
@@ -931,28 +1028,48 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             stamps = source_psfs(ctx, psf_new, sub_pn, ys, xs, nsx, size)
             f, e = psf_optflux(ctx, work, bstd, stamps, ys, xs, v_is_sigma=True)        # (bstd: frame or MiniImage)
             back = [d_mk, f, e]
+            peaks_off = None
+            if do_shapes:
+                # the windowed centroids once, for the shapes and for the star match; the moments and their statistics are
+                # queued behind the photometry and come back with it
+                d_y32, d_x32 = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
+                sigw = window_sigma(sub_pn)
+                peaks_off = (d_y32, d_x32, win_centroid(ctx, work, d_y32, d_x32, sigw, size, nsy, nsx))
+                d_shp, d_sfl = src_shapes(ctx, work, new_mask, d_y32, d_x32, peaks_off[2], sigw, size, nsy, nsx)
+                d_stab = shape_stats(ctx, d_y32, d_x32, d_shp, d_sfl, f, e, size, nsy, nsx, shape_snr_min)
             if do_match:
                 # the star match rides on the same copy back: centroids, match against the reference's catalogue (the run's,
                 # or made here) and the table of clipped statistics are queued behind the photometry
                 rc = ref_catalog if ref_catalog is not None and ref_catalog.matches(ref_side[0], ref_side[1], size, border) else \
                     RefCatalog(ctx, ref_side[0], ref_side[1], ref_mask if ref_grid is None else None, psf_ref, size, border,
                                cat_nsigma=cat_nsigma, sigma_median=hdr_t['S-BKGSTDR'][0], sub_psfs=ref_side[3], max_sources=max_sources)
-                back += match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, match_dist, match_snr_min)
-                mk, f, e, mtab, npairs = fetch(ctx, *back)
+                back += match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, match_dist, match_snr_min,
+                                      peaks_off=peaks_off)
+            if do_shapes:
+                back += [d_shp, d_sfl, d_stab]
+            got = fetch(ctx, *back)
+            mk, f, e = got[:3]
+            if do_match:
+                mtab, npairs = got[3:5]
                 res['ref_catalog'] = rc
                 res['match'] = dict(n_new=int((mk == 0).sum()), n_ref=rc.n, n_pairs=int(npairs[0]))
-            else:
-                mk, f, e = fetch(ctx, *back)
             ok = mk == 0
             ys, xs, pk, f, e = ys[ok], xs[ok], pk[ok], f[ok], e[ok]
+            if do_shapes:
+                shp, sfl, stab = got[-3][ok], got[-2][ok], got[-1]
         else:
             f = e = np.zeros(0, np.float32)
+            shp, sfl, stab = np.zeros((0, 8), np.float32), np.zeros(0, np.uint8), empty_shape_table(nsub)
         if cat_extract:
             peaks = ys
             res['catalog'] = dict(Y_POS=ys.astype(np.float32) + 1, X_POS=xs.astype(np.float32) + 1,
                                   E_FLUX_PEAK=pk.astype(np.float32), E_FLUX_OPT=f, E_FLUXERR_OPT=e,
                                   SNR_OPT=np.where(e > 0, f / np.where(e > 0, e, 1), 0).astype(np.float32))
             hdr['NOBJECTS'] = (len(peaks), 'number of objects detected')
+        if do_shapes:
+            res['catalog'].update(shape_columns(ys, xs, shp, sfl))
+            res['shapes'] = dict(table=stab, n_good=int(stab[nsub, _SC['n_fwhm']]))
+            hdr.update(shape_header(stab, len(ys), settings.shape_nmin, settings.pixscale))
     if 'S-BKG' not in hdr:
         scal_n = host_side_meanwhile()
     if not have_ref:

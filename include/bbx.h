@@ -748,6 +748,40 @@ int bbx_match_stats(bbx_ctx *ctx, int n_a, const int32_t *d_a_ys, const int32_t 
                     const int32_t *d_b_xs, const float *d_b_off, const float *d_b_flux, const float *d_b_err,
                     const int32_t *d_match, int size, int nsy, int nsx, float snr_min, double *d_out, void *stream);
 
+/* ---- source shapes of the full-source catalogue and the frame's seeing / elongation statistics: the header keys S-NOBJ,
+ * S-FWHM, S-FWSTD, S-SEEING, S-SEESTD, S-ELONG, S-ELOSTD (blackbox.py:3051-3057), which set_qc range-checks (S-SEEING
+ * min_max, S-ELONG sigma (1.1, 0.2): set_qc.py:256-266).  In zogy these numbers come from SExtractor ([EXT]: neither is in
+ * the reference tree); here they are the published adaptive second moments (Bernstein & Jarvis 2002, AJ 123, 583;
+ * Hirata & Seljak 2003, MNRAS 343, 459): parity with the reference's values is UNPINNED, the rules below are THIS
+ * PROJECT'S OWN.  Both entries are deterministic: every sum in a fixed order, same input -> same bits.
+ *
+ * bbx_src_shapes: per source, over the (2 radius + 1)^2 pixels around the INTEGER peak (d_ys, d_xs) (1 <= radius <= 10;
+ * pixels off the frame contribute 0), all in float32: c = offset from the peak, starting at d_off[src] (bbx_win_centroid);
+ * W = window covariance, starting at sigma_w^2 I, sigma_w = d_sigw[tile of the integer peak].  Each of niter >= 1 rounds:
+ * w_k = exp(-1/2 d^T W^-1 d) I_k with d = p_k - c; s0 = sum w, m = sum w d / s0, M = sum w d d^T / s0 - m m^T;
+ * c <- c + 2 m; T^-1 = M^-1 - W^-1; W <- T.  (For a Gaussian source of covariance C seen through a Gaussian window W
+ * the weighted moments are M^-1 = C^-1 + W^-1, so T = C; the fixed point W = T is the matched window.)
+ * The source fails, and its whole row is NaN, when d_off is not finite, sigma_w is not positive and finite, s0 <= 0,
+ * det M <= 0 or Myy <= 0, |c_y| or |c_x| > radius / 2, T^-1 is not positive definite (det <= 0 or (T^-1)yy <= 0),
+ * Tyy + Txx > 2 (radius / 2)^2, or anything is not finite.
+ * d_out[nsrc][8] = {c_y, c_x, Tyy, Txx, Txy, FWHM = 2 sqrt(ln 2 (Tyy + Txx)), ELONGATION = sqrt(A^2 / B^2) with A^2, B^2 =
+ * ((Tyy + Txx) +- sqrt((Txx - Tyy)^2 + 4 Txy^2)) / 2, THETA = 1/2 atan2(2 Txy, Txx - Tyy) in degrees from +x}.
+ * d_flags[nsrc] u8 = OR of d_mask over the window pixels on the frame (d_mask NULL: 0), written for failed sources too.
+ * nsrc == 0: nothing is done.  One wave per source, the window in registers, no LDS.                                  */
+int bbx_src_shapes(bbx_ctx *ctx, int ny, int nx, const float *d_img, const uint8_t *d_mask, int nsrc,
+                   const int32_t *d_ys, const int32_t *d_xs, const float *d_off, const float *d_sigw, int size, int nsy,
+                   int nsx, int radius, int niter, float *d_out, uint8_t *d_flags, void *stream);
+
+/* Clipped statistics of FWHM and ELONGATION (columns 5, 6 of d_shapes[nsrc][8]) per segment: the nsy x nsx sub-image tiles
+ * and, last, the whole frame.  The list is SORTED BY (y, x) of the integer peak.  A source qualifies when its FWHM and
+ * ELONGATION are finite, d_flags is 0, err > 0, flux / err >= snr_min and its integer peak lies in the tile.  Selection
+ * (every s-th in list order above BBX_MATCH_CAP), sort and clipping are bbx_match_stats's, by the same device code.
+ * d_out[nsy * nsx + 1][8] float64 = {n_qualifying, stride s, n_fwhm, med_fwhm, std_fwhm, n_elong, med_elong, std_elong};
+ * an empty segment: counts 0, s = 1, NaN elsewhere.  nsrc == 0: nothing is done (d_out is not written).                */
+int bbx_shape_stats(bbx_ctx *ctx, int nsrc, const int32_t *d_ys, const int32_t *d_xs, const float *d_shapes,
+                    const uint8_t *d_flags, const float *d_flux, const float *d_err, int size, int nsy, int nsx,
+                    float snr_min, double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
