@@ -138,6 +138,10 @@ SIGNATURES = {
     'bbx_match_stats': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     'bbx_src_shapes': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'bbx_shape_stats': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    'bbx_psf_select': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _f, _f, _f, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'bbx_psf_stamps': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    'bbx_psf_fit': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    'bbx_psf_chi2': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError if the export is missing

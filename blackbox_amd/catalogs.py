@@ -137,7 +137,8 @@ def save_png_thumbnails(png8, numbers, dir_dest):
 def write_small_products(jobs):
     """the small files of a frame in one call (a worker process of the host pool runs it for blackbox.py's list run, so
     that their formatting does not hold the interpreter lock of the process that drives the GPU): jobs = [(kind, args)],
-    kind in 'image' (fitsio.write_image), 'header' (fitsio.write_header), 'cat' (format_cat), 'trans' (format_cat of
+    kind in 'image' (fitsio.write_image), 'header' (fitsio.write_header), 'psf' (fitsio.write_psfex: path, model with a host
+    basis, header), 'cat' (format_cat), 'trans' (format_cat of
     transient_table(args[0]); an optional fourth argument dict(thumbnails=float32 [n, 4, S, S] or None, png8=uint8 [n, 4, S, S] or
     None, png_dir=) adds the thumbnail columns and / or writes the PNG files of the rows, NUMBER = 1..n)"""
     done = []
@@ -146,6 +147,8 @@ def write_small_products(jobs):
             fitsio.write_image(*args)
         elif kind == 'header':
             fitsio.write_header(*args)
+        elif kind == 'psf':
+            fitsio.write_psfex(*args)
         elif kind == 'cat':
             format_cat(args[0], args[1], cat_type=args[2], header2add=args[3])
         elif kind == 'trans':

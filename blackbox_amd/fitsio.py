@@ -346,3 +346,34 @@ def read_psfex(path):
                     polscal=(float(_hv(h, 'POLSCAL1', 1.0) or 1.0), float(_hv(h, 'POLSCAL2', 1.0) or 1.0)),
                     psf_samp=float(_hv(h, 'PSF_SAMP', 1.0) or 1.0), psf_fwhm=float(_hv(h, 'PSF_FWHM', 0.0) or 0.0))
     raise ValueError('no PSF_MASK table in {}'.format(path))
+
+
+def write_psfex(path, model, header=None):
+    """a model dict of the form read_psfex returns (basis: numpy array or device tensor) -> PSFEx-style `.psf` file: a
+    binary table with one PSF_MASK cell, TDIM1 (S, S, ncoef), and the POL* / PSF* cards read_psfex reads; [header]: further
+    cards (the frame's PSF-* keys).  read_psfex(path) returns what went in, bit for bit"""
+    basis = model['basis']
+    if hasattr(basis, 'detach'):
+        basis = basis.detach().cpu().numpy()
+    basis = np.ascontiguousarray(basis, np.float32)
+    if basis.ndim != 3 or basis.shape[1] != basis.shape[2]:
+        raise ValueError('basis [ncoef, S, S] expected, got {}'.format(basis.shape))
+    ncoef, S, _ = basis.shape
+    poldeg = int(model.get('poldeg', 0))
+    if ncoef != (poldeg + 1) * (poldeg + 2) // 2:
+        raise ValueError('basis has {} planes, polynomial degree {} needs {}'.format(ncoef, poldeg, (poldeg + 1) * (poldeg + 2) // 2))
+    hdr = {'EXTNAME': ('PSF_DATA', 'table name'),
+           'POLNAXIS': (2, 'Number of context parameters'), 'POLNGRP': (1, 'Number of context groups'),
+           'POLNAME1': ('X_IMAGE', 'Name of this context-key'), 'POLGRP1': (1, 'Polynom group for this context-key'),
+           'POLZERO1': (float(model['polzero'][0]), 'Offset value for this context-key'),
+           'POLSCAL1': (float(model['polscal'][0]), 'Scale value for this context-key'),
+           'POLNAME2': ('Y_IMAGE', 'Name of this context-key'), 'POLGRP2': (1, 'Polynom group for this context-key'),
+           'POLZERO2': (float(model['polzero'][1]), 'Offset value for this context-key'),
+           'POLSCAL2': (float(model['polscal'][1]), 'Scale value for this context-key'),
+           'POLDEG1': (poldeg, 'Polynom degree for this context-group'),
+           'PSF_FWHM': (float(model.get('psf_fwhm', 0.0)), 'PSF FWHM'), 'PSF_SAMP': (float(model.get('psf_samp', 1.0)), 'Sampling step of the PSF data'),
+           'PSFNAXIS': (3, 'Dimensionality of the PSF data'), 'PSFAXIS1': (S, 'Number of element along this axis'),
+           'PSFAXIS2': (S, 'Number of element along this axis'), 'PSFAXIS3': (ncoef, 'Number of element along this axis')}
+    for k, v in (header or {}).items():
+        hdr.setdefault(k, v)
+    write_table(path, {'PSF_MASK': basis[None]}, header=hdr)

@@ -98,6 +98,23 @@ shape_nmin = 15                # fewer unflagged stars than this in the frame: t
 pixscale = 0.564               # [arcsec/pix] S-SEEING = S-FWHM x pixscale (finding_chart.py:502)
 # the window radius and the number of iterations are the centroid's: centroid_radius, centroid_niter
 
+# ---- PSF model from the frame's own stars (`_psf.fits`, header keys PSF-*: blackbox.py:3085-3110, set_qc.py:293-296;
+# [EXT] PSFEx in zogy: the rules of include/bbx.h here; this project's own unless a PSFEx parameter is named) ----
+# Off by default: a frame without --psf_new is processed without a PSF as before.
+psf_build = False              # build the model where no PSF file is given (zogy.build_psf)
+psf_size = 49                  # [pix] side of the (square, odd) vignettes and of the model, at most 49
+psf_poldeg = 2                 # degree of the polynomial in the frame position (zogy's psf_poldeg, [EXT])
+psf_seed_fwhm = 4.0            # [pix] FWHM of the window the centroids and adaptive moments start from
+psf_snr_min = 20.0             # peak / S-BKGSTD a PSF star needs (PSFEx SAMPLE_MINSN)
+psf_fwhm_tol = 0.2             # |FWHM / median - 1| a PSF star may have (PSFEx SAMPLE_VARIABILITY)
+psf_elong_max = 1.3            # largest ELONGATION of a PSF star
+psf_iso_frac = 0.05            # a neighbour inside the vignette with a peak above this fraction of the star's excludes it
+psf_stars_nmax = 2048          # at most this many stars enter the fit (every s-th in list order above it)
+psf_nstars_min = 15            # fewer stars than this in the final fit: no model (PSF-P False)
+psf_accuracy = 0.01            # relative error of the model added to the pixel variances (PSFEx PSF_ACCURACY)
+psf_chi2_clip = 3.0            # stars with a chi^2 above this many times the median leave the fit
+psf_nclip = 2                  # rounds of that
+
 # calibration files of a reduction (explicit paths; the date-based master selection
 # of master_prep, blackbox.py:4625-4905, is blackbox_amd.masters, run by --master_date)
 bad_pixel_mask = None      # path containing 'bpm' -> 'bpm_{filt}' (blackbox.py:4386)

@@ -551,6 +551,226 @@ def shape_header(table, nobj, nmin, pixscale):
     return hdr
 
 
+# ---- PSF model from the frame's own stars ---------------------------------------------------
+# `_psf.fits` and the header keys PSF-P PSF-NOBJ PSF-CHI2 PSF-FWHM PSF-SEE PSF-SIZE PSF-CFGS PSF-SAMP PSF-PLDG PSF-FIX
+# (blackbox.py:3085-3110, set_qc.py:293-296, 408-409).  [EXT] zogy runs PSFEx; here: the rules of include/bbx.h
+# (bbx_psfbuild.hip), parity unpinned.
+BBX_ERR_NOTCONV = -5
+PSF_REASONS = ('star', 'no shape or flagged', 'peak S/N', 'FWHM or elongation', 'frame edge', 'neighbour')
+_PSF_HDR = (('PSF-P', 'successfully processed by the PSF build?'), ('PSF-NOBJ', 'number of stars in the final PSF fit'),
+            ('PSF-CHI2', 'mean reduced chi2 of the stars in the final PSF fit'), ('PSF-FWHM', '[pix] median FWHM of the PSF stars'),
+            ('PSF-SEE', '[arcsec] PSF-FWHM x pixel scale'), ('PSF-SIZE', '[pix] size of the PSF model image'),
+            ('PSF-CFGS', '[pix] size of the PSF vignettes'), ('PSF-SAMP', '[pix] sampling step of the PSF model'),
+            ('PSF-PLDG', 'degree of the polynomial in the frame position'), ('PSF-FIX', 'single fixed PSF used for the entire image?'))
+
+
+def psf_ncoef(poldeg):
+    return (poldeg + 1) * (poldeg + 2) // 2
+
+
+def psf_select(ctx, d_ys, d_xs, d_pk, d_shapes, d_flags, sigma_bkg, fwhm_med, V, ny, nx, cap=None, snr_min=None, fwhm_tol=None,
+               elong_max=None, iso_frac=None):
+    """bbx_psf_select of the (y, x)-sorted list; fwhm_med: a number, or a one-element float64 device tensor (the frame row of
+    bbx_shape_stats, no host wait) -> device (reason uint8 [n], star int32 [cap] (zeros past the kept ones), nstar int32 [2])"""
+    S = settings
+    cap = int(S.psf_stars_nmax if cap is None else cap)
+    n = int(d_ys.numel())
+    reason = torch.empty(n, dtype=torch.uint8, device=ctx.device)
+    star = torch.zeros(cap, dtype=torch.int32, device=ctx.device)
+    nstar = torch.empty(2, dtype=torch.int32, device=ctx.device)
+    dev_med = torch.is_tensor(fwhm_med)
+    if dev_med and (fwhm_med.dtype != torch.float64 or fwhm_med.numel() != 1):
+        raise ValueError('fwhm_med: a number or a one-element float64 device tensor expected')
+    check(lib.bbx_psf_select(ctx.h, n, _p(d_ys), _p(d_xs), _p(d_pk), _p(d_shapes), _p(d_flags), float(sigma_bkg),
+                             float(S.psf_snr_min if snr_min is None else snr_min), 0.0 if dev_med else float(fwhm_med),
+                             _p(fwhm_med) if dev_med else None, float(S.psf_fwhm_tol if fwhm_tol is None else fwhm_tol),
+                             float(S.psf_elong_max if elong_max is None else elong_max), float(S.psf_iso_frac if iso_frac is None else iso_frac),
+                             int(V), int(ny), int(nx), cap, _p(reason), _p(star), _p(nstar), ctx.stream()), 'bbx_psf_select', ctx.h)
+    return reason, star, nstar
+
+
+def psf_stamps(ctx, img, mask, d_ys, d_xs, d_shapes, d_sig, V, nstar, d_star=None, d_nstar=None, acc=None):
+    """bbx_psf_stamps: [nstar] vignettes V x V about the centroids of the sources d_star (None: the first nstar of the list)
+    -> device (I float32 [nstar, V, V], w float32 [nstar, V, V], norm float64 [nstar], ok uint8 [nstar])"""
+    if img.dim() != 2 or img.dtype != torch.float32 or not img.is_contiguous():
+        raise ValueError('contiguous 2-D float32 frame expected')
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(img.shape) or not mask.is_contiguous()):
+        raise ValueError('the mask must be a contiguous uint8 frame of the image shape')
+    nstar, V = int(nstar), int(V)
+    dev = ctx.device
+    I = torch.empty((nstar, V, V), dtype=torch.float32, device=dev)
+    w = torch.empty((nstar, V, V), dtype=torch.float32, device=dev)
+    norm = torch.empty(nstar, dtype=torch.float64, device=dev)
+    ok = torch.empty(nstar, dtype=torch.uint8, device=dev)
+    check(lib.bbx_psf_stamps(ctx.h, img.shape[0], img.shape[1], _p(img), _p(mask), int(d_ys.numel()), _p(d_ys), _p(d_xs), _p(d_shapes),
+                             _p(d_sig), nstar, _p(d_star), _p(d_nstar), V, float(settings.psf_accuracy if acc is None else acc), _p(I), _p(w),
+                             _p(norm), _p(ok), ctx.stream()), 'bbx_psf_stamps', ctx.h)
+    return I, w, norm, ok
+
+
+def psf_fit(ctx, I, w, terms, ok, chi2=None, chi2_med=None, clip=None):
+    """bbx_psf_fit over the stars with ok set and, where chi2 [nstar] and chi2_med [1] (device float32) are given, chi2 <=
+    clip * chi2_med -> device basis float32 [ncoef, V, V]"""
+    nstar, V = int(I.shape[0]), int(I.shape[1])
+    ncoef = int(terms.shape[1])
+    basis = torch.empty((ncoef, V, V), dtype=torch.float32, device=ctx.device)
+    check(lib.bbx_psf_fit(ctx.h, nstar, V, ncoef, _p(I), _p(w), _p(terms), _p(ok), _p(chi2), _p(chi2_med),
+                          float(settings.psf_chi2_clip if clip is None else clip), _p(basis), ctx.stream()), 'bbx_psf_fit', ctx.h)
+    return basis
+
+
+def psf_chi2(ctx, I, w, terms, basis, ok):
+    """bbx_psf_chi2 -> device float32 [nstar], NaN where ok is 0"""
+    nstar, V = int(I.shape[0]), int(I.shape[1])
+    chi2 = torch.empty(nstar, dtype=torch.float32, device=ctx.device)
+    check(lib.bbx_psf_chi2(ctx.h, nstar, V, int(terms.shape[1]), _p(I), _p(w), _p(terms), _p(basis), _p(ok), _p(chi2), ctx.stream()),
+          'bbx_psf_chi2', ctx.h)
+    return chi2
+
+
+def psf_chi2_median(ctx, chi2, ok):
+    """np.median of chi2 over the stars with ok set, on the device without knowing their number there: bbx_mini_median of the
+    values taken twice, the others replaced once by the lowest and once by the highest float32 -- the middle pair of that
+    sample is the middle (pair) of the ok values.  No ok star: 0.  -> device float32 [1]"""
+    good = ok != 0
+    big = torch.finfo(torch.float32).max
+    both = torch.cat([torch.where(good, chi2, torch.full_like(chi2, -big)), torch.where(good, chi2, torch.full_like(chi2, big))]).contiguous()
+    med = torch.empty(1, dtype=torch.float32, device=ctx.device)
+    check(lib.bbx_mini_median(ctx.h, both.numel(), _p(both), _p(med), ctx.stream()), 'bbx_mini_median', ctx.h)
+    return med
+
+
+def psf_header(ok, nobj=None, chi2=None, fwhm=None, V=None, poldeg=None, pixscale=None):
+    """{PSF-P, PSF-NOBJ, PSF-CHI2, PSF-FWHM, PSF-SEE, PSF-SIZE, PSF-CFGS, PSF-SAMP, PSF-PLDG, PSF-FIX: (value, comment)}; a build that
+    failed: PSF-P False and the string 'None', set_qc's default, for the rest.  Pure Python"""
+    pixscale = settings.pixscale if pixscale is None else pixscale
+    if ok:
+        vals = (True, int(nobj), float(chi2), float(fwhm), float(fwhm) * float(pixscale), int(V), int(V), 1.0, int(poldeg), False)
+    else:
+        vals = (False,) + ('None',) * 9
+    return {k: (v, c) for (k, c), v in zip(_PSF_HDR, vals)}
+
+
+def _source_sigma(ctx, sigma, shape, ys, xs):
+    """the background sigma at the integer peaks (host arrays): a number, a frame, a mini image (a small 2-D tensor or array: the
+    value of the box the peak falls in) or a MiniImage (its frame is made) -> device float32 [n]"""
+    ny, nx = shape
+    n = len(ys)
+    if isinstance(sigma, MiniImage):
+        sigma = sigma.frame(ctx)
+    if np.isscalar(sigma):
+        return torch.full((n,), float(sigma), dtype=torch.float32, device=ctx.device)
+    if not torch.is_tensor(sigma):
+        sigma = push(ctx, np.ascontiguousarray(sigma, np.float32))
+    if sigma.dim() != 2:
+        raise ValueError('sigma: a number, a frame, a mini image or a MiniImage expected')
+    if tuple(sigma.shape) == (ny, nx):
+        iy, ix = ys, xs
+    else:
+        by, bx = -(-ny // sigma.shape[0]), -(-nx // sigma.shape[1])
+        iy, ix = np.minimum(np.asarray(ys) // by, sigma.shape[0] - 1), np.minimum(np.asarray(xs) // bx, sigma.shape[1] - 1)
+    d_iy, d_ix = push(ctx, np.asarray(iy, np.int64), np.asarray(ix, np.int64)) if n else (torch.empty(0, dtype=torch.int64, device=ctx.device),) * 2
+    return sigma[d_iy, d_ix].to(torch.float32).contiguous()
+
+
+def build_psf(ctx, data_bkgsub, sigma, mask, size, nsy, nsx, cat_nsigma=5.0, sigma_median=None, peaks=None, psf_size=None,
+              poldeg=None, max_sources=200000):
+    """A PSFEx-style model of the frame's PSF from its own stars (include/bbx.h, bbx_psfbuild.hip):
+      peaks of the background-subtracted frame above cat_nsigma x sigma_median (peaks = (ys, xs, pk), host arrays sorted by
+      (y, x), where the caller has searched already) -> windowed centroids and adaptive moments from the seed window
+      settings.psf_seed_fwhm / 2.3548 -> the frame's median FWHM (bbx_shape_stats, flux = peak, err = sigma) -> bbx_psf_select
+      -> bbx_psf_stamps -> bbx_psf_fit over all stars, then settings.psf_nclip rounds of {bbx_psf_chi2, median, fit of the stars
+      within settings.psf_chi2_clip x the median} and a last bbx_psf_chi2.
+    sigma: the background sigma: a number, a frame, a mini image or a MiniImage (_source_sigma); sigma_median: its median
+    (S-BKGSTD; needed unless sigma is a number).  The polynomial terms are those of the integer peak in FITS pixels, where
+    source_psfs evaluates the model.  Every degree up to poldeg (settings.psf_poldeg) that the list could support is fitted, and
+    the degree taken is the largest with 5 coefficients' worth of stars with a vignette; fewer than settings.psf_nstars_min
+    stars in its final fit: no model.  ONE host wait (two when a fit raised the device's soft-fault word), besides the search.
+    -> dict(model: dict(basis device float32 [ncoef, V, V], polzero, polscal, poldeg, psf_samp, psf_fwhm) as fitsio.read_psfex
+            gives it, or None; header: psf_header; stars: dict(n_sources, n_qualifying, stride, reason [n_sources], index, ys,
+            xs [m], ok, used [m], chi2 [m], norm [m]))"""
+    S = settings
+    V = int(psf_size or S.psf_size)
+    poldeg = int(S.psf_poldeg if poldeg is None else poldeg)
+    if V < 1 or V > 49 or not V % 2 or not 0 <= poldeg <= 3:
+        raise ValueError('psf_size odd and at most 49, psf_poldeg 0..3 expected')
+    if data_bkgsub.dim() != 2 or data_bkgsub.dtype != torch.float32 or not data_bkgsub.is_contiguous():
+        raise ValueError('contiguous 2-D float32 frame expected')
+    ny, nx = data_bkgsub.shape
+    if sigma_median is None:
+        if not np.isscalar(sigma):
+            raise ValueError('sigma_median (median of the sigma image) is needed unless sigma is a number')
+        sigma_median = float(sigma)
+    sigma_median = float(sigma_median)
+    fail = dict(model=None, header=psf_header(False), stars=dict(n_sources=0, n_qualifying=0, stride=1))
+    if peaks is None:
+        thr = float(cat_nsigma) * sigma_median
+        if not (np.isfinite(thr) and thr > 0):
+            return fail
+        peaks = find_peaks_arrays(ctx, data_bkgsub, thr, max_out=max_sources)
+    ys, xs, pk = (np.asarray(a) for a in peaks)
+    keep = pk > 0
+    ys, xs, pk = ys[keep].astype(np.int32), xs[keep].astype(np.int32), pk[keep].astype(np.float32)
+    n = int(ys.size)
+    fail['stars']['n_sources'] = n
+    if not n or not (np.isfinite(sigma_median) and sigma_median > 0):
+        return fail
+    nsub = nsy * nsx
+    dev = ctx.device
+    d_y32, d_x32, d_pk = push(ctx, ys, xs, pk)
+    d_sig = _source_sigma(ctx, sigma, (ny, nx), ys, xs)
+    sigw = torch.full((nsub,), float(S.psf_seed_fwhm) / 2.3548, dtype=torch.float32, device=dev)
+    off = win_centroid(ctx, data_bkgsub, d_y32, d_x32, sigw, size, nsy, nsx)
+    d_shp, d_sfl = src_shapes(ctx, data_bkgsub, mask, d_y32, d_x32, off, sigw, size, nsy, nsx)
+    d_stab = shape_stats(ctx, d_y32, d_x32, d_shp, d_sfl, d_pk, d_sig, size, nsy, nsx, S.psf_snr_min)
+    d_fmed = d_stab[nsub, _SC['med_fwhm']:_SC['med_fwhm'] + 1]         # (a view: one float64 of the frame row)
+    cap = max(1, min(int(S.psf_stars_nmax), n))
+    d_reason, d_star, d_nstar = psf_select(ctx, d_y32, d_x32, d_pk, d_shp, d_sfl, sigma_median, d_fmed, V, ny, nx, cap=cap)
+    I, w, d_norm, d_ok = psf_stamps(ctx, data_bkgsub, mask, d_y32, d_x32, d_shp, d_sig, V, cap, d_star=d_star, d_nstar=d_nstar)
+    polzero, polscal = ((nx + 1) / 2.0, (ny + 1) / 2.0), (nx / 2.0, ny / 2.0)
+    degs = [d for d in range(poldeg + 1) if 5 * psf_ncoef(d) <= cap] or [0]
+    idx = d_star.to(torch.int64)
+    fits, back = [], [d_nstar, d_star, d_ok, d_norm, d_reason, d_fmed]
+    for d in degs:
+        terms = push(ctx, psf_poly_terms(xs + 1.0, ys + 1.0, polzero, polscal, d)).index_select(0, idx).contiguous()
+        basis = psf_fit(ctx, I, w, terms, d_ok)
+        used = d_ok != 0
+        for _ in range(int(S.psf_nclip)):
+            chi2 = psf_chi2(ctx, I, w, terms, basis, d_ok)
+            med = psf_chi2_median(ctx, chi2, d_ok)
+            basis = psf_fit(ctx, I, w, terms, d_ok, chi2, med, S.psf_chi2_clip)
+            used = (d_ok != 0) & (chi2 <= float(S.psf_chi2_clip) * med)
+        chi2 = psf_chi2(ctx, I, w, terms, basis, d_ok)
+        nfit = used.sum().reshape(1)
+        csum = torch.where(used, chi2, torch.zeros_like(chi2)).to(torch.float64).sum().reshape(1)
+        fits.append(basis)
+        back += [used.to(torch.uint8), chi2, nfit, csum]
+    try:
+        got = fetch(ctx, *back, check_device_errors=True)
+    except _lib_BBXError as e:
+        if e.code != BBX_ERR_NOTCONV:
+            raise
+        # a fit met a pixel without a positive definite matrix (a degree with too few stars): the numbers decide below
+        got = fetch(ctx, *back)
+    (nq, stride), star, ok, norm, reason, fmed = got[:6]
+    m = min(-(-int(nq) // max(int(stride), 1)), cap)
+    star, ok, norm = star[:m], ok[:m], norm[:m]
+    n_ok = int((ok != 0).sum())
+    k = max([j for j, d in enumerate(degs) if n_ok >= 5 * psf_ncoef(d)] or [0])
+    used, chi2, nfit, csum = got[6 + 4 * k:10 + 4 * k]
+    nfit, fwhm = int(nfit[0]), float(fmed[0])
+    stars = dict(n_sources=n, n_qualifying=int(nq), stride=int(stride), reason=reason, index=star, ys=ys[star], xs=xs[star], ok=ok,
+                 used=used[:m] != 0, chi2=chi2[:m], norm=norm)
+    chi2_mean = float(csum[0]) / nfit if nfit else float('nan')
+    if nfit < int(S.psf_nstars_min) or not np.isfinite(fwhm) or not np.isfinite(chi2_mean):
+        import logging
+        logging.getLogger(__name__).warning('PSF build: %d stars in the final fit (%d sources, %d selected), fewer than the minimum or no '
+                                            'finite statistics: no model', nfit, n, int(nq))
+        return dict(model=None, header=psf_header(False), stars=stars)
+    model = dict(basis=fits[k], polzero=polzero, polscal=polscal, poldeg=degs[k], psf_samp=1.0, psf_fwhm=fwhm)
+    return dict(model=model, header=psf_header(True, nfit, chi2_mean, fwhm, V, degs[k]), stars=stars)
+
+
 def run_zogy_frame(ctx, new, ref, sig_new, sig_ref, psf_n, psf_r, scal, size, border, want_S=False, outs=None, ref_rows=None):
     """ZOGY of whole frames (bbx_zogy_frame): background-subtracted frames + sigma images + PSF
     stamps [nsub, S, S] -> D, S (or None), Scorr, Fpsf, Fpsferr full frames.  sig_new, sig_ref: frames, or both
@@ -845,7 +1065,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          cat_extract=False, cat_nsigma=5.0, trans_extract=True, frame_stats=True, max_sources=200000,
                          zogy_gate=None, ref_bkg_std=None, sigma_frames=False, thumbnails=False, thumbnail_size=None,
                          thumbnail_pngs=False, ref_rows=None, match=False, ref_catalog=None, match_dist=None, match_nmin=None,
-                         match_snr_min=None, shapes=False, shape_snr_min=None):
+                         match_snr_min=None, shapes=False, shape_snr_min=None, psf_build=False, psf_size=None, psf_poldeg=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -886,6 +1106,12 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       res['shapes'] = dict(table, n_good), header_new gets S-NOBJ, S-FWHM, S-FWSTD, S-SEEING, S-SEESTD,
                       S-ELONG, S-ELOSTD (shape_header).  False: no kernel of bbx_shapes.hip is launched, no such keys or columns.
                       shape_snr_min: settings
+      psf_build     : True with psf_new None: the new frame's PSF model is built from its own stars (build_psf) between the
+                      catalogue's peak search and the photometry and used as psf_new from there on (catalogue, shapes, star
+                      match, sub-image PSFs, subtraction); res['psf'] = dict(model, header, stars), header_new gets PSF-P,
+                      PSF-NOBJ, PSF-CHI2, PSF-FWHM, PSF-SEE, PSF-SIZE, PSF-CFGS, PSF-SAMP, PSF-PLDG, PSF-FIX.  A build that fails
+                      (PSF-P False): the frame goes on as one without a PSF (background products only).  With psf_new given, or
+                      False: no kernel of bbx_psfbuild.hip is launched, no such keys.  psf_size, psf_poldeg: settings
       ref_catalog   : a RefCatalog made of the reference and of ref_bkg_std by the caller that keeps both for many frames (used
                       only where it was made of this call's very reference, sigma map and geometry; same result bit for bit)
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
@@ -899,13 +1125,16 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     nsy, nsx = ny // size, nx // size
     nsub = nsy * nsx
     have_ref = ref is not None and trans_extract
-    do_match = bool(match) and have_ref and psf_new is not None and psf_ref is not None
-    do_shapes = bool(shapes) and bool(cat_extract) and psf_new is not None
+    build_here = bool(psf_build) and psf_new is None                 # the PSF of the new frame is made below, behind the peak search
+    have_psf = psf_new is not None or build_here
+    do_match = bool(match) and have_ref and have_psf and psf_ref is not None
+    do_shapes = bool(shapes) and bool(cat_extract) and have_psf
 
     # ---- new frame: mesh, subtraction, sigma image, variance
     mini, mini_std = get_back(ctx, new, new_mask, bkg_boxsize=box)
     work = torch.empty_like(new)
-    want_cat = (cat_extract or do_match) and psf_new is not None
+    want_phot = cat_extract or do_match
+    want_cat = (want_phot or (build_here and have_ref)) and have_psf
     if want_cat:
         # the kernel that writes the background-subtracted frame lists the pixels above cat_nsigma x S-BKGSTD for the
         # catalogue's peak search; S-BKGSTD = median of the sigma mini image, taken on the device for that
@@ -1004,22 +1233,35 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     # cat_nsigma x S-BKGSTD, PSF-weighted optimal flux at each (zogy.get_psfoptflux)
     res['catalog'] = None
     mtab = None
-    if (cat_extract or do_match) and sub_pn is not None:
+    if want_cat:
         thr = float(cat_nsigma) * hdr['S-BKGSTD'][0]
         if np.isfinite(thr) and thr > 0:
             pending = find_peaks_enqueue(ctx, work, thr, max_out=max_sources)
-            if do_match:
+            if do_match and not build_here:
                 ref_side = prepare_reference()                       # (behind the search: its zoom would drop the candidate list)
             scal_n = host_side_meanwhile()
             ys, xs, pk = find_peaks_collect(ctx, pending)
         else:                                                        # no usable noise level: nothing is significant
             lib.bbx_zoom_candidates(ctx.h, None, 0.0)
-            if do_match:
+            if do_match and not build_here:
                 ref_side = prepare_reference()
             scal_n = host_side_meanwhile()
             ys = xs = np.zeros(0, np.int32); pk = np.zeros(0, np.float32)
         keep = pk > 0
         ys, xs, pk = ys[keep], xs[keep], pk[keep]
+        if build_here:
+            # the model from this very list of peaks; from here on the frame is one whose PSF was given
+            res['psf'] = build_psf(ctx, work, mini_std, new_mask, size, nsy, nsx, cat_nsigma, sigma_median=hdr['S-BKGSTD'][0],
+                                   peaks=(ys, xs, pk), psf_size=psf_size, poldeg=psf_poldeg, max_sources=max_sources)
+            hdr.update(res['psf']['header'])
+            psf_new = res['psf']['model']
+            if psf_new is not None:
+                sub_pn = subimage_psfs(ctx, psf_new, nsy, nsx, size)
+                if do_match:
+                    ref_side = prepare_reference()
+            else:                                                    # no model: the frame of today without --psf_new
+                want_phot = do_match = do_shapes = have_ref = False
+    if want_phot and sub_pn is not None:
         if ys.size:
             # peaks on masked pixels are dropped; their mask values come back with the fluxes (one host wait: the photometry
             # of the few masked ones is made and thrown away)

@@ -782,6 +782,60 @@ int bbx_shape_stats(bbx_ctx *ctx, int nsrc, const int32_t *d_ys, const int32_t *
                     const uint8_t *d_flags, const float *d_flux, const float *d_err, int size, int nsy, int nsx,
                     float snr_min, double *d_out, void *stream);
 
+/* ---- a PSF model from the frame's own stars (the _psf.fits product and the PSF-* header keys: blackbox.py:3085-3110,
+ * set_qc.py:293-296, 408-409; bbx_psfbuild.hip).  In zogy the model comes from PSFEx ([EXT]: it is not in the reference
+ * tree): parity with its numbers is UNPINNED, the rules below are THIS PROJECT'S OWN; only the form of the result -- a
+ * polynomial in the normalised frame position over a cube of basis images, what bbx_psf_model evaluates -- is PSFEx's.
+ * All four entries are deterministic: no float atomics, every sum in a fixed order, same input -> same bits.
+ *
+ * bbx_psf_select: the PSF stars of a source list SORTED BY (y, x) of the integer peak (d_ys, d_xs), with peak values d_pk,
+ * the rows d_shapes[n][8] and flags d_flags[n] of bbx_src_shapes.  A source is a star when, in this order (d_reason[n] u8 =
+ * 0, or the number of the first rule it fails): 1 its shape row is finite and its flags are 0; 2 pk / sigma_bkg >= snr_min;
+ * 3 |FWHM / fwhm_med - 1| <= fwhm_tol and ELONGATION <= elong_max (fwhm_med: the float argument, or, where d_fwhm_med is
+ * given, that device double as float -- the frame row of bbx_shape_stats without a host wait); 4 the integer peak is at
+ * least V / 2 + 3 pixels from every frame edge; 5 no other source of the list with pk > iso_frac * its own pk has its
+ * integer peak within Chebyshev distance V / 2 (band search over the sorted list, as bbx_match_mutual).  All in float32.
+ * d_nstar[2] = {n qualifying, stride s}, s = ceil(n qualifying / cap) (1 where they fit); d_star[cap] = the indices of every
+ * s-th star in list order (ceil(n qualifying / s) entries; the rest is not written), by a prefix count, not by atomics.
+ * V odd, <= 49; 1 <= cap <= BBX_MATCH_CAP.  n == 0: d_nstar = {0, 1}.
+ *
+ * bbx_psf_stamps: one V x V vignette per star s < nstar, of source src = d_star[s] (d_star NULL: src = s) of the list
+ * (d_ys, d_xs, d_shapes, d_sig: per source), centred on its CENTROID (c_y, c_x) = d_shapes[src][0..1]: pixel (r, c) is the
+ * LANCZOS3 interpolation of the frame at (y + c_y + r - V/2, x + c_x + c - V/2), separable, six taps per axis about the
+ * floor, each axis' taps normalised to unit sum (float64, then float32; the co-add's kernel), a row pass then a column
+ * pass, float32 products added in float32 in tap order.  norm = sum of the vignette pixels with (r - V/2)^2 + (c - V/2)^2
+ * <= (V/2)^2 in float64; I = vignette / norm (float64 division, then float32); w = 1 / var (float32) with var = q (max(
+ * vignette, 0) + sigma^2) / norm^2 + (acc I)^2 in float64, sigma = d_sig[src], q = (sum wy^2)(sum wx^2) the variance
+ * factor of the resampling (covariances neglected).  The star fails -- d_ok[s] = 0, d_norm[s] = 0, its I and w all 0 --
+ * when its centroid or sigma is not finite, any of the (V + 5)^2 pixels under the vignette and its taps is off the frame
+ * or not finite, d_mask (may be NULL) is set under the V x V pixels about the floor of the centroid, or norm is not
+ * positive and finite.  d_nstar (may be NULL): the device pair of bbx_psf_select; stars s >= ceil(n / stride) fail
+ * likewise, so nstar can be the capacity.  One workgroup per star, the window in LDS.
+ *
+ * bbx_psf_fit: per vignette pixel p the weighted least squares min sum_s w_sp (I_sp - sum_k a_kp t_sk)^2 over the stars
+ * with d_ok[s] != 0 and, where d_chi2 is given, d_chi2[s] <= clip * d_chi2_med[0] (float32; a NaN never passes).
+ * d_terms[nstar][ncoef] float32 (the PSFEx polynomial terms), ncoef = 1, 3, 6 or 10.  Normal matrix and right-hand side in
+ * float64, stars in list order within each of the workgroup's 8 shares, the shares added in order; Cholesky in float64.
+ * A pixel whose matrix is not positive definite (a pivot <= 1e-13 of its diagonal element) gets 0 in every plane and
+ * raises the device error word (BBX_ERR_NOTCONV at the next bbx_sync).  d_basis[ncoef][V][V] float32.
+ *
+ * bbx_psf_chi2: d_chi2[s] = sum_p w_sp (I_sp - model_sp)^2 / V^2 as float32, model_sp = the float32 fma chain over k of
+ * t_sk basis_kp (bbx_psf_model's arithmetic), difference, square and sum in float64 in a fixed order; NaN where d_ok[s]
+ * is 0.  One workgroup per star.                                                                                      */
+int bbx_psf_select(bbx_ctx *ctx, int n, const int32_t *d_ys, const int32_t *d_xs, const float *d_pk,
+                   const float *d_shapes, const uint8_t *d_flags, float sigma_bkg, float snr_min, float fwhm_med,
+                   const double *d_fwhm_med, float fwhm_tol, float elong_max, float iso_frac, int V, int ny, int nx,
+                   int cap, uint8_t *d_reason, int32_t *d_star, int32_t *d_nstar, void *stream);
+int bbx_psf_stamps(bbx_ctx *ctx, int ny, int nx, const float *d_img, const uint8_t *d_mask, int nsrc,
+                   const int32_t *d_ys, const int32_t *d_xs, const float *d_shapes, const float *d_sig, int nstar,
+                   const int32_t *d_star, const int32_t *d_nstar, int V, float acc, float *d_I, float *d_w,
+                   double *d_norm, uint8_t *d_ok, void *stream);
+int bbx_psf_fit(bbx_ctx *ctx, int nstar, int V, int ncoef, const float *d_I, const float *d_w, const float *d_terms,
+                const uint8_t *d_ok, const float *d_chi2, const float *d_chi2_med, float clip, float *d_basis,
+                void *stream);
+int bbx_psf_chi2(bbx_ctx *ctx, int nstar, int V, int ncoef, const float *d_I, const float *d_w, const float *d_terms,
+                 const float *d_basis, const uint8_t *d_ok, float *d_chi2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
