@@ -126,6 +126,9 @@ SIGNATURES = {
     'bbx_zogy_refrows_fill': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'bbx_zogy_refrows_fill_mini': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'bbx_zogy_refrows': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'bbx_zogy_refpsf_bytes': (C.c_size_t, [_i, _i, _i, _i]),
+    'bbx_zogy_refpsf_fill': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'bbx_zogy_refpsf': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i]),
     'bbx_psf_optflux_mini': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'bbx_psf_optflux': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'bbx_psf_optflux_sigma': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -73,6 +73,9 @@ struct bbx_ctx {
     const void* zrows_ref;     // were made of: the reference frame, its sigma frame or spline coefficients, (ny, nx, size, border)
     const void* zrows_sig;
     int    zrows_geom[4];
+    const float2* zpsf;        // bbx_zogy_refpsf: the reference PSF's prepared spectra (caller's buffer; NULL: none) and what they were
+    const float* zpsf_stamps;  // made of: the reference's stamps [nsub][S][S], S, (ny, nx, size, border)
+    int    zpsf_S, zpsf_geom[4];
     const float* bcand_med;    // bbx_zoom_candidates: device scalar m; the next bbx_spline_zoom_sub lists |out| >= (float)(m * bcand_nsig) (WS_BCAND, CNT_BCAND)
     double bcand_nsig;
     const float* bcand_img;    // the frame the list in WS_BCAND belongs to (consumed by bbx_find_peaks), its median scalar and factor

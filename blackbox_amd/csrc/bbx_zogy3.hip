@@ -162,6 +162,13 @@ __device__ __forceinline__ void st_nt(float4* p, float4 v) {
     *p = v;
 #endif
 }
+__device__ __forceinline__ void st_nt(float2* p, float2 v) {
+#if Z3_NT
+    __builtin_nontemporal_store(z3_v2{v.x, v.y}, reinterpret_cast<z3_v2*>(p));
+#else
+    *p = v;
+#endif
+}
 __device__ __forceinline__ void st_nt(float* p, float v) {
 #if Z3_NT
     __builtin_nontemporal_store(v, p);
@@ -613,10 +620,14 @@ __global__ __launch_bounds__(256) void k_psf_rowdft(const float* __restrict__ ps
 // KS (small grid): k_n^, k_r^ are not taken back to real space here.  Their entries with ky and kx multiples of F go to the
 // half spectra of the small grid, Ukr[sub][which][kx / F][ky / F] (which: 0 k_r^, 1 k_n^; Ukn then holds the cells of the window
 // check, zeroed here); k_ks_cols and k_ks_rows take them from there.
-template <class P, bool KS>
+// PREP (prepared reference PSF, bbx_zogy_refpsf; full-grid path -- on the small-grid path k_img_cols does this kernel's work):
+// Q holds the new stamps' row DFTs only and one pass (Pn^) runs; Pr^ comes from the prepared buffer cPr (C layout,
+// k_refpsf_cols: the bits pass 1 would make), a thread's entries loaded into registers behind the transform; cP is then a
+// float2 array that takes Pn^ alone.
+template <class P, bool KS, bool PREP = false>
 __global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_psf_cols(const float2* __restrict__ Q, int S,
                                                          const zscal* __restrict__ sc, const float2* __restrict__ twg,
-                                                         float4* __restrict__ cP,
+                                                         float4* __restrict__ cP, const float2* __restrict__ cPr,
                                                          float2* __restrict__ Ukn, float2* __restrict__ Ukr,
                                                          double* __restrict__ fs_partial, int nsub, int wh) {
     extern __shared__ float2 s[];
@@ -632,8 +643,8 @@ __global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_psf_cols(const floa
     const int h = S / 2;
     const size_t cbase = (size_t)(sub * P::G + g) * P::NL * P::L;
     constexpr int RT = P::THREADS, NE = (P::NL * P::L + RT - 1) / RT;
-    float2 park[NE];                                               // Pn^, then kn^
-    for (int pass = 0; pass < 2; pass++) {
+    float2 park[NE];                                               // Pn^ (PREP: Pr^), then kn^
+    for (int pass = 0; pass < (PREP ? 1 : 2); pass++) {
         const float2* qs = Q + ((size_t)pass * nsub + sub) * S * P::HP;
         for (int e = threadIdx.x; e < P::NL * P::LS; e += blockDim.x) s[e] = make_float2(0.f, 0.f);
         __syncthreads();
@@ -650,10 +661,15 @@ __global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_psf_cols(const floa
         ZSTAMP(0, 2 + 3 * pass);
         fft_fwd<P>(s, tw, S - h);                                      // the stamp's rows: [0, S - h) and [L - h, L)
         ZSTAMP(0, 3 + 3 * pass);
-        if (pass == 0) {
+        if (!PREP && pass == 0) {
             R_LOOP(k, e, l, p) park[k] = s[l * P::LS + npos(p)];      // Pn^ waits in registers while Pr^ is transformed
             __syncthreads();
         }
+    }
+    if constexpr (PREP) {
+        const int t = opaque_tid();
+#pragma unroll
+        for (int k = 0; k < NE; k++) park[k] = ld_nt(cPr + cbase + min(t + k * RT, P::NL * P::L - 1));
     }
     const zscal z = sc[sub];
     const float sn2 = z.sn * z.sn, sr2 = z.sr * z.sr, fn2 = z.fn * z.fn, fr2 = z.fr * z.fr;
@@ -664,7 +680,7 @@ __global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_psf_cols(const floa
         float4 cp = make_float4(0.f, 0.f, 0.f, 0.f);
         if (kx < P::H) {
             const double wgt = (kx == 0 || (P::L % 2 == 0 && kx == P::L / 2)) ? 1.0 : 2.0;
-            const float2 pn = park[k], pr = s[l * P::LS + npos(p)];
+            const float2 pn = PREP ? s[l * P::LS + npos(p)] : park[k], pr = PREP ? park[k] : s[l * P::LS + npos(p)];
             const float pn2 = pn.x * pn.x + pn.y * pn.y, pr2 = pr.x * pr.x + pr.y * pr.y;
             const float den = (sn2 * fr2) * pr2 + (sr2 * fn2) * pn2;
             // one division per entry: 1 / den as the square of 1 / sqrt(den) (a float32 division is ~10 instructions,
@@ -679,7 +695,8 @@ __global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_psf_cols(const floa
         }
         // k_img_cols gets the two spectra themselves (16 bytes per entry, one load) and forms 1 / sqrt(den) and the
         // coefficients of D^, S_n^, S_r^ from them again (rounds 3-4: A, B and sqrt(den), 20 bytes in three loads)
-        st_nt(cP + cbase + e, cp);
+        if constexpr (PREP) st_nt(reinterpret_cast<float2*>(cP) + cbase + e, make_float2(cp.x, cp.y));
+        else st_nt(cP + cbase + e, cp);
         if constexpr (KS) {
             constexpr int F = small_of<P>::F, M = P::L / F, HM = M / 2 + 1;
             const int ky = kofp<P>(p);
@@ -728,6 +745,34 @@ __global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_psf_cols(const floa
         fs_partial[((size_t)threadIdx.x * nsub + sub) * P::G + g] = tot;      // [5][nsub][G]
     }
     ZSTAMP(0, 11);
+}
+
+// bbx_zogy_refpsf_fill: pass 1 of k_psf_cols for the reference's stamps alone (Q: their row DFTs) -- the same lines, the
+// same transform -- and the spectrum Pr^ of the column group into the caller's buffer in C layout (the order of R_LOOP),
+// zero in the padding columns kx >= H as k_psf_cols writes them.
+template <class P>
+__global__ __launch_bounds__(P::THREADS, P::MINW_PSF) void k_refpsf_cols(const float2* __restrict__ Q, int S, const float2* __restrict__ twg,
+                                                            float2* __restrict__ cPr, int nsub) {
+    extern __shared__ float2 s[];
+    WG_TASK(P::G, nsub, g, sub);
+    const aux_t aux = aux_setup<P>(s + P::NL * P::LS, twg);
+    const float2* tw = aux.tw;
+    const int h = S / 2;
+    const size_t cbase = (size_t)(sub * P::G + g) * P::NL * P::L;
+    constexpr int RT = P::THREADS, NE = (P::NL * P::L + RT - 1) / RT;
+    const float2* qs = Q + (size_t)sub * S * P::HP;
+    for (int e = threadIdx.x; e < P::NL * P::LS; e += blockDim.x) s[e] = make_float2(0.f, 0.f);
+    __syncthreads();
+    for (int e = threadIdx.x; e < P::NL * S; e += blockDim.x) {
+        const int ll = e % P::NL, j = e / P::NL;
+        const int kk = g * P::NL + ll;
+        if (kk >= P::H) continue;
+        const int y = ((j - h) % P::L + P::L) % P::L;
+        s[ll * P::LS + npos(y)] = qs[(size_t)j * P::HP + kk];
+    }
+    __syncthreads();
+    fft_fwd<P>(s, tw, S - h);
+    R_LOOP(k, e, l, p) cPr[cbase + e] = (g * P::NL + l < P::H) ? s[l * P::LS + npos(p)] : make_float2(0.f, 0.f);
 }
 
 // inverse row pass of kr^, kn^ -> kr, kn -> squares -> forward row pass, T tiles
@@ -1074,34 +1119,128 @@ __global__ __launch_bounds__(P::LIGHT_THREADS, P::MINW_LIGHT) void k_img_rows_on
 // PREP (prepared reference, bbx_zogy_refrows): TR is R^ itself, column-transformed by k_cols_fwd (C layout, the order of
 // R_LOOP): a thread loads its own entries into registers behind the transform of N, N^ stays in the lines, and the load of
 // the T_R tiles, its two barriers and one forward transform are gone.
-template <class P, bool PREP>
+// PPSF 1 (prepared reference PSF as well, bbx_zogy_refpsf): cP is a float2 array of Pn^ alone and cPr the prepared Pr^; the
+// float4 of an entry is put together from two 8-byte loads, in the same two batches.
+// PPSF 2 (the same on the small-grid path): no Pn^ array and no k_psf_cols launch either.  The workgroup first does pass 1 of
+// k_psf_cols for the new stamps (pf.Q: their row DFTs), N's tiles and its Pr^ entries travelling to registers behind that
+// transform; a loop of its own, in front of N's transform, parks Pn^ and emits what k_psf_cols<P, true> emitted, by the same
+// expressions in the same thread-to-entry mapping: the F_S / Parseval partial sums, the samples of k_r^, k_n^ for the small
+// grid (pf.Ksm) and the zeroed cells of the window check (pf.kchk).  Of Pr^ the first half stays in registers across N's
+// transform; the second is read again behind it (all of Pn^, Pr^ and R^ parked at once do not fit 85 VGPRs).
+struct psf_fuse_args { const float2* Q; int S; float* kchk; float2* Ksm; double* fs_partial; };
+template <class P, bool PREP, int PPSF = 0>
 __global__ __launch_bounds__(P::THREADS, P::MINW) void k_img_cols(const float2* __restrict__ TN, const float2* __restrict__ TR, const float4* __restrict__ cP,
-                                                         const zscal* __restrict__ sc, const float2* __restrict__ twg,
+                                                         const float2* __restrict__ cPr, const zscal* __restrict__ sc, const float2* __restrict__ twg,
                                                          float2* __restrict__ UD, float2* __restrict__ USn, float2* __restrict__ USr,
-                                                         float2* __restrict__ HSn, float2* __restrict__ HSr, int nsub, chunk_args ch) {
+                                                         float2* __restrict__ HSn, float2* __restrict__ HSr, int nsub, chunk_args ch, psf_fuse_args pf) {
     extern __shared__ float2 s[];
+    if (PPSF == 2 && blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < 4 * nsub; i += blockDim.x) pf.kchk[i] = 0.f;
+    }
     WG_TASK(P::G, nsub, g, sub);
     ZSTAMP_HEAD(3);
     const aux_t aux = aux_setup<P>(s + P::NL * P::LS, twg);
     const float2* tw = aux.tw;
     const size_t cbase = (size_t)(sub * P::G + g) * P::NL * P::L;
-    load_t_lines<P>(TN, sub, g, s);
     constexpr int RT = P::THREADS, NE = (P::NL * P::L + RT - 1) / RT;
+    constexpr int NC0 = NE / 2;
+    float4 c0[NC0], c1[NE - NC0];
+    float2 pnr[PPSF == 2 ? NE : 1];                                // PPSF 2: this thread's entries of Pn^
+    if constexpr (PPSF == 2) {
+        const int h = pf.S / 2;
+        const float2* qs = pf.Q + (size_t)sub * pf.S * P::HP;
+        for (int e = threadIdx.x; e < P::NL * P::LS; e += blockDim.x) s[e] = make_float2(0.f, 0.f);
+        __syncthreads();
+        for (int e = threadIdx.x; e < P::NL * pf.S; e += blockDim.x) {
+            const int ll = e % P::NL, j = e / P::NL;
+            const int kk = g * P::NL + ll;
+            if (kk >= P::H) continue;
+            const int y = ((j - h) % P::L + P::L) % P::L;
+            s[ll * P::LS + npos(y)] = qs[(size_t)j * P::HP + kk];
+        }
+        __syncthreads();
+        t_regs<P, P::THREADS> rn;                                  // T_N and Pr^ on their way while the stamps are transformed
+        fetch_t_lines<P, P::THREADS>(TN, sub, g, rn);
+        float2 pra[NE];
+        {
+            // (the second half is read again behind N's transform, as the batches below have it: plain loads keep it near)
+            const int t = opaque_tid();
+#pragma unroll
+            for (int k = 0; k < NE; k++) {
+                const float2* q = cPr + cbase + min(t + k * RT, P::NL * P::L - 1);
+                pra[k] = k < NC0 ? ld_nt(q) : *q;
+            }
+        }
+        fft_fwd<P>(s, tw, pf.S - h);
+        // what k_psf_cols<P, true> computes from the two spectra, by its expressions in its thread-to-entry mapping (its own
+        // 1 / den: the square of 1 / sqrt(den) by division); Pn^ is parked, zero in the padding columns kx >= H as k_psf_cols
+        // writes them
+        const zscal z = sc[sub];
+        const float sn2 = z.sn * z.sn, sr2 = z.sr * z.sr, fn2 = z.fn * z.fn, fr2 = z.fr * z.fr;
+        double fs = 0.0, sk2n = 0.0, sk2r = 0.0;
+        R_LOOP(k, e, l, p) {
+            const int kx = g * P::NL + l;
+            float2 pn = make_float2(0.f, 0.f);
+            if (kx < P::H) {
+                const double wgt = (kx == 0 || (P::L % 2 == 0 && kx == P::L / 2)) ? 1.0 : 2.0;
+                const float2 pr = pra[k];
+                pn = s[l * P::LS + npos(p)];
+                const float pn2 = pn.x * pn.x + pn.y * pn.y, pr2 = pr.x * pr.x + pr.y * pr.y;
+                const float den = (sn2 * fr2) * pr2 + (sr2 * fn2) * pn2;
+                const float sd = sqrtf(den), isd = 1.0f / sd, rden = isd * isd;
+                const float2 kr = cscale(make_float2(pr.x, -pr.y), z.fr * fn2 * pn2 * rden);
+                const float2 kn = cscale(make_float2(pn.x, -pn.y), z.fn * fr2 * pr2 * rden);
+                fs += wgt * (double)(fn2 * pn2 * fr2 * pr2 * rden);
+                sk2n += wgt * (double)(kn.x * kn.x + kn.y * kn.y);
+                sk2r += wgt * (double)(kr.x * kr.x + kr.y * kr.y);
+                constexpr int F = small_of<P>::F, M = P::L / F, HM = M / 2 + 1;
+                const int ky = kofp<P>(p);
+                if (kx % F == 0 && ky % F == 0) {
+                    const size_t o = ((size_t)sub * 2 * HM + kx / F) * M + ky / F;
+                    pf.Ksm[o] = kr; pf.Ksm[o + (size_t)HM * M] = kn;
+                }
+            }
+            pnr[k] = pn;
+        }
+#pragma unroll
+        for (int k = 0; k < NC0; k++) c0[k] = make_float4(0.f, 0.f, pra[k].x, pra[k].y);
+        // the partial sums of the column group, reduced as k_psf_cols reduces them
+        __shared__ double red[3][P::THREADS / 64];
+        fs = wave_sum_f64(fs); sk2n = wave_sum_f64(sk2n); sk2r = wave_sum_f64(sk2r);
+        if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = fs; red[1][threadIdx.x >> 6] = sk2n; red[2][threadIdx.x >> 6] = sk2r; }
+        __syncthreads();
+        if (threadIdx.x < 3) {
+            double tot = 0.0;
+            for (int i = 0; i < (int)blockDim.x / 64; i++) tot += red[threadIdx.x][i];
+            pf.fs_partial[((size_t)threadIdx.x * nsub + sub) * P::G + g] = tot;      // [3][nsub][G]
+        }
+        pack_t_lines<P, P::THREADS>(rn, s);
+    } else
+    load_t_lines<P>(TN, sub, g, s);
     // N^ waits in registers for R^; then one loop makes D^, S_n^ (both parked) and S_r^ (into the lines) from A, B, sqrt(den)
     float2 park[NE], parkd[NE];
     // the PSF spectra of this column group: the first half of a thread's entries is on its way while R is transformed, the
     // second half goes out in one round behind it (a load inside the guarded loop below waits for its own round trip in
     // every iteration: 8 x 2 700 cycles of this kernel's 95 000 in round 4)
-    constexpr int NC0 = NE / 2;
-    float4 c0[NC0], c1[NE - NC0];
     float2 rh[PREP ? NE : 1];                                      // PREP: this thread's entries of R^
+    static_assert(PREP || !PPSF, "prepared PSF spectra go with prepared rows");
+    static_assert(PPSF != 2 || small_of<P>::ok, "Pn^ is formed here on the small-grid path only");
+    const auto ld_c = [&](int e) -> float4 {
+        if constexpr (PPSF == 2) {
+            const float2 pr = ld_nt(cPr + cbase + e);              // (x, y stay unused: Pn^ is in pnr)
+            return make_float4(0.f, 0.f, pr.x, pr.y);
+        } else if constexpr (PPSF == 1) {
+            const float2 pn = ld_nt(reinterpret_cast<const float2*>(cP) + cbase + e), pr = ld_nt(cPr + cbase + e);
+            return make_float4(pn.x, pn.y, pr.x, pr.y);
+        } else return ld_nt(cP + cbase + e);
+    };
     if constexpr (PREP) {
         {
             const int t = opaque_tid();
 #pragma unroll
             for (int k = 0; k < NE; k++) rh[k] = ld_nt(TR + cbase + min(t + k * RT, P::NL * P::L - 1));
 #pragma unroll
-            for (int k = 0; k < NC0; k++) c0[k] = ld_nt(cP + cbase + min(t + k * RT, P::NL * P::L - 1));
+            for (int k = 0; k < NC0; k++) if (PPSF != 2) c0[k] = ld_c(min(t + k * RT, P::NL * P::L - 1));
         }
         __syncthreads();
         ZSTAMP(3, 1);
@@ -1136,7 +1275,7 @@ __global__ __launch_bounds__(P::THREADS, P::MINW) void k_img_cols(const float2* 
     {
         const int t = opaque_tid();
 #pragma unroll
-        for (int k = NC0; k < NE; k++) c1[k - NC0] = ld_nt(cP + cbase + min(t + k * RT, P::NL * P::L - 1));
+        for (int k = NC0; k < NE; k++) c1[k - NC0] = ld_c(min(t + k * RT, P::NL * P::L - 1));
     }
     const zscal z = sc[sub];
     const float cn = (z.sr * z.sr) * (z.fn * z.fn), cr = (z.sn * z.sn) * (z.fr * z.fr);      // den = cr |Pr^|^2 + cn |Pn^|^2
@@ -1145,7 +1284,7 @@ __global__ __launch_bounds__(P::THREADS, P::MINW) void k_img_cols(const float2* 
         float2* q = s + l * P::LS + npos(p);
         const float2 r = PREP ? rh[PREP ? k : 0] : *q, n = PREP ? *q : park[k];
         const float4 c = k < NC0 ? c0[k < NC0 ? k : 0] : c1[k >= NC0 ? k - NC0 : 0];      // (Pn^, Pr^); zero in the padding columns kx >= H
-        const float2 pn = make_float2(c.x, c.y), pr = make_float2(c.z, c.w);
+        const float2 pn = PPSF == 2 ? pnr[PPSF == 2 ? k : 0] : make_float2(c.x, c.y), pr = make_float2(c.z, c.w);
         const float pn2 = pn.x * pn.x + pn.y * pn.y, pr2 = pr.x * pr.x + pr.y * pr.y;
         const float den = cr * pr2 + cn * pn2;
         const float isd = (g * P::NL + l < P::H) ? __builtin_amdgcn_rsqf(den) : 0.f, rden = isd * isd;
@@ -1471,6 +1610,8 @@ template <class P> static int lds_attrs(bbx_ctx* ctx) {
     if (ctx->zogy3_attr_L == P::L) return BBX_OK;
     const int lds = (int)lds_bytes<P>();
     BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_refpsf_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     if constexpr (small_of<P>::ok) {
         typedef typename small_of<P>::type PK;
         BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -1483,6 +1624,8 @@ template <class P> static int lds_attrs(bbx_ctx* ctx) {
     BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows_one<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if constexpr (small_of<P>::ok) BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     BBX_HIP(hipFuncSetAttribute((const void*)k_var_cols<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     BBX_HIP(hipFuncSetAttribute((const void*)k_var_cols<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     BBX_HIP(hipFuncSetAttribute((const void*)k_final_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fin_bytes<P>()));
@@ -1533,6 +1676,17 @@ static int fill_ref_rows(bbx_ctx* ctx, const float2* d_tw, int ny, int nx, int s
     BBX_LAUNCH_CHECK();
     return BBX_OK;
 }
+// the reference PSF's spectra Pr^ into a caller's buffer [nsub][G][NL L] (C layout; bbx_zogy_refpsf_fill): the row DFTs of the
+// reference's stamps into the context's work array, then pass 1 of k_psf_cols on them.  Not timed, as fill_ref_rows.
+template <class P>
+static int fill_ref_psf(bbx_ctx* ctx, const float2* d_tw, int nsub, const float* d_psf_r, int S, float2* out, hipStream_t s) {
+    int rc = lds_attrs<P>(ctx); if (rc) return rc;
+    float2* Q = (float2*)bbx_ws(ctx, WS_CAND, (size_t)nsub * S * P::HP * sizeof(float2), &rc); if (rc) return rc;
+    hipLaunchKernelGGL(k_psf_rowdft<P>, dim3((P::H + 255) / 256, (S + ZQ_J - 1) / ZQ_J, nsub), dim3(256), 0, s, d_psf_r, d_psf_r, S, d_tw, Q, nsub);
+    hipLaunchKernelGGL(k_refpsf_cols<P>, grid8(P::G, nsub), dim3(P::THREADS), lds_bytes<P>(), s, Q, S, d_tw, out, nsub);
+    BBX_LAUNCH_CHECK();
+    return BBX_OK;
+}
 template <class P>
 static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, int nx, int size, int border, const float* d_new, const float* d_ref,
                const float* d_sig_new, const float* d_sig_ref, const bbx_spl* spn, const bbx_spl* spr, const float* d_psf_n, const float* d_psf_r, int S, const float* h_scal,
@@ -1542,6 +1696,7 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
     const bool vec4 = rows_vec4<P>(nx, size, border, d_new, d_ref, d_sig_new, d_sig_ref);
     const float2* ref_rows = ctx->zrows;                    // prepared reference rows (checked by zogy_frame_entry)
     if (ref_rows && !vec4) return BBX_ERR_ARG;
+    const float2* ref_psf = ctx->zpsf;                      // prepared reference PSF spectra (checked by zogy_frame_entry: only with rows)
     // chunks of the final kernel (chunk_plan; cached with the twiddle table)
     const int yb0 = border / P::NL, yb1 = (border + size - 1) / P::NL, nyb = yb1 - yb0 + 1;
     const int nslots = 2 * (ctx->num_cus > 0 ? ctx->num_cus : 256);
@@ -1551,11 +1706,13 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
     const size_t unit = (size_t)nsub * P::UNIT, hunit = (size_t)nsub * nch * P::HP;
     // 4 T + 4 U arrays + the PSF spectra (Pn^, Pr^) as float4 (two arrays) + 2 row-transformed k^2 arrays + 2 halo arrays +
     // the row DFTs of the stamps + scalars + partial sums
-    constexpr int NARR = 12;
-    const size_t qunit = 2 * (size_t)nsub * S * P::HP;
+    // (prepared reference PSF: Pn^ alone as float2, one array -- or, where k_img_cols forms it, the arrays of the small grid
+    // in its place; row DFTs of the new stamps only)
+    const int NARR = ref_psf ? 11 : 12;
+    const size_t qunit = (ref_psf ? 1 : 2) * (size_t)nsub * S * P::HP;
     const size_t bytes = (NARR * unit + 2 * hunit + qunit) * sizeof(float2) + (size_t)nsub * sizeof(zscal) + 5 * (size_t)nsub * P::G * sizeof(double) + (size_t)nsub * sizeof(z3::sub_scal) + 4 * (size_t)nsub * sizeof(float) + 4096;
     char* ws = (char*)bbx_ws(ctx, WS_CAND, bytes, &rc); if (rc) return rc;
-    float2* arr[NARR]; for (int i = 0; i < NARR; i++) arr[i] = (float2*)ws + (size_t)i * unit;
+    float2* arr[12]; for (int i = 0; i < 12; i++) arr[i] = (float2*)ws + (size_t)i * unit;
     float2 *HSn = (float2*)ws + NARR * unit, *HSr = HSn + hunit, *Qdft = HSr + hunit;
     char* p = ws + (NARR * unit + 2 * hunit + qunit) * sizeof(float2);
     zscal* d_sc = (zscal*)p; p += (size_t)nsub * sizeof(zscal);
@@ -1564,8 +1721,8 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
     sub_scal* sub_sc = (sub_scal*)p; p += (size_t)nsub * sizeof(sub_scal);
     float* kchk = (float*)p;                                 // small-grid path: [nsub][2][2] energies of the window check
     float2 *T0 = arr[0], *T1 = arr[1], *T2 = arr[2], *T3 = arr[3], *U0 = arr[4], *U1 = arr[5], *U2 = arr[6], *U3 = arr[7];
-    float4* cP = (float4*)arr[8];                            // arr[8], arr[9]
-    float2 *cK2n = arr[10], *cK2r = arr[11];
+    float4* cP = (float4*)arr[8];                            // arr[8], arr[9] (prepared reference PSF: arr[8])
+    float2 *cK2n = arr[NARR - 2], *cK2r = arr[NARR - 1];
     BBX_HIP(hipMemcpyAsync(d_sc, h_scal, (size_t)nsub * sizeof(zscal), hipMemcpyHostToDevice, s));      // pageable source: staged before the call returns
     const size_t lds = lds_bytes<P>(), lds_fin = lds_fin_bytes<P>();
     rc = lds_attrs<P>(ctx); if (rc) return rc;
@@ -1583,19 +1740,22 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
     }
     const bool win = 2 * wh < P::L;
     const int wb = win ? wh / P::NL : 0, nyb_psf = win ? 2 * wb : P::LB;
-    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_DFT, k_psf_rowdft<P>, dim3((P::H + 255) / 256, (S + ZQ_J - 1) / ZQ_J, 2 * nsub), dim3(256), 0, s, d_psf_n, d_psf_r, S, tw, Qdft, nsub);
+    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_DFT, k_psf_rowdft<P>, dim3((P::H + 255) / 256, (S + ZQ_J - 1) / ZQ_J, (ref_psf ? 1 : 2) * nsub), dim3(256), 0, s, d_psf_n, d_psf_r, S, tw, Qdft, nsub);
     float2 *TK2r = cK2r, *TK2n = cK2n;                      // row-transformed (kr^2)^, (kn^2)^: T layout, column pass inside k_var_cols
     // Small grid: inside the window k_n, k_r are given by every F-th frequency of their spectra, so their way back to real
     // space runs at side M = L / F (1 / F^2 of the work); taken where the side has a plan and the window leaves a guard band
     // of a row block or more below M / 2 (L = 1400: F = 5, M = 280).  BBX_OPT_ZOGY_KSMALL_OFF: the full grid, as the sides without.
     bool ks = false;
     if constexpr (small_of<P>::ok) ks = win && !ctx->zogy_ksmall_off && small_of<P>::type::L / 2 - wh >= P::NL;
-    if constexpr (small_of<P>::ok) if (ks) {
+    // Prepared reference PSF on the small-grid path: no k_psf_cols at all.  k_img_cols forms Pn^ itself and emits the sums and
+    // the small-grid samples; k_ks_cols and k_ks_rows follow it (below), their arrays in the space the PSF spectra leave.
+    const bool fuse = ks && ref_psf != nullptr;
+    if constexpr (small_of<P>::ok) if (ks && !fuse) {
         typedef typename small_of<P>::type PK;
         constexpr int M = PK::L, HM = PK::H, HMP = (HM + 7) / 8 * 8, NG = (HM + PK::NL - 1) / PK::NL;
         static_assert(2 * (size_t)HM * M <= P::UNIT && 2 * (size_t)M * HMP <= P::UNIT && P::L % PK::L == 0 && M % P::NL == 0, "small-grid arrays fit a unit");
         float2 *Ksm = U1, *Us = U2;                          // free until k_img_cols writes the U arrays
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_psf_cols<P, true>), gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, (float2*)kchk, Ksm, fs_partial, nsub, wh);
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_psf_cols<P, true>), gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, nullptr, (float2*)kchk, Ksm, fs_partial, nsub, wh);
         bbx_prof_start(ctx, BBX_PROF_Z_PSF_ROWS, s);          // the two launches as one entry: the slots count frames
         hipLaunchKernelGGL((k_ks_cols<P, PK>), dim3((unsigned)(NG * 2 * nsub)), dim3(Z3_KS_THREADS), lds_ks_cols_bytes<PK>(), s, Ksm, tw, Us, kchk, nsub, wh);
         hipLaunchKernelGGL((k_ks_rows<P, PK>), grid8(nyb_psf, nsub), dim3(P::LIGHT_THREADS), (lds_ks_rows_bytes<P, PK>()), s, Us,
@@ -1603,7 +1763,10 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
         bbx_prof_stop(ctx, s);
     }
     if (!ks) {
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_psf_cols<P, false>), gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, U0, U1, fs_partial, nsub, wh);
+        if (ref_psf)
+            BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_psf_cols<P, false, true>), gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, ref_psf, U0, U1, fs_partial, nsub, wh);
+        else
+            BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_psf_cols<P, false>), gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, nullptr, U0, U1, fs_partial, nsub, wh);
         BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_ROWS, k_psf_rows<P>, grid8(nyb_psf, nsub), dim3(P::LIGHT_THREADS), lds, s, U1, U0, inv_n2, tw, TK2r, TK2n, nsub,
                          nyb_psf, wb, d_sc, fs_partial, sub_sc, ctx->d_err);
     }
@@ -1633,11 +1796,28 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
         BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, k_img_rows<P>, grow, dim3(P::LIGHT_THREADS), lds, s, fa, tw, T2, T3, nsub);
     }
     // D, Sn, Sr; V_S.  Prepared reference: R^, Vr^ come column-transformed (C layout)
+    const psf_fuse_args nofuse{nullptr, 0, nullptr, nullptr, nullptr};
     if (ref_rows) {
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, true>), gcol, blk, lds, s, T0, TR, cP, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch);
+        if (fuse) {
+            if constexpr (small_of<P>::ok) {
+                typedef typename small_of<P>::type PK;
+                constexpr int M = PK::L, HM = PK::H, HMP = (HM + 7) / 8 * 8, NG = (HM + PK::NL - 1) / PK::NL;
+                static_assert(2 * (size_t)HM * M + 2 * (size_t)M * HMP <= P::UNIT, "small-grid arrays fit a unit");
+                float2 *Ksm = arr[8], *Us = Ksm + (size_t)nsub * 2 * HM * M;
+                const psf_fuse_args pf{Qdft, S, kchk, Ksm, fs_partial};
+                BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, true, 2>), gcol, blk, lds, s, T0, TR, nullptr, ref_psf, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch, pf);
+                // the PSF side's column pass and its row pass, one slot each (the slots count the launches of a frame)
+                BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_ks_cols<P, PK>), dim3((unsigned)(NG * 2 * nsub)), dim3(Z3_KS_THREADS), lds_ks_cols_bytes<PK>(), s, Ksm, tw, Us, kchk, nsub, wh);
+                BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_ROWS, (k_ks_rows<P, PK>), grid8(nyb_psf, nsub), dim3(P::LIGHT_THREADS), (lds_ks_rows_bytes<P, PK>()), s, Us,
+                                 1.0f / ((float)M * (float)M), tw, TK2r, TK2n, nsub, nyb_psf, wb, d_sc, fs_partial, sub_sc, ctx->d_err, kchk);
+            }
+        } else if (ref_psf)
+            BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, true, 1>), gcol, blk, lds, s, T0, TR, cP, ref_psf, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch, nofuse);
+        else
+            BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, true>), gcol, blk, lds, s, T0, TR, cP, nullptr, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch, nofuse);
         BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_VAR_COLS, (k_var_cols<P, true>), gcol, dim3(P::VAR_THREADS), lds, s, T2, TVr, TK2n, TK2r, tw, U3, sub_sc, nsub, wh, &ctx->d_counters[CNT_TICKET], kchk_c, ctx->d_err);
     } else {
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, false>), gcol, blk, lds, s, T0, TR, cP, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch);
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, false>), gcol, blk, lds, s, T0, TR, cP, nullptr, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch, nofuse);
         BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_VAR_COLS, (k_var_cols<P, false>), gcol, dim3(P::VAR_THREADS), lds, s, T2, TVr, TK2n, TK2r, tw, U3, sub_sc, nsub, wh, &ctx->d_counters[CNT_TICKET], kchk_c, ctx->d_err);
     }
     out_args oa; oa.D = d_D; oa.S = d_S; oa.Scorr = d_Scorr; oa.Fpsf = d_Fpsf; oa.Fpsferr = d_Fpsferr;
@@ -1691,6 +1871,29 @@ static int bbx_zogy3_fill_ref_rows(bbx_ctx* ctx, const float2* d_tw, int L, int 
         case 64: Z3_FILL(8, 8);
     }
     return BBX_ERR_ARG;
+}
+static int bbx_zogy3_fill_ref_psf(bbx_ctx* ctx, const float2* d_tw, int L, int nsub, const float* d_psf_r, int S, float2* out, hipStream_t s) {
+#define Z3_FILLP(...) return z3::fill_ref_psf<z3::Plan<__VA_ARGS__>>(ctx, d_tw, nsub, d_psf_r, S, out, s)
+    switch (L) {
+        case 1400: Z3_FILLP(Z3_PLAN1400);
+        case 140: Z3_FILLP(5, 7, 4);
+        case 128: Z3_FILLP(8, 16);
+        case 100: Z3_FILLP(5, 5, 4);
+        case 64: Z3_FILLP(8, 8);
+    }
+    return BBX_ERR_ARG;
+}
+// entries of one sub-image's spectrum in C layout: G column groups of NL lines of L
+static size_t bbx_zogy3_cunit(int L) {
+#define Z3_CUNIT(...) return (size_t)z3::Plan<__VA_ARGS__>::G * z3::Plan<__VA_ARGS__>::NL * z3::Plan<__VA_ARGS__>::L
+    switch (L) {
+        case 1400: Z3_CUNIT(Z3_PLAN1400);
+        case 140: Z3_CUNIT(5, 7, 4);
+        case 128: Z3_CUNIT(8, 16);
+        case 100: Z3_CUNIT(5, 5, 4);
+        case 64: Z3_CUNIT(8, 8);
+    }
+    return 0;
 }
 static size_t bbx_zogy3_unit(int L) {
 #define Z3_UNIT(...) return z3::Plan<__VA_ARGS__>::UNIT
@@ -1778,6 +1981,10 @@ static int zogy_frame_entry(bbx_ctx* ctx, int ny, int nx, int size, int border, 
     if (ctx->zrows && (d_ref != ctx->zrows_ref || (spl ? (const void*)sig_ref->d_coef : (const void*)d_sig_ref) != ctx->zrows_sig || ny != ctx->zrows_geom[0] ||
                        nx != ctx->zrows_geom[1] || size != ctx->zrows_geom[2] || border != ctx->zrows_geom[3]))
         return BBX_ERR_ARG;
+    // prepared reference PSF spectra (bbx_zogy_refpsf): only with prepared rows, for the very stamps, S and geometry they were made of
+    if (ctx->zpsf && (!ctx->zrows || d_psf_r != ctx->zpsf_stamps || S != ctx->zpsf_S || ny != ctx->zpsf_geom[0] || nx != ctx->zpsf_geom[1] ||
+                      size != ctx->zpsf_geom[2] || border != ctx->zpsf_geom[3]))
+        return BBX_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     zogy_tw_state* st;
     int rc = zogy_tw(ctx, L, &st); if (rc) return rc;
@@ -1844,6 +2051,30 @@ extern "C" int bbx_zogy_refrows(bbx_ctx* ctx, const void* d_rows, int ny, int nx
     if (!d_ref || !ref_sigma || !refrows_geom_ok(ny, nx, size, border) || (uintptr_t)d_rows % 16) return BBX_ERR_ARG;
     ctx->zrows = (const float2*)d_rows; ctx->zrows_ref = d_ref; ctx->zrows_sig = ref_sigma;
     ctx->zrows_geom[0] = ny; ctx->zrows_geom[1] = nx; ctx->zrows_geom[2] = size; ctx->zrows_geom[3] = border;
+    return BBX_OK;
+}
+
+// ---- prepared reference PSF spectra ------------------------------------------------------------------------------
+extern "C" size_t bbx_zogy_refpsf_bytes(int ny, int nx, int size, int border) {
+    if (!refrows_geom_ok(ny, nx, size, border)) return 0;
+    return (size_t)(ny / size) * (nx / size) * bbx_zogy3_cunit(size + 2 * border) * sizeof(float2);
+}
+
+extern "C" int bbx_zogy_refpsf_fill(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_psf_r, int S, void* d_out, void* stream) {
+    if (!ctx || !d_psf_r || !d_out || (uintptr_t)d_out % 16 || !refrows_geom_ok(ny, nx, size, border) || S < 1 || S > size + 2 * border) return BBX_ERR_ARG;
+    const int L = size + 2 * border;
+    zogy_tw_state* st;
+    int rc = zogy_tw(ctx, L, &st); if (rc) return rc;
+    return bbx_zogy3_fill_ref_psf(ctx, st->d_tw, L, (ny / size) * (nx / size), d_psf_r, S, (float2*)d_out, (hipStream_t)stream);
+}
+
+extern "C" int bbx_zogy_refpsf(bbx_ctx* ctx, const void* d_spec, int ny, int nx, int size, int border, const float* d_psf_r, int S) {
+    if (!ctx) return BBX_ERR_ARG;
+    ctx->zpsf = nullptr; ctx->zpsf_stamps = nullptr; ctx->zpsf_S = 0;
+    if (!d_spec) return BBX_OK;
+    if (!d_psf_r || !refrows_geom_ok(ny, nx, size, border) || S < 1 || S > size + 2 * border || (uintptr_t)d_spec % 16) return BBX_ERR_ARG;
+    ctx->zpsf = (const float2*)d_spec; ctx->zpsf_stamps = d_psf_r; ctx->zpsf_S = S;
+    ctx->zpsf_geom[0] = ny; ctx->zpsf_geom[1] = nx; ctx->zpsf_geom[2] = size; ctx->zpsf_geom[3] = border;
     return BBX_OK;
 }
 

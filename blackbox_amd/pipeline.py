@@ -330,6 +330,7 @@ class FramePipeline:
         # one lane at a time inside bbx_zogy_frame (BBX_ZOGY_GATE=0 switches the gate off)
         self.ref_bkg_std = None
         self.ref_rows = None                                         # zogy.RefRows of the run's reference (made with ref_bkg_std)
+        self.ref_psf = None                                          # zogy.RefPsf of the run's reference PSF (made with them; BBX_REF_PSF=0: none)
         self.ref_catalog = None                                      # zogy.RefCatalog of the run's reference (star match; made with them)
         self._ref_lock = threading.Lock()                            # one lane makes the two and hands them over
         self.zogy_gate = None
@@ -456,7 +457,7 @@ class FramePipeline:
                 lib.bbx_event_destroy(sl[k])
         self.slots = []
         self.lane_out = None
-        self.ref_rows = self.ref_bkg_std = self.ref_catalog = None
+        self.ref_rows = self.ref_psf = self.ref_bkg_std = self.ref_catalog = None
         self.arena.close()
         for c in self.own_ctx:
             c.close()
@@ -672,7 +673,7 @@ class FramePipeline:
             from . import zogy as G
             try:
                 sub = G.optimal_subtraction(ctx, data, new_mask=mask, zogy_gate=self.zogy_gate, ref_bkg_std=self.ref_bkg_std,
-                                            ref_rows=self.ref_rows, ref_catalog=self.ref_catalog, **self.subtract)
+                                            ref_rows=self.ref_rows, ref_psf=self.ref_psf, ref_catalog=self.ref_catalog, **self.subtract)
                 if (self.ref_bkg_std is None and self.subtract.get('ref_is_bkgsub') and self.subtract.get('ref_bkg_std_mini') is not None
                         and self.subtract.get('ref_grid') is None and 'bkg_std_ref' in sub):
                     with self._ref_lock:
@@ -681,14 +682,20 @@ class FramePipeline:
                             # comes first (its stream has finished with it before any other lane can pick it up: see below);
                             # and so are the row transforms of the reference and of its variance image inside bbx_zogy_frame:
                             # one buffer (1 GB at full size) for all lanes, where the geometry has the aligned row path
-                            rows = None
+                            # and the spectra of the reference's PSF (--psf_ref is loaded once per run): one more buffer (505 MB
+                            # at full size) where there are rows; BBX_REF_PSF=0 leaves it out (A/B runs of one build)
+                            rows = rpsf = None
                             zsize, zborder = sub['header_new']['Z-SIZE'][0], sub['header_new']['Z-BSIZE'][0]
                             if G.frame_path_supported(zsize + 2 * zborder) and G.RefRows.supported(data.shape, zsize, zborder):
                                 rows = G.RefRows(ctx, sub['ref_bkgsub'], sub['bkg_std_ref'], zsize, zborder)
+                                if (os.environ.get('BBX_REF_PSF', '1') != '0' and self.subtract.get('psf_ref') is not None
+                                        and G.RefPsf.supported(data.shape, zsize, zborder)):
+                                    rpsf = G.RefPsf(ctx, self.subtract['psf_ref'], data.shape, zsize, zborder)
                             check(lib.bbx_wait(ctx.h, ctx.sp), 'bbx_wait', ctx.h)
                             # (the star match's catalogue of the reference, where the switch is on: the one this call made of
                             # the same two tensors)
                             self.ref_catalog = sub.get('ref_catalog')
+                            self.ref_psf = rpsf
                             self.ref_rows, self.ref_bkg_std = rows, sub['bkg_std_ref']
                 for k in ('thumbnails', 'thumbnail_png8'):
                     # the thumbnails of the transient candidates leave the GPU on this lane, behind the kernels that made them

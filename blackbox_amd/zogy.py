@@ -293,6 +293,39 @@ class RefRows:
             and (ref.shape[0], ref.shape[1], int(size), int(border)) == self.geom
 
 
+class RefPsf:
+    """The reference PSF's half of bbx_zogy_frame's PSF spectra (include/bbx.h, bbx_zogy_refpsf): Pr^ of every sub-image,
+    made once for a reference PSF that stays the same over many frames (--psf_ref is loaded once per run; the new frame's
+    PSF is per-frame work and stays it).  Holds the buffer and the contiguous stamp tensor [nsub, S, S] it was made of:
+    the library knows the stamps by their pointer, so frame calls pass this very tensor (stamps) as the reference's PSFs.
+    psf_ref is the caller's object (a stamp tensor or a PSFEx model dict) that matches() recognises.  Made on ctx's
+    current stream: a caller that hands the object to other streams or contexts waits for that stream first."""
+    fills = 0                                    # reference PSF spectra made so far (tests: once per run, not per frame)
+
+    def __init__(self, ctx, psf_ref, shape, size, border):
+        ny, nx = int(shape[0]), int(shape[1])
+        nbytes = int(lib.bbx_zogy_refpsf_bytes(ny, nx, int(size), int(border)))
+        if not nbytes:
+            raise ValueError('no prepared reference PSF spectra for this geometry')
+        self.psf_ref, self.geom = psf_ref, (ny, nx, int(size), int(border))
+        self.stamps = subimage_psfs(ctx, psf_ref, ny // int(size), nx // int(size), int(size)).contiguous()
+        if self.stamps.dtype != torch.float32:
+            raise ValueError('float32 PSF stamps expected')
+        self.S = int(self.stamps.shape[1])
+        self.buf = torch.empty(nbytes // 4, dtype=torch.float32, device=ctx.device)
+        check(lib.bbx_zogy_refpsf_fill(ctx.h, ny, nx, int(size), int(border), _p(self.stamps), self.S, _p(self.buf), ctx.stream()),
+              'bbx_zogy_refpsf_fill', ctx.h)
+        RefPsf.fills += 1
+
+    @staticmethod
+    def supported(shape, size, border):
+        return bool(lib.bbx_zogy_refpsf_bytes(int(shape[0]), int(shape[1]), int(size), int(border)))
+
+    def matches(self, psf_ref, shape, size, border):
+        """made of this very psf_ref object, for this geometry?"""
+        return psf_ref is self.psf_ref and (int(shape[0]), int(shape[1]), int(size), int(border)) == self.geom
+
+
 # ---- flux ratio and dx, dy from matched stars ---------------------------------------------
 # buildref.py:2782-3014 (get_fratio, "simplified version of zogy.get_fratio_dxdy") shows the computation; [EXT]
 # get_fratio_dxdy, get_matches, get_mean_fratio are not in the reference tree (conventions: include/bbx.h).
@@ -771,12 +804,21 @@ def build_psf(ctx, data_bkgsub, sigma, mask, size, nsy, nsx, cat_nsigma=5.0, sig
     return dict(model=model, header=psf_header(True, nfit, chi2_mean, fwhm, V, degs[k]), stars=stars)
 
 
-def run_zogy_frame(ctx, new, ref, sig_new, sig_ref, psf_n, psf_r, scal, size, border, want_S=False, outs=None, ref_rows=None):
+def run_zogy_frame(ctx, new, ref, sig_new, sig_ref, psf_n, psf_r, scal, size, border, want_S=False, outs=None, ref_rows=None, ref_psf=None):
     """ZOGY of whole frames (bbx_zogy_frame): background-subtracted frames + sigma images + PSF
     stamps [nsub, S, S] -> D, S (or None), Scorr, Fpsf, Fpsferr full frames.  sig_new, sig_ref: frames, or both
     MiniImage (bbx_zogy_frame_mini: the sigma maps are read off their mini images, no frames exist).
     ref_rows: a RefRows made of (ref, sig_ref): the call skips the reference's row and column pass (the library refuses rows of
-    another reference, sigma map or geometry)"""
+    another reference, sigma map or geometry)
+    ref_psf: a RefPsf whose stamps tensor is psf_r: the call transforms the new stamps only (needs ref_rows; the library refuses
+    spectra of another stamp tensor, stamp size or geometry)"""
+    if ref_psf is not None:
+        ny, nx = new.shape
+        check(lib.bbx_zogy_refpsf(ctx.h, _p(ref_psf.buf), ny, nx, int(size), int(border), _p(ref_psf.stamps), ref_psf.S), 'bbx_zogy_refpsf', ctx.h)
+        try:
+            return run_zogy_frame(ctx, new, ref, sig_new, sig_ref, psf_n, psf_r, scal, size, border, want_S=want_S, outs=outs, ref_rows=ref_rows)
+        finally:
+            lib.bbx_zogy_refpsf(ctx.h, None, 0, 0, 0, 0, None, 0)         # the setting never outlives the call it was made for
     if ref_rows is not None:
         ny, nx = new.shape
         check(lib.bbx_zogy_refrows(ctx.h, _p(ref_rows.buf), ny, nx, int(size), int(border), _p(ref), C.c_void_p(ref_rows.sigma_id())),
@@ -1064,7 +1106,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          ref_is_bkgsub=False, ref_bkg_std_mini=None, ref_grid=None, ref_grid_step=32,
                          cat_extract=False, cat_nsigma=5.0, trans_extract=True, frame_stats=True, max_sources=200000,
                          zogy_gate=None, ref_bkg_std=None, sigma_frames=False, thumbnails=False, thumbnail_size=None,
-                         thumbnail_pngs=False, ref_rows=None, match=False, ref_catalog=None, match_dist=None, match_nmin=None,
+                         thumbnail_pngs=False, ref_rows=None, ref_psf=None, match=False, ref_catalog=None, match_dist=None, match_nmin=None,
                          match_snr_min=None, shapes=False, shape_snr_min=None, psf_build=False, psf_size=None, psf_poldeg=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
@@ -1082,6 +1124,9 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
       ref_rows      : a RefRows made of the reference and of ref_bkg_std by the caller that keeps both for many frames: the
                       subtraction skips the reference's row transforms (used only where it was made of this call's very
                       reference, sigma map and geometry; same result bit for bit)
+      ref_psf       : a RefPsf made of this call's very psf_ref object by the caller that keeps it for many frames: its stamp
+                      tensor serves as the reference's PSFs and, where ref_rows is used, the subtraction skips the
+                      reference PSF's transforms (same result bit for bit)
       sigma_frames  : True: the two sigma images are made as full frames (rounds 1-4; bbx_zogy_frame) instead of
                       being read off their mini images inside the kernels (bbx_zogy_frame_mini)
       ref_grid      : projection lattice (coadd.projection_grid) when the reference lives on
@@ -1210,7 +1255,9 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         elif (rny, rnx) != (ny, nx):
             raise ValueError('reference frame of another shape needs ref_grid')
         # co-added reference: no channel structure in its noise -> interpolation across the frame
-        sub_pr = subimage_psfs(ctx, psf_ref, nsy, nsx, size)
+        # (a RefPsf of this psf_ref: its own stamp tensor, the one its spectra were made of -- the library knows them by pointer)
+        rpsf = ref_psf if ref_psf is not None and ref_psf.matches(psf_ref, (ny, nx), size, border) else None
+        sub_pr = rpsf.stamps if rpsf is not None else subimage_psfs(ctx, psf_ref, nsy, nsx, size)
         frame_path = frame_path_supported(L) and sub_pn.shape[1] == sub_pr.shape[1]
         if ref_bkg_std is not None and ref_grid is None and tuple(ref_bkg_std.shape) == (ny, nx) and isinstance(ref_bkg_std, MiniImage) == use_mini:
             rbstd = ref_bkg_std
@@ -1350,12 +1397,14 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         sub_pn, sub_pr = sub_pn.contiguous(), sub_pr.contiguous()
         nsig_cand = float(settings.transient_nsigma if nsigma is None else nsigma)
         rows = ref_rows if ref_rows is not None and ref_rows.matches(rwork, rbstd, size, border) else None
+        # prepared reference PSF spectra: with prepared rows only, and only where sub_pr is the tensor they were made of
+        rpsf = ref_psf if rows is not None and ref_psf is not None and sub_pr is ref_psf.stamps else None
 
         def zogy_frame_call():
             # the kernel that writes Scorr lists the pixels above the transient threshold for the peak search below
             check(lib.bbx_zogy_candidates(ctx.h, nsig_cand), 'bbx_zogy_candidates', ctx.h)
             with (zogy_gate or _NoGate()):
-                return run_zogy_frame(ctx, work, rwork, bstd, rbstd, sub_pn, sub_pr, scal, size, border, outs=outs, ref_rows=rows)
+                return run_zogy_frame(ctx, work, rwork, bstd, rbstd, sub_pn, sub_pr, scal, size, border, outs=outs, ref_rows=rows, ref_psf=rpsf)
         D, _, Scorr, Fpsf, Fpsferr = zogy_frame_call()
         res['D'], res['Scorr'], res['Fpsf'], res['Fpsferr'] = D, Scorr, Fpsf, Fpsferr
     else:

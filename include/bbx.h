@@ -177,8 +177,9 @@ int  bbx_copy_async(void *dst, const void *src, size_t nbytes, int kind, void *s
 #define BBX_PROF_MASK_FINISH 5 /* mask_init tail + fill  (1 group / frame)   */
 #define BBX_PROF_ZOGY 6        /* bbx_zogy_subimages, or (register-DFT core) the kernels of bbx_zogy_frame before its last one */
 #define BBX_PROF_ZOGY_FINAL 7  /* k_final_rows of bbx_zogy_frame (1 launch / frame) */
-#define BBX_PROF_Z_PSF_COLS 8  /* the other kernels of bbx_zogy_frame (LDS-pass core), one slot each: k_psf_cols, */
-#define BBX_PROF_Z_PSF_ROWS 9  /*   k_psf_rows, */
+#define BBX_PROF_Z_PSF_COLS 8  /* the other kernels of bbx_zogy_frame (LDS-pass core), one slot each: k_psf_cols (with a prepared
+                                  reference PSF on the small-grid path: k_ks_cols, the PSF side's column pass), */
+#define BBX_PROF_Z_PSF_ROWS 9  /*   k_psf_rows (small grid: k_ks_cols + k_ks_rows; prepared reference PSF: k_ks_rows alone), */
 #define BBX_PROF_Z_IMG_ROWS 10 /*   k_img_rows_one (2 launches / frame; 1 with prepared reference rows), */
 #define BBX_PROF_Z_IMG_COLS 11 /*   k_img_cols, */
 #define BBX_PROF_Z_VAR_COLS 12 /*   k_var_cols, */
@@ -628,6 +629,27 @@ int bbx_zogy_refrows_fill_mini(bbx_ctx *ctx, int ny, int nx, int size, int borde
                                const bbx_spline_image *sig_ref, void *d_rows, void *stream);
 int bbx_zogy_refrows(bbx_ctx *ctx, const void *d_rows, int ny, int nx, int size, int border,
                      const float *d_ref, const void *ref_sigma);
+
+/* Prepared reference PSF.  The spectrum Pr^ of the reference's PSF stamps depends on the stamps d_psf_r [nsub][S][S] and
+ * the geometry alone; a caller whose reference PSF stays the same over many frames makes it once, into a buffer of its
+ * own, beside the prepared rows.  (The new frame's PSF changes from frame to frame and stays per-frame work.)
+ *   bbx_zogy_refpsf_bytes : size of the buffer: nsub half spectra of G column groups x NL lines x L points of 8 bytes
+ *                           (505 MB for 64 sub-images of 1400^2); 0 wherever bbx_zogy_refrows_bytes is 0
+ *   bbx_zogy_refpsf_fill  : the row DFTs of the stamps (into the context's work array) and their pruned column transform
+ *                           (into d_out, 16-byte aligned) on the stream -- the transform an unprepared frame call runs on
+ *                           the same data, so the results with and without are equal bit for bit
+ *   bbx_zogy_refpsf       : sticky, per context: the following bbx_zogy_frame[_mini] calls transform the new stamps only
+ *                           and read Pr^ from d_spec.  Identity is by pointer, as for the reference frame: the library keeps
+ *                           no copy and cannot see whether the stamps' values changed.  A frame call with another d_psf_r
+ *                           pointer, S, ny, nx, size or border returns BBX_ERR_ARG, and so does one while no prepared rows
+ *                           are set (bbx_zogy_refrows); nothing is written then.  d_spec = NULL clears the setting (the
+ *                           other arguments are then ignored).  One buffer may serve several contexts once its fill has
+ *                           completed. */
+size_t bbx_zogy_refpsf_bytes(int ny, int nx, int size, int border);
+int bbx_zogy_refpsf_fill(bbx_ctx *ctx, int ny, int nx, int size, int border, const float *d_psf_r, int S,
+                         void *d_out, void *stream);
+int bbx_zogy_refpsf(bbx_ctx *ctx, const void *d_spec, int ny, int nx, int size, int border,
+                    const float *d_psf_r, int S);
 
 /* ---- a17: PSFEx model evaluation [EXT: zogy.get_psf / psfex poly] ----------------------
  * stamp[s][p] = sum_k terms[s][k] * basis[k][p]: terms [nsrc][ncoef] f32 = the polynomial
