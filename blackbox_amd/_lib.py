@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BBX_LIB_PATH') or os.path.join(_HERE, 'libbbx_hip.so')
 
 BBX_RAW_U16, BBX_RAW_F32 = 0, 1
+BBX_OPT_ZOGY_KWIN_OFF = 4                # bbx_set_option (include/bbx.h): the matched-filter kernels of bbx_zogy_frame without their row window
 BBX_OPT_ZOGY_KSMALL_OFF = 9              # bbx_set_option (include/bbx.h): the matched-filter kernels of bbx_zogy_frame on the full grid
 
 

@@ -1023,10 +1023,9 @@ int bbx_mini_fill_filter(bbx_ctx* ctx, int nby, int nbx, float* d_mini, void* st
     float* tmp = (float*)bbx_ws(ctx, WS_MISC, (size_t)nby * nbx * 4 + 256, &rc); if (rc) return rc;
     const size_t n = (size_t)nby * nbx;
     if (n <= MINI_LDS_MAX) {
-        static bool attr_set = false;                        // (idempotent: a race only sets it twice)
-        if (!attr_set) {
+        if (!ctx->mini_attr_set) {                           // per context: the attribute belongs to the device
             BBX_HIP(hipFuncSetAttribute((const void*)k_mini_fill_filter_lds, hipFuncAttributeMaxDynamicSharedMemorySize, MINI_LDS_MAX * 4));
-            attr_set = true;
+            ctx->mini_attr_set = 1;
         }
         hipLaunchKernelGGL(k_mini_fill_filter_lds, dim3(1), dim3(1024), n * sizeof(float), (hipStream_t)stream, d_mini, nby, nbx);
         BBX_LAUNCH_CHECK();

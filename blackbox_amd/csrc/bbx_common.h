@@ -42,6 +42,10 @@ static inline int bbx_make_dims(const bbx_geom* g, bbx_dims* d) {
 #define BBX_DERR_NOTCONV       2
 #define BBX_DERR_PSF_WINDOW    4    // bbx_zogy_frame: the PSFs' matched-filter kernels do not fit their row window
 
+// prepared reference data of bbx_zogy_frame (bbx_zogy_refrows, bbx_zogy_refpsf): the caller's buffer (NULL: none) and what it was
+// made of -- two inputs by address, the stamp side S (rows: 0) and the geometry (ny, nx, size, border)
+struct bbx_zprep { const float2* buf; const void* id[2]; int S; int geom[4]; };
+
 struct bbx_ctx {
     int device;
     char hip_err[256];
@@ -62,20 +66,16 @@ struct bbx_ctx {
     int    lac_feed;           // BBX_OPT_LAC_LEVEL_FEED (bbx_set_option)
     int    debug_listcap;      // BBX_OPT_DEBUG_LISTCAP: capacity the LA-Cosmic kernels see (0 = the allocated one)
     void*  zogy_state;         // per-context FFT plans / work buffer of bbx_zogy.hip (NULL until first use)
-    void*  zogy2_state;        // twiddle table of bbx_zogy_frame (bbx_zogy3.hip)
+    void*  zogy_frame_state;   // twiddle table and chunk plan of bbx_zogy_frame (bbx_zogy3.hip)
     int    zogy_kwin_off;      // BBX_OPT_ZOGY_KWIN_OFF: full-size transforms of the matched-filter kernels (no row window)
     int    zogy_ksmall_off;    // BBX_OPT_ZOGY_KSMALL_OFF: k_n, k_r through the full grid even where a small grid exists
     int    sat_attr_set;       // dynamic-LDS attribute of k_trail_segment set through this context
+    int    mini_attr_set;      // the same of k_mini_fill_filter_lds
     float  zcand_thr;          // bbx_zogy_candidates: > 0: bbx_zogy_frame lists the pixels with |Scorr| >= thr (WS_ZCAND, CNT_ZCAND)
     const float* zcand_img;    // the Scorr frame the list in WS_ZCAND belongs to (NULL: none); consumed by bbx_find_peaks
     float  zcand_thr_used; size_t zcand_npix;
-    const float2* zrows;       // bbx_zogy_refrows: the reference's prepared row transforms (caller's buffer; NULL: none) and what they
-    const void* zrows_ref;     // were made of: the reference frame, its sigma frame or spline coefficients, (ny, nx, size, border)
-    const void* zrows_sig;
-    int    zrows_geom[4];
-    const float2* zpsf;        // bbx_zogy_refpsf: the reference PSF's prepared spectra (caller's buffer; NULL: none) and what they were
-    const float* zpsf_stamps;  // made of: the reference's stamps [nsub][S][S], S, (ny, nx, size, border)
-    int    zpsf_S, zpsf_geom[4];
+    bbx_zprep zrows;           // bbx_zogy_refrows: the reference's row transforms; id: the reference frame, its sigma frame or spline coefficients
+    bbx_zprep zpsf;            // bbx_zogy_refpsf: the reference PSF's spectra; id: the reference's stamps [nsub][S][S], NULL
     const float* bcand_med;    // bbx_zoom_candidates: device scalar m; the next bbx_spline_zoom_sub lists |out| >= (float)(m * bcand_nsig) (WS_BCAND, CNT_BCAND)
     double bcand_nsig;
     const float* bcand_img;    // the frame the list in WS_BCAND belongs to (consumed by bbx_find_peaks), its median scalar and factor
@@ -146,9 +146,8 @@ static inline size_t bbx_cand_cap(size_t npix) {
     const size_t c = npix / 16 + 1024, f = npix < 65536 ? npix : 65536;
     return c > f ? c : f;
 }
-void bbx_zogy2_release(bbx_ctx* ctx);
+void bbx_zogy_frame_release(bbx_ctx* ctx);   // bbx_zogy3.hip: frees ctx->zogy_frame_state (called by bbx_ctx_destroy)
 void bbx_fpack_release(bbx_ctx* ctx);     // bbx_fpack.hip: frees the per-stream hint tables (called by bbx_ctx_destroy)
-int bbx_zogy3_supported(int L);
 int bbx_build_flags_fpack(void); int bbx_build_flags_zogy(void); int bbx_build_flags_bkg(void); int bbx_build_flags_sat(void); int bbx_build_flags_canny(void);
 void bbx_zogy_release(bbx_ctx* ctx);      // bbx_zogy.hip: frees ctx->zogy_state (called by bbx_ctx_destroy)
 void* bbx_ws(bbx_ctx* ctx, int slot, size_t bytes, int* rc);

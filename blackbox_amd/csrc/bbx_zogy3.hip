@@ -1564,7 +1564,19 @@ __global__ __launch_bounds__(P::FIN_THREADS, P::FIN_MINW) void k_final_rows(cons
 }
 
 // ---- host side --------------------------------------------------------------------------------
-}  // namespace z3
+// The one list of sub-image sides and their plans: f is called with a value of the side's Plan type, and its result
+// returned; a side without a plan gives [none].
+template <class R, class F> static inline R with_plan(int L, R none, F&& f) {
+    switch (L) {
+        case 1400: return f(Plan<Z3_PLAN1400>{});
+        case 140: return f(Plan<5, 7, 4>{});
+        case 128: return f(Plan<8, 16>{});
+        case 100: return f(Plan<5, 5, 4>{});
+        case 64: return f(Plan<8, 8>{});
+    }
+    return none;
+}
+
 // Chunks of the final kernel: every sub-image's nyb row blocks are cut the same way into runs of decreasing length (guided
 // schedule: a round of nslots / nsub chunks per sub-image takes two thirds of what is left, down to 2 blocks), and the tasks
 // (sub-image, chunk) are listed longest first: the first round fills every workgroup slot, the short ones at the end even
@@ -1598,37 +1610,74 @@ static int chunk_plan(bbx_ctx* ctx, zogy_chunk_plan* pl, int yb0, int nyb, int n
     pl->key[0] = yb0; pl->key[1] = nyb; pl->key[2] = nsub; pl->key[3] = nslots; pl->nch = nch; pl->ntasks = nt;
     return BBX_OK;
 }
-namespace z3 {
+
+// The frame call's work arrays in the WS_CAND slot, every region named once, in this order (a unit: nsub P::UNIT entries):
+//   T[0..3]     row-transformed N, R, Vn, Vr           U[0..3]    k_img_cols' and k_var_cols' results for k_final_rows
+//   cP          the PSF spectra (Pn^, Pr^) as float4: two units; prepared reference PSF: Pn^ alone as float2, one unit
+//   K2n, K2r    row-transformed (kn^2)^, (kr^2)^       HSn, HSr   halo rows of the chunks: [nsub][nch][HP]
+//   Qdft        row DFTs of the stamps (prepared reference PSF: of the new frame's only)
+//   d_sc, (16-byte round-up,) fs_partial, sub_sc, kchk (small grid: [nsub][2][2] energies of the window check)
+// The small grid's arrays Ksm, Us lie in U[1], U[2], free until k_img_cols writes them; where k_img_cols itself emits the
+// samples (fuse), both in the one unit of cP, which then holds nothing else.
+template <class P> struct frame_ws {
+    float2 *T[4], *U[4]; float4* cP; float2 *K2n, *K2r, *HSn, *HSr, *Qdft; zscal* d_sc; double* fs_partial; sub_scal* sub_sc; float* kchk;
+    float2 *Ksm, *Us;
+    size_t bytes;                                           // of the slot, 4096 spare bytes included (the round-up comes out of them)
+    template <class X> static void take(uintptr_t& p, X*& m, size_t nbytes) { m = (X*)p; p += nbytes; }
+    frame_ws() = default;
+    frame_ws(void* base, int nsub, int nch, int S, bool ref_psf, bool fuse) {       // base: the slot, or nullptr to ask for [bytes] alone
+        const size_t unit = (size_t)nsub * P::UNIT * sizeof(float2), hunit = (size_t)nsub * nch * P::HP * sizeof(float2);
+        uintptr_t p = (uintptr_t)base;
+        for (float2*& t : T) take(p, t, unit);
+        for (float2*& u : U) take(p, u, unit);
+        take(p, cP, (ref_psf ? 1 : 2) * unit);
+        take(p, K2n, unit); take(p, K2r, unit);
+        take(p, HSn, hunit); take(p, HSr, hunit);
+        take(p, Qdft, (ref_psf ? 1 : 2) * (size_t)nsub * S * P::HP * sizeof(float2));
+        take(p, d_sc, (size_t)nsub * sizeof(zscal));
+        const size_t pad = (0 - p) & 15; p += pad;
+        take(p, fs_partial, 5 * (size_t)nsub * P::G * sizeof(double));
+        take(p, sub_sc, (size_t)nsub * sizeof(sub_scal));
+        take(p, kchk, 4 * (size_t)nsub * sizeof(float));
+        bytes = p - (uintptr_t)base - pad + 4096;
+        Ksm = U[1]; Us = U[2];
+        if constexpr (small_of<P>::ok) {
+            typedef typename small_of<P>::type PK;
+            constexpr size_t M = PK::L, HM = PK::H, HMP = (HM + 7) / 8 * 8;
+            static_assert(2 * HM * M + 2 * M * HMP <= P::UNIT && P::L % PK::L == 0 && M % P::NL == 0, "small-grid arrays fit a unit, both together");
+            if (fuse) { Ksm = (float2*)cP; Us = (float2*)((uintptr_t)Ksm + (size_t)nsub * 2 * HM * M * sizeof(float2)); }
+        }
+    }
+    // the once-per-run fills of the prepared reference work at the head of the slot, before the frames lay it out in full: the
+    // reference's row pass in T[1], T[3] (the T arrays lead the layout), the row DFTs of its stamps in a Qdft that is all there is
+    static frame_ws ref_rows(void* base, int nsub) { frame_ws w(base, nsub, 0, 0, false, false); w.bytes = (uintptr_t)w.U[0] - (uintptr_t)base; return w; }
+    static frame_ws ref_psf(void* base, int nsub, int S) { frame_ws w{}; w.Qdft = (float2*)base; w.bytes = (size_t)nsub * S * P::HP * sizeof(float2); return w; }
+};
+
 #ifndef Z3_LDS_PAD
 #define Z3_LDS_PAD 0           // experiments: extra dynamic LDS per workgroup (forces one workgroup per CU)
 #endif
 template <class P> constexpr size_t lds_bytes() { return (size_t)P::NL * P::LS * sizeof(float2) + aux_bytes<P>() + Z3_LDS_PAD; }
 template <class P, class PK> constexpr size_t lds_ks_rows_bytes() { return lds_bytes<P>() + (size_t)P::NL * PK::LS * sizeof(float2) + ks_tab_bytes<PK>(); }
 template <class P> constexpr size_t lds_fin_bytes() { return (size_t)(P::NL + 1) * P::LS * sizeof(float2) + aux_bytes<P>() + Z3_LDS_PAD; }
-// dynamic-LDS attribute of the kernels, once per context (= per device and issuing thread) and sub-image side
+// dynamic-LDS attribute of the kernels, once per context (= per device and issuing thread) and sub-image side: every kernel
+// launched with dynamic LDS is named here, in the group of its byte count
+template <class... K> static hipError_t lds_optin(size_t bytes, K... kern) {
+    hipError_t e = hipSuccess;
+    ((e = e != hipSuccess ? e : hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)), ...);
+    return e;
+}
 template <class P> static int lds_attrs(bbx_ctx* ctx) {
     if (ctx->zogy3_attr_L == P::L) return BBX_OK;
-    const int lds = (int)lds_bytes<P>();
-    BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_refpsf_cols<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    BBX_HIP(lds_optin(lds_bytes<P>(), k_psf_cols<P, false>, k_psf_cols<P, false, true>, k_refpsf_cols<P>, k_psf_rows<P>, k_cols_fwd<P>, k_img_rows<P>,
+                      k_img_rows_one<P, false>, k_img_rows_one<P, true>, k_img_cols<P, false>, k_img_cols<P, true>, k_img_cols<P, true, 1>,
+                      k_var_cols<P, false>, k_var_cols<P, true>));
+    BBX_HIP(lds_optin(lds_fin_bytes<P>(), k_final_rows<P>));
     if constexpr (small_of<P>::ok) {
         typedef typename small_of<P>::type PK;
-        BBX_HIP(hipFuncSetAttribute((const void*)k_psf_cols<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        BBX_HIP(hipFuncSetAttribute((const void*)k_ks_rows<P, PK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ks_rows_bytes<P, PK>()));
+        BBX_HIP(lds_optin(lds_bytes<P>(), k_psf_cols<P, true>, k_img_cols<P, true, 2>));
+        BBX_HIP(lds_optin(lds_ks_rows_bytes<P, PK>(), k_ks_rows<P, PK>));
     }
-    BBX_HIP(hipFuncSetAttribute((const void*)k_psf_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_cols_fwd<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows_one<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_img_rows_one<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if constexpr (small_of<P>::ok) BBX_HIP(hipFuncSetAttribute((const void*)k_img_cols<P, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_var_cols<P, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_var_cols<P, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    BBX_HIP(hipFuncSetAttribute((const void*)k_final_rows<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fin_bytes<P>()));
     ctx->zogy3_attr_L = P::L;
     return BBX_OK;
 }
@@ -1657,7 +1706,7 @@ static void rows_one(bbx_ctx* ctx, const float2* tw, int ny, int nx, int size, i
 }
 static inline size_t spl_table_bytes(const bbx_spl& sp, int ny) { return ((size_t)ny * sp.cnx * sizeof(float4) + 255) & ~(size_t)255; }
 // the reference's spectra into a caller's buffer [2][nsub][UNIT] (R^, then Vr^; C layout, a unit holds G NL L <= UNIT entries):
-// the row pass into the context's T1 / T3 work arrays, then the column pass of each (bbx_zogy_refrows_fill).  The two column
+// the row pass into the T[1] / T[3] work arrays, then the column pass of each (bbx_zogy_refrows_fill).  The two column
 // launches are not timed: the profile slots count the launches of a frame.
 template <class P>
 static int fill_ref_rows(bbx_ctx* ctx, const float2* d_tw, int ny, int nx, int size, int border, const float* d_ref, const float* d_sig_ref, const bbx_spl* spr,
@@ -1667,12 +1716,10 @@ static int fill_ref_rows(bbx_ctx* ctx, const float2* d_tw, int ny, int nx, int s
     float4* tab = nullptr;
     if (spr) { tab = (float4*)bbx_ws(ctx, WS_ZSPL, spl_table_bytes(*spr, ny), &rc); if (rc) return rc; }
     const int nsub = (ny / size) * (nx / size);
-    const size_t unit = (size_t)nsub * P::UNIT;
-    float2* ws = (float2*)bbx_ws(ctx, WS_CAND, 4 * unit * sizeof(float2), &rc); if (rc) return rc;
-    float2 *T1 = ws + unit, *T3 = ws + 3 * unit;                   // run()'s work arrays of the reference's row pass
-    rows_one<P>(ctx, d_tw, ny, nx, size, border, d_ref, d_sig_ref, spr, tab, T1, T3, s);
-    hipLaunchKernelGGL(k_cols_fwd<P>, grid8(P::G, nsub), dim3(P::THREADS), lds_bytes<P>(), s, T1, d_tw, rows, nsub);
-    hipLaunchKernelGGL(k_cols_fwd<P>, grid8(P::G, nsub), dim3(P::THREADS), lds_bytes<P>(), s, T3, d_tw, rows + unit, nsub);
+    const auto w = frame_ws<P>::ref_rows(bbx_ws(ctx, WS_CAND, frame_ws<P>::ref_rows(nullptr, nsub).bytes, &rc), nsub); if (rc) return rc;
+    rows_one<P>(ctx, d_tw, ny, nx, size, border, d_ref, d_sig_ref, spr, tab, w.T[1], w.T[3], s);
+    hipLaunchKernelGGL(k_cols_fwd<P>, grid8(P::G, nsub), dim3(P::THREADS), lds_bytes<P>(), s, w.T[1], d_tw, rows, nsub);
+    hipLaunchKernelGGL(k_cols_fwd<P>, grid8(P::G, nsub), dim3(P::THREADS), lds_bytes<P>(), s, w.T[3], d_tw, rows + (size_t)nsub * P::UNIT, nsub);
     BBX_LAUNCH_CHECK();
     return BBX_OK;
 }
@@ -1681,145 +1728,148 @@ static int fill_ref_rows(bbx_ctx* ctx, const float2* d_tw, int ny, int nx, int s
 template <class P>
 static int fill_ref_psf(bbx_ctx* ctx, const float2* d_tw, int nsub, const float* d_psf_r, int S, float2* out, hipStream_t s) {
     int rc = lds_attrs<P>(ctx); if (rc) return rc;
-    float2* Q = (float2*)bbx_ws(ctx, WS_CAND, (size_t)nsub * S * P::HP * sizeof(float2), &rc); if (rc) return rc;
-    hipLaunchKernelGGL(k_psf_rowdft<P>, dim3((P::H + 255) / 256, (S + ZQ_J - 1) / ZQ_J, nsub), dim3(256), 0, s, d_psf_r, d_psf_r, S, d_tw, Q, nsub);
-    hipLaunchKernelGGL(k_refpsf_cols<P>, grid8(P::G, nsub), dim3(P::THREADS), lds_bytes<P>(), s, Q, S, d_tw, out, nsub);
+    const auto w = frame_ws<P>::ref_psf(bbx_ws(ctx, WS_CAND, frame_ws<P>::ref_psf(nullptr, nsub, S).bytes, &rc), nsub, S); if (rc) return rc;
+    hipLaunchKernelGGL(k_psf_rowdft<P>, dim3((P::H + 255) / 256, (S + ZQ_J - 1) / ZQ_J, nsub), dim3(256), 0, s, d_psf_r, d_psf_r, S, d_tw, w.Qdft, nsub);
+    hipLaunchKernelGGL(k_refpsf_cols<P>, grid8(P::G, nsub), dim3(P::THREADS), lds_bytes<P>(), s, w.Qdft, S, d_tw, out, nsub);
     BBX_LAUNCH_CHECK();
     return BBX_OK;
 }
+
+// Which kernels a frame call runs: decided once at the top of run() from its arguments and the context, before anything is queued.
+struct frame_path {
+    bool vec4, spl, two;    // row pass: its 16-byte paths (rows_vec4); sigma maps read off their mini images; the two-image kernel k_img_rows
+    bool rows, psf;         // prepared reference rows; prepared reference PSF spectra (only with rows: zogy_frame_entry)
+    bool win; int wh, wb, nyb_psf;  // row window of k_n, k_r: half-height in rows (no window: L) and row blocks; row blocks of k_psf_rows / k_ks_rows
+    bool ks, fuse;          // k_n, k_r on the small grid; k_img_cols forms Pn^ and the grid's samples itself, no k_psf_cols at all (ks && psf)
+};
+// cut + row pass of the frames -> T[0..3] (prepared reference rows: of the new frame alone -> T[0], T[2])
 template <class P>
-static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, int nx, int size, int border, const float* d_new, const float* d_ref,
+static int launch_rows(bbx_ctx* ctx, const frame_path& pa, const frame_ws<P>& w, const float2* tw, int ny, int nx, int size, int border, const float* d_new,
+                       const float* d_ref, const float* d_sig_new, const float* d_sig_ref, const bbx_spl* spn, const bbx_spl* spr, hipStream_t s) {
+    if (pa.two) {
+        const int nsx = nx / size, nsub = (ny / size) * nsx;
+        const dim3 grow = grid8(P::LB, nsub);
+        frame_args fa; fa.a = d_new; fa.b = d_ref; fa.sa = nullptr; fa.sb = nullptr; fa.ny = ny; fa.nx = nx; fa.size = size; fa.border = border; fa.nsx = nsx;
+        fa.vec4 = pa.vec4 ? 1 : 0;
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, k_img_rows<P>, grow, dim3(P::LIGHT_THREADS), lds_bytes<P>(), s, fa, tw, w.T[0], w.T[1], nsub);
+        fa.sa = d_sig_new; fa.sb = d_sig_ref;
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, k_img_rows<P>, grow, dim3(P::LIGHT_THREADS), lds_bytes<P>(), s, fa, tw, w.T[2], w.T[3], nsub);
+        return BBX_OK;
+    }
+    char* tab = nullptr; size_t nbn = 0;                     // mini images: their cubic tables, the new frame's first
+    if (pa.spl) {
+        int rc;
+        nbn = spl_table_bytes(*spn, ny);
+        tab = (char*)bbx_ws(ctx, WS_ZSPL, nbn + (pa.rows ? 0 : spl_table_bytes(*spr, ny)), &rc); if (rc) return rc;
+    }
+    rows_one<P>(ctx, tw, ny, nx, size, border, d_new, d_sig_new, spn, (float4*)tab, w.T[0], w.T[2], s);
+    if (!pa.rows) rows_one<P>(ctx, tw, ny, nx, size, border, d_ref, d_sig_ref, spr, (float4*)(tab + nbn), w.T[1], w.T[3], s);
+    return BBX_OK;
+}
+
+// small grid: column pass and row pass of k_n, k_r on the samples in Ksm -> K2r, K2n.  The profile slots count the launches of a
+// frame: after k_psf_cols (its COLS slot) the two are one BBX_PROF_Z_PSF_ROWS entry, after k_img_cols (fuse) COLS and ROWS.
+template <class P>
+static void launch_ks(bbx_ctx* ctx, const frame_path& pa, const frame_ws<P>& w, const float2* tw, int nsub, hipStream_t s) {
+    if constexpr (small_of<P>::ok) {
+        typedef typename small_of<P>::type PK;
+        constexpr int M = PK::L, NG = (PK::H + PK::NL - 1) / PK::NL;
+        hipEvent_t c0 = nullptr, c1 = nullptr, r0 = nullptr, r1 = nullptr;
+        if (pa.fuse) bbx_prof_events(ctx, BBX_PROF_Z_PSF_COLS, &c0, &c1);
+        else bbx_prof_start(ctx, BBX_PROF_Z_PSF_ROWS, s);
+        hipExtLaunchKernelGGL((k_ks_cols<P, PK>), dim3((unsigned)(NG * 2 * nsub)), dim3(Z3_KS_THREADS), lds_ks_cols_bytes<PK>(), s, c0, c1, 0, w.Ksm, tw, w.Us,
+                              w.kchk, nsub, pa.wh);
+        if (pa.fuse) bbx_prof_events(ctx, BBX_PROF_Z_PSF_ROWS, &r0, &r1);
+        hipExtLaunchKernelGGL((k_ks_rows<P, PK>), grid8(pa.nyb_psf, nsub), dim3(P::LIGHT_THREADS), (lds_ks_rows_bytes<P, PK>()), s, r0, r1, 0, w.Us,
+                              1.0f / ((float)M * (float)M), tw, w.K2r, w.K2n, nsub, pa.nyb_psf, pa.wb, w.d_sc, w.fs_partial, w.sub_sc, ctx->d_err, w.kchk);
+        if (!pa.fuse) bbx_prof_stop(ctx, s);
+    }
+}
+
+template <class P>
+static int run(bbx_ctx* ctx, const float2* tw, zogy_chunk_plan* plan, int ny, int nx, int size, int border, const float* d_new, const float* d_ref,
                const float* d_sig_new, const float* d_sig_ref, const bbx_spl* spn, const bbx_spl* spr, const float* d_psf_n, const float* d_psf_r, int S, const float* h_scal,
                float* d_D, float* d_S, float* d_Scorr, float* d_Fpsf, float* d_Fpsferr, hipStream_t s) {
     const int nsy = ny / size, nsx = nx / size, nsub = nsy * nsx;
-    int rc;
-    const bool vec4 = rows_vec4<P>(nx, size, border, d_new, d_ref, d_sig_new, d_sig_ref);
-    const float2* ref_rows = ctx->zrows;                    // prepared reference rows (checked by zogy_frame_entry)
-    if (ref_rows && !vec4) return BBX_ERR_ARG;
-    const float2* ref_psf = ctx->zpsf;                      // prepared reference PSF spectra (checked by zogy_frame_entry: only with rows)
-    // chunks of the final kernel (chunk_plan; cached with the twiddle table)
-    const int yb0 = border / P::NL, yb1 = (border + size - 1) / P::NL, nyb = yb1 - yb0 + 1;
-    const int nslots = 2 * (ctx->num_cus > 0 ? ctx->num_cus : 256);
-    rc = chunk_plan(ctx, plan, yb0, nyb, nsub, nslots); if (rc) return rc;
-    const int nch = plan->nch;
-    const z3::chunk_args ch{plan->d_start, nch};
-    const size_t unit = (size_t)nsub * P::UNIT, hunit = (size_t)nsub * nch * P::HP;
-    // 4 T + 4 U arrays + the PSF spectra (Pn^, Pr^) as float4 (two arrays) + 2 row-transformed k^2 arrays + 2 halo arrays +
-    // the row DFTs of the stamps + scalars + partial sums
-    // (prepared reference PSF: Pn^ alone as float2, one array -- or, where k_img_cols forms it, the arrays of the small grid
-    // in its place; row DFTs of the new stamps only)
-    const int NARR = ref_psf ? 11 : 12;
-    const size_t qunit = (ref_psf ? 1 : 2) * (size_t)nsub * S * P::HP;
-    const size_t bytes = (NARR * unit + 2 * hunit + qunit) * sizeof(float2) + (size_t)nsub * sizeof(zscal) + 5 * (size_t)nsub * P::G * sizeof(double) + (size_t)nsub * sizeof(z3::sub_scal) + 4 * (size_t)nsub * sizeof(float) + 4096;
-    char* ws = (char*)bbx_ws(ctx, WS_CAND, bytes, &rc); if (rc) return rc;
-    float2* arr[12]; for (int i = 0; i < 12; i++) arr[i] = (float2*)ws + (size_t)i * unit;
-    float2 *HSn = (float2*)ws + NARR * unit, *HSr = HSn + hunit, *Qdft = HSr + hunit;
-    char* p = ws + (NARR * unit + 2 * hunit + qunit) * sizeof(float2);
-    zscal* d_sc = (zscal*)p; p += (size_t)nsub * sizeof(zscal);
-    p = (char*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-    double* fs_partial = (double*)p; p += 5 * (size_t)nsub * P::G * sizeof(double);
-    sub_scal* sub_sc = (sub_scal*)p; p += (size_t)nsub * sizeof(sub_scal);
-    float* kchk = (float*)p;                                 // small-grid path: [nsub][2][2] energies of the window check
-    float2 *T0 = arr[0], *T1 = arr[1], *T2 = arr[2], *T3 = arr[3], *U0 = arr[4], *U1 = arr[5], *U2 = arr[6], *U3 = arr[7];
-    float4* cP = (float4*)arr[8];                            // arr[8], arr[9] (prepared reference PSF: arr[8])
-    float2 *cK2n = arr[NARR - 2], *cK2r = arr[NARR - 1];
-    BBX_HIP(hipMemcpyAsync(d_sc, h_scal, (size_t)nsub * sizeof(zscal), hipMemcpyHostToDevice, s));      // pageable source: staged before the call returns
-    const size_t lds = lds_bytes<P>(), lds_fin = lds_fin_bytes<P>();
-    rc = lds_attrs<P>(ctx); if (rc) return rc;
-    const float inv_n2 = 1.0f / ((float)P::L * (float)P::L);
-    const dim3 gcol = grid8(P::G, nsub), grow = grid8(P::LB, nsub), blk(P::THREADS);
-    const float2* tw = d_tw;
+    frame_path pa;
+    pa.vec4 = rows_vec4<P>(nx, size, border, d_new, d_ref, d_sig_new, d_sig_ref);
+    pa.spl = spn != nullptr;
+    pa.two = !pa.spl && !pa.vec4;
+#ifdef Z3_ROWS_SPLIT
+    pa.two = !pa.spl;
+#endif
+    const float2 *ref_rows = ctx->zrows.buf, *ref_psf = ctx->zpsf.buf;      // prepared reference (checked by zogy_frame_entry)
+    pa.rows = ref_rows != nullptr; pa.psf = ref_psf != nullptr;
+    // prepared rows come in the layout of the one-image row kernel; mini images are read in aligned groups of four pixels
+    if (pa.rows && (!pa.vec4 || pa.two)) return BBX_ERR_ARG;
+    if (pa.spl && (!pa.vec4 || !spl_vec4(*spn) || (!pa.rows && !spl_vec4(*spr)))) return BBX_ERR_ARG;
     // Row window of the matched-filter kernels k_n, k_r (real space): they are as compact as the PSFs they are made
     // of, so only 2 wh of their L rows go through the inverse row pass, the squares and the forward row pass; the rest
     // is below float32 rounding (checked on the device, Z3_KWIN_TOL).  wh: a multiple of NL; W = 2 wh >= 4 S + 32.
-    int wh = P::L;                                          // 2 wh >= L: no window
+    pa.wh = P::L;                                           // 2 wh >= L: no window
     if (!ctx->zogy_kwin_off && P::L % P::NL == 0) {
         int w = ((4 * S + 32) / 2 + P::NL - 1) / P::NL * P::NL;
         if (w < 32) w = (32 + P::NL - 1) / P::NL * P::NL;
-        if (2 * w < P::L) wh = w;
+        if (2 * w < P::L) pa.wh = w;
     }
-    const bool win = 2 * wh < P::L;
-    const int wb = win ? wh / P::NL : 0, nyb_psf = win ? 2 * wb : P::LB;
-    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_DFT, k_psf_rowdft<P>, dim3((P::H + 255) / 256, (S + ZQ_J - 1) / ZQ_J, (ref_psf ? 1 : 2) * nsub), dim3(256), 0, s, d_psf_n, d_psf_r, S, tw, Qdft, nsub);
-    float2 *TK2r = cK2r, *TK2n = cK2n;                      // row-transformed (kr^2)^, (kn^2)^: T layout, column pass inside k_var_cols
+    pa.win = 2 * pa.wh < P::L;
+    pa.wb = pa.win ? pa.wh / P::NL : 0; pa.nyb_psf = pa.win ? 2 * pa.wb : P::LB;
     // Small grid: inside the window k_n, k_r are given by every F-th frequency of their spectra, so their way back to real
     // space runs at side M = L / F (1 / F^2 of the work); taken where the side has a plan and the window leaves a guard band
     // of a row block or more below M / 2 (L = 1400: F = 5, M = 280).  BBX_OPT_ZOGY_KSMALL_OFF: the full grid, as the sides without.
-    bool ks = false;
-    if constexpr (small_of<P>::ok) ks = win && !ctx->zogy_ksmall_off && small_of<P>::type::L / 2 - wh >= P::NL;
-    // Prepared reference PSF on the small-grid path: no k_psf_cols at all.  k_img_cols forms Pn^ itself and emits the sums and
-    // the small-grid samples; k_ks_cols and k_ks_rows follow it (below), their arrays in the space the PSF spectra leave.
-    const bool fuse = ks && ref_psf != nullptr;
-    if constexpr (small_of<P>::ok) if (ks && !fuse) {
-        typedef typename small_of<P>::type PK;
-        constexpr int M = PK::L, HM = PK::H, HMP = (HM + 7) / 8 * 8, NG = (HM + PK::NL - 1) / PK::NL;
-        static_assert(2 * (size_t)HM * M <= P::UNIT && 2 * (size_t)M * HMP <= P::UNIT && P::L % PK::L == 0 && M % P::NL == 0, "small-grid arrays fit a unit");
-        float2 *Ksm = U1, *Us = U2;                          // free until k_img_cols writes the U arrays
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_psf_cols<P, true>), gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, nullptr, (float2*)kchk, Ksm, fs_partial, nsub, wh);
-        bbx_prof_start(ctx, BBX_PROF_Z_PSF_ROWS, s);          // the two launches as one entry: the slots count frames
-        hipLaunchKernelGGL((k_ks_cols<P, PK>), dim3((unsigned)(NG * 2 * nsub)), dim3(Z3_KS_THREADS), lds_ks_cols_bytes<PK>(), s, Ksm, tw, Us, kchk, nsub, wh);
-        hipLaunchKernelGGL((k_ks_rows<P, PK>), grid8(nyb_psf, nsub), dim3(P::LIGHT_THREADS), (lds_ks_rows_bytes<P, PK>()), s, Us,
-                           1.0f / ((float)M * (float)M), tw, TK2r, TK2n, nsub, nyb_psf, wb, d_sc, fs_partial, sub_sc, ctx->d_err, kchk);
-        bbx_prof_stop(ctx, s);
+    pa.ks = false;
+    if constexpr (small_of<P>::ok) pa.ks = pa.win && !ctx->zogy_ksmall_off && small_of<P>::type::L / 2 - pa.wh >= P::NL;
+    pa.fuse = pa.ks && pa.psf;
+    // chunks of the final kernel (chunk_plan; cached with the twiddle table)
+    const int yb0 = border / P::NL, yb1 = (border + size - 1) / P::NL, nyb = yb1 - yb0 + 1;
+    const int nslots = 2 * (ctx->num_cus > 0 ? ctx->num_cus : 256);
+    int rc = chunk_plan(ctx, plan, yb0, nyb, nsub, nslots); if (rc) return rc;
+    const int nch = plan->nch;
+    const chunk_args ch{plan->d_start, nch};
+    const size_t bytes = frame_ws<P>(nullptr, nsub, nch, S, pa.psf, pa.fuse).bytes;
+    const frame_ws<P> w(bbx_ws(ctx, WS_CAND, bytes, &rc), nsub, nch, S, pa.psf, pa.fuse); if (rc) return rc;
+    BBX_HIP(hipMemcpyAsync(w.d_sc, h_scal, (size_t)nsub * sizeof(zscal), hipMemcpyHostToDevice, s));      // pageable source: staged before the call returns
+    const size_t lds = lds_bytes<P>(), lds_fin = lds_fin_bytes<P>();
+    rc = lds_attrs<P>(ctx); if (rc) return rc;
+    const float inv_n2 = 1.0f / ((float)P::L * (float)P::L);
+    const dim3 gcol = grid8(P::G, nsub), blk(P::THREADS);
+    // the PSFs: row DFTs of the stamps; then Pn^, Pr^ -> cP and (kn^2)^, (kr^2)^ row-transformed -> K2n, K2r (T layout: their
+    // column pass is inside k_var_cols), on the full grid or the small one -- or nothing more here (fuse)
+    BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_DFT, k_psf_rowdft<P>, dim3((P::H + 255) / 256, (S + ZQ_J - 1) / ZQ_J, (pa.psf ? 1 : 2) * nsub), dim3(256), 0, s, d_psf_n, d_psf_r, S, tw, w.Qdft, nsub);
+    auto psf_cols = [&](auto kern, float2* a, float2* b) {
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, kern, gcol, blk, lds, s, w.Qdft, S, w.d_sc, tw, w.cP, ref_psf, a, b, w.fs_partial, nsub, pa.wh);
+    };
+    if (!pa.ks) {
+        if (pa.psf) psf_cols(k_psf_cols<P, false, true>, w.U[0], w.U[1]);
+        else psf_cols(k_psf_cols<P, false>, w.U[0], w.U[1]);
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_ROWS, k_psf_rows<P>, grid8(pa.nyb_psf, nsub), dim3(P::LIGHT_THREADS), lds, s, w.U[1], w.U[0], inv_n2, tw, w.K2r, w.K2n, nsub,
+                         pa.nyb_psf, pa.wb, w.d_sc, w.fs_partial, w.sub_sc, ctx->d_err);
+    } else if (!pa.fuse) {
+        if constexpr (small_of<P>::ok) psf_cols(k_psf_cols<P, true>, (float2*)w.kchk, w.Ksm);
+        launch_ks<P>(ctx, pa, w, tw, nsub, s);
     }
-    if (!ks) {
-        if (ref_psf)
-            BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_psf_cols<P, false, true>), gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, ref_psf, U0, U1, fs_partial, nsub, wh);
-        else
-            BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_psf_cols<P, false>), gcol, blk, lds, s, Qdft, S, d_sc, tw, cP, nullptr, U0, U1, fs_partial, nsub, wh);
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_ROWS, k_psf_rows<P>, grid8(nyb_psf, nsub), dim3(P::LIGHT_THREADS), lds, s, U1, U0, inv_n2, tw, TK2r, TK2n, nsub,
-                         nyb_psf, wb, d_sc, fs_partial, sub_sc, ctx->d_err);
+    rc = launch_rows<P>(ctx, pa, w, tw, ny, nx, size, border, d_new, d_ref, d_sig_new, d_sig_ref, spn, spr, s); if (rc) return rc;
+    // D, Sn, Sr; V_S.  Prepared reference: R^, Vr^ come column-transformed (C layout).  k_img_cols<P, PREP, PPSF>: PPSF = 1
+    // reads the prepared Pr^, 2 forms Pn^ as well and feeds the small grid (fuse)
+    const float2 *TR = pa.rows ? ref_rows : w.T[1], *TVr = pa.rows ? ref_rows + (size_t)nsub * P::UNIT : w.T[3];
+    const psf_fuse_args pf = pa.fuse ? psf_fuse_args{w.Qdft, S, w.kchk, w.Ksm, w.fs_partial} : psf_fuse_args{nullptr, 0, nullptr, nullptr, nullptr};
+    auto img_cols = [&](auto kern) {
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, kern, gcol, blk, lds, s, w.T[0], TR, pa.fuse ? nullptr : w.cP, ref_psf, w.d_sc, tw, w.U[0], w.U[1], w.U[2], w.HSn, w.HSr,
+                         nsub, ch, pf);
+    };
+    if (!pa.rows) img_cols(k_img_cols<P, false>);
+    else if (!pa.psf) img_cols(k_img_cols<P, true>);
+    else if (!pa.fuse) img_cols(k_img_cols<P, true, 1>);
+    else {
+        if constexpr (small_of<P>::ok) img_cols(k_img_cols<P, true, 2>);
+        launch_ks<P>(ctx, pa, w, tw, nsub, s);
     }
-    const float* kchk_c = ks ? kchk : nullptr;
-    const float2 *TR = T1, *TVr = T3;
-    if (ref_rows) { TR = ref_rows; TVr = ref_rows + unit; }
-    if (spn) {
-        // sigma maps read off their mini images
-        if (!vec4 || !spl_vec4(*spn) || (!ref_rows && !spl_vec4(*spr))) return BBX_ERR_ARG;
-        const size_t nbn = spl_table_bytes(*spn, ny);
-        char* tab = (char*)bbx_ws(ctx, WS_ZSPL, nbn + (ref_rows ? 0 : spl_table_bytes(*spr, ny)), &rc); if (rc) return rc;
-        rows_one<P>(ctx, tw, ny, nx, size, border, d_new, nullptr, spn, (float4*)tab, T0, T2, s);
-        if (!ref_rows) rows_one<P>(ctx, tw, ny, nx, size, border, d_ref, nullptr, spr, (float4*)(tab + nbn), T1, T3, s);
-    } else
-#ifndef Z3_ROWS_SPLIT
-    if (vec4) {
-        rows_one<P>(ctx, tw, ny, nx, size, border, d_new, d_sig_new, nullptr, nullptr, T0, T2, s);
-        if (!ref_rows) rows_one<P>(ctx, tw, ny, nx, size, border, d_ref, d_sig_ref, nullptr, nullptr, T1, T3, s);
-    } else
-#endif
-    {
-        if (ref_rows) return BBX_ERR_ARG;
-        frame_args fa; fa.a = d_new; fa.b = d_ref; fa.sa = nullptr; fa.sb = nullptr; fa.ny = ny; fa.nx = nx; fa.size = size; fa.border = border; fa.nsx = nsx;
-        fa.vec4 = vec4 ? 1 : 0;
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, k_img_rows<P>, grow, dim3(P::LIGHT_THREADS), lds, s, fa, tw, T0, T1, nsub);
-        fa.sa = d_sig_new; fa.sb = d_sig_ref;
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_ROWS, k_img_rows<P>, grow, dim3(P::LIGHT_THREADS), lds, s, fa, tw, T2, T3, nsub);
-    }
-    // D, Sn, Sr; V_S.  Prepared reference: R^, Vr^ come column-transformed (C layout)
-    const psf_fuse_args nofuse{nullptr, 0, nullptr, nullptr, nullptr};
-    if (ref_rows) {
-        if (fuse) {
-            if constexpr (small_of<P>::ok) {
-                typedef typename small_of<P>::type PK;
-                constexpr int M = PK::L, HM = PK::H, HMP = (HM + 7) / 8 * 8, NG = (HM + PK::NL - 1) / PK::NL;
-                static_assert(2 * (size_t)HM * M + 2 * (size_t)M * HMP <= P::UNIT, "small-grid arrays fit a unit");
-                float2 *Ksm = arr[8], *Us = Ksm + (size_t)nsub * 2 * HM * M;
-                const psf_fuse_args pf{Qdft, S, kchk, Ksm, fs_partial};
-                BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, true, 2>), gcol, blk, lds, s, T0, TR, nullptr, ref_psf, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch, pf);
-                // the PSF side's column pass and its row pass, one slot each (the slots count the launches of a frame)
-                BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_COLS, (k_ks_cols<P, PK>), dim3((unsigned)(NG * 2 * nsub)), dim3(Z3_KS_THREADS), lds_ks_cols_bytes<PK>(), s, Ksm, tw, Us, kchk, nsub, wh);
-                BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_PSF_ROWS, (k_ks_rows<P, PK>), grid8(nyb_psf, nsub), dim3(P::LIGHT_THREADS), (lds_ks_rows_bytes<P, PK>()), s, Us,
-                                 1.0f / ((float)M * (float)M), tw, TK2r, TK2n, nsub, nyb_psf, wb, d_sc, fs_partial, sub_sc, ctx->d_err, kchk);
-            }
-        } else if (ref_psf)
-            BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, true, 1>), gcol, blk, lds, s, T0, TR, cP, ref_psf, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch, nofuse);
-        else
-            BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, true>), gcol, blk, lds, s, T0, TR, cP, nullptr, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch, nofuse);
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_VAR_COLS, (k_var_cols<P, true>), gcol, dim3(P::VAR_THREADS), lds, s, T2, TVr, TK2n, TK2r, tw, U3, sub_sc, nsub, wh, &ctx->d_counters[CNT_TICKET], kchk_c, ctx->d_err);
-    } else {
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_IMG_COLS, (k_img_cols<P, false>), gcol, blk, lds, s, T0, TR, cP, nullptr, d_sc, tw, U0, U1, U2, HSn, HSr, nsub, ch, nofuse);
-        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_VAR_COLS, (k_var_cols<P, false>), gcol, dim3(P::VAR_THREADS), lds, s, T2, TVr, TK2n, TK2r, tw, U3, sub_sc, nsub, wh, &ctx->d_counters[CNT_TICKET], kchk_c, ctx->d_err);
-    }
+    auto var_cols = [&](auto kern) {
+        BBX_LAUNCH_TIMED(ctx, BBX_PROF_Z_VAR_COLS, kern, gcol, dim3(P::VAR_THREADS), lds, s, w.T[2], TVr, w.K2n, w.K2r, tw, w.U[3], w.sub_sc, nsub, pa.wh,
+                         &ctx->d_counters[CNT_TICKET], pa.ks ? w.kchk : nullptr, ctx->d_err);
+    };
+    if (pa.rows) var_cols(k_var_cols<P, true>);
+    else var_cols(k_var_cols<P, false>);
     out_args oa; oa.D = d_D; oa.S = d_S; oa.Scorr = d_Scorr; oa.Fpsf = d_Fpsf; oa.Fpsferr = d_Fpsferr;
     oa.ny = ny; oa.nx = nx; oa.size = size; oa.border = border; oa.nsx = nsx; oa.vec4 = 0;
     const dim3 gfin = grid8(plan->ntasks < nslots ? plan->ntasks : nslots, 1);
@@ -1833,7 +1883,7 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
         BBX_HIP(hipMemsetAsync(cand_cnt, 0, sizeof(int32_t), s));
         cand_thr = ctx->zcand_thr;
     }
-    BBX_LAUNCH_TIMED(ctx, BBX_PROF_ZOGY_FINAL, k_final_rows<P>, gfin, dim3(P::FIN_THREADS), lds_fin, s, U0, U3, U1, U2, HSn, HSr, d_sc, sub_sc,
+    BBX_LAUNCH_TIMED(ctx, BBX_PROF_ZOGY_FINAL, k_final_rows<P>, gfin, dim3(P::FIN_THREADS), lds_fin, s, w.U[0], w.U[3], w.U[1], w.U[2], w.HSn, w.HSr, w.d_sc, w.sub_sc,
                      inv_n2, tw, oa, ch, plan->d_tasks, plan->ntasks, &ctx->d_counters[CNT_TICKET], nsub, cand_thr, cand_list, cand_cnt, cand_cap,
                      ctx->d_err);
     if (cand_thr > 0.f) { ctx->zcand_img = d_Scorr; ctx->zcand_thr_used = cand_thr; ctx->zcand_npix = (size_t)ny * nx; }
@@ -1843,81 +1893,23 @@ static int run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int ny, 
 
 }  // namespace z3
 
-int bbx_zogy3_supported(int L) { return (L == 1400 || L == 140 || L == 128 || L == 100 || L == 64) ? 1 : 0; }
-
-static int bbx_zogy3_run(bbx_ctx* ctx, const float2* d_tw, zogy_chunk_plan* plan, int L, int ny, int nx, int size, int border, const float* d_new, const float* d_ref,
-                  const float* d_sig_new, const float* d_sig_ref, const bbx_spl* spn, const bbx_spl* spr, const float* d_psf_n, const float* d_psf_r, int S, const float* h_scal,
-                  float* d_D, float* d_S, float* d_Scorr, float* d_Fpsf, float* d_Fpsferr, hipStream_t s) {
-#define Z3_RUN(...) return z3::run<z3::Plan<__VA_ARGS__>>(ctx, d_tw, plan, ny, nx, size, border, d_new, d_ref, d_sig_new, d_sig_ref, spn, spr, d_psf_n, d_psf_r, S, \
-                                                          h_scal, d_D, d_S, d_Scorr, d_Fpsf, d_Fpsferr, s)
-    switch (L) {
-        case 1400: Z3_RUN(Z3_PLAN1400);
-        case 140: Z3_RUN(5, 7, 4);
-        case 128: Z3_RUN(8, 16);
-        case 100: Z3_RUN(5, 5, 4);
-        case 64: Z3_RUN(8, 8);
-    }
-    return BBX_ERR_ARG;
-}
-
-static int bbx_zogy3_fill_ref_rows(bbx_ctx* ctx, const float2* d_tw, int L, int ny, int nx, int size, int border, const float* d_ref, const float* d_sig_ref,
-                                   const bbx_spl* spr, float2* rows, hipStream_t s) {
-#define Z3_FILL(...) return z3::fill_ref_rows<z3::Plan<__VA_ARGS__>>(ctx, d_tw, ny, nx, size, border, d_ref, d_sig_ref, spr, rows, s)
-    switch (L) {
-        case 1400: Z3_FILL(Z3_PLAN1400);
-        case 140: Z3_FILL(5, 7, 4);
-        case 128: Z3_FILL(8, 16);
-        case 100: Z3_FILL(5, 5, 4);
-        case 64: Z3_FILL(8, 8);
-    }
-    return BBX_ERR_ARG;
-}
-static int bbx_zogy3_fill_ref_psf(bbx_ctx* ctx, const float2* d_tw, int L, int nsub, const float* d_psf_r, int S, float2* out, hipStream_t s) {
-#define Z3_FILLP(...) return z3::fill_ref_psf<z3::Plan<__VA_ARGS__>>(ctx, d_tw, nsub, d_psf_r, S, out, s)
-    switch (L) {
-        case 1400: Z3_FILLP(Z3_PLAN1400);
-        case 140: Z3_FILLP(5, 7, 4);
-        case 128: Z3_FILLP(8, 16);
-        case 100: Z3_FILLP(5, 5, 4);
-        case 64: Z3_FILLP(8, 8);
-    }
-    return BBX_ERR_ARG;
-}
-// entries of one sub-image's spectrum in C layout: G column groups of NL lines of L
-static size_t bbx_zogy3_cunit(int L) {
-#define Z3_CUNIT(...) return (size_t)z3::Plan<__VA_ARGS__>::G * z3::Plan<__VA_ARGS__>::NL * z3::Plan<__VA_ARGS__>::L
-    switch (L) {
-        case 1400: Z3_CUNIT(Z3_PLAN1400);
-        case 140: Z3_CUNIT(5, 7, 4);
-        case 128: Z3_CUNIT(8, 16);
-        case 100: Z3_CUNIT(5, 5, 4);
-        case 64: Z3_CUNIT(8, 8);
-    }
-    return 0;
-}
-static size_t bbx_zogy3_unit(int L) {
-#define Z3_UNIT(...) return z3::Plan<__VA_ARGS__>::UNIT
-    switch (L) {
-        case 1400: Z3_UNIT(Z3_PLAN1400);
-        case 140: Z3_UNIT(5, 7, 4);
-        case 128: Z3_UNIT(8, 16);
-        case 100: Z3_UNIT(5, 5, 4);
-        case 64: Z3_UNIT(8, 8);
-    }
-    return 0;
-}
+extern "C" int bbx_zogy_frame_supported(int L) { return z3::with_plan(L, 0, [](auto) { return 1; }); }
+// entries of one sub-image's T / U array, and of its spectrum in C layout: G column groups of NL lines of L
+static size_t bbx_zogy3_unit(int L) { return z3::with_plan(L, (size_t)0, [](auto p) { return decltype(p)::UNIT; }); }
+static size_t bbx_zogy3_cunit(int L) { return z3::with_plan(L, (size_t)0, [](auto p) { return (size_t)decltype(p)::G * decltype(p)::NL * decltype(p)::L; }); }
 
 // ---- entry points (include/bbx.h) ------------------------------------------------------------------------------------
-struct zogy_tw_state { float2* d_tw; int L; zogy_chunk_plan plan; };
+// what the context keeps for bbx_zogy_frame across calls: the twiddle table of the sub-image side, the chunk plan of the geometry
+struct zogy_frame_tables { float2* d_tw; int L; z3::zogy_chunk_plan plan; };
 
-void bbx_zogy2_release(bbx_ctx* ctx) {          // (name kept: bbx_ctx_destroy calls it) frees the context's twiddle table
-    if (!ctx || !ctx->zogy2_state) return;
-    zogy_tw_state* st = (zogy_tw_state*)ctx->zogy2_state;
+void bbx_zogy_frame_release(bbx_ctx* ctx) {          // called by bbx_ctx_destroy
+    if (!ctx || !ctx->zogy_frame_state) return;
+    zogy_frame_tables* st = (zogy_frame_tables*)ctx->zogy_frame_state;
     if (st->d_tw) (void)hipFree(st->d_tw);
     if (st->plan.d_start) (void)hipFree(st->plan.d_start);
     if (st->plan.d_tasks) (void)hipFree(st->plan.d_tasks);
     free(st);
-    ctx->zogy2_state = nullptr;
+    ctx->zogy_frame_state = nullptr;
 }
 
 #ifdef Z3_STAMPS
@@ -1928,8 +1920,6 @@ extern "C" int bbx_z3_stamps(void* buf) {
 }
 #endif
 
-extern "C" int bbx_zogy_frame_supported(int L) { return bbx_zogy3_supported(L); }
-
 extern "C" int bbx_zogy_candidates(bbx_ctx* ctx, float thr) {
     if (!ctx || !(thr >= 0.f)) return BBX_ERR_ARG;
     ctx->zcand_thr = thr;
@@ -1937,13 +1927,13 @@ extern "C" int bbx_zogy_candidates(bbx_ctx* ctx, float thr) {
     return BBX_OK;
 }
 
-// the context's twiddle table for sub-images of side L
-static int zogy_tw(bbx_ctx* ctx, int L, zogy_tw_state** out) {
-    if (!ctx->zogy2_state) {
-        ctx->zogy2_state = calloc(1, sizeof(zogy_tw_state));
-        if (!ctx->zogy2_state) return BBX_ERR_NOMEM;
+// the context's tables, with the twiddle table for sub-images of side L
+static int zogy_tables(bbx_ctx* ctx, int L, zogy_frame_tables** out) {
+    if (!ctx->zogy_frame_state) {
+        ctx->zogy_frame_state = calloc(1, sizeof(zogy_frame_tables));
+        if (!ctx->zogy_frame_state) return BBX_ERR_NOMEM;
     }
-    zogy_tw_state* st = (zogy_tw_state*)ctx->zogy2_state;
+    zogy_frame_tables* st = (zogy_frame_tables*)ctx->zogy_frame_state;
     if (st->L != L) {
         // twiddle table W^m = exp(-2 pi i m / L), float64 on the host, rounded once
         if (st->d_tw) { BBX_HIP(hipDeviceSynchronize()); BBX_HIP(hipFree(st->d_tw)); st->d_tw = nullptr; }
@@ -1963,14 +1953,34 @@ static int zogy_tw(bbx_ctx* ctx, int L, zogy_tw_state** out) {
     return BBX_OK;
 }
 
+// a frame geometry the frame call takes: whole sub-images of a side with a plan, 4096 at most; aligned: and groups of four
+// pixels that never straddle a sub-image edge, as the prepared reference needs them
+static bool zgeom_ok(int ny, int nx, int size, int border, bool aligned) {
+    if (size < 1 || border < 0 || ny < size || nx < size || ny % size || nx % size) return false;
+    const int L = size + 2 * border;
+    if (!bbx_zogy_frame_supported(L) || (ny / size) * (nx / size) > 4096) return false;
+    return !aligned || (size % 4 == 0 && border % 4 == 0 && nx % 4 == 0 && L % 4 == 0);
+}
+// prepared reference data (bbx_common.h): made of these very inputs, S and geometry?
+static bool zprep_matches(const bbx_zprep& z, const void* id0, const void* id1, int S, int ny, int nx, int size, int border) {
+    return z.id[0] == id0 && z.id[1] == id1 && z.S == S && z.geom[0] == ny && z.geom[1] == nx && z.geom[2] == size && z.geom[3] == border;
+}
+// forget what was prepared; then, with a buffer, remember it and what it was made of (inputs_ok: the caller's own checks of them)
+static int zprep_set(bbx_zprep* z, const void* buf, const void* id0, const void* id1, int S, bool inputs_ok, int ny, int nx, int size, int border) {
+    *z = bbx_zprep{};
+    if (!buf) return BBX_OK;
+    if (!inputs_ok || !zgeom_ok(ny, nx, size, border, true) || (uintptr_t)buf % 16) return BBX_ERR_ARG;
+    *z = bbx_zprep{(const float2*)buf, {id0, id1}, S, {ny, nx, size, border}};
+    return BBX_OK;
+}
+
 static int zogy_frame_entry(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_new, const float* d_ref,
                             const float* d_sig_new, const float* d_sig_ref, const bbx_spline_image* sig_new, const bbx_spline_image* sig_ref,
                             const float* d_psf_n, const float* d_psf_r, int S,
                             const float* h_scal, float* d_D, float* d_S, float* d_Scorr, float* d_Fpsf, float* d_Fpsferr, void* stream) {
     if (!ctx || !d_new || !d_ref || !d_psf_n || !d_psf_r || !h_scal || !d_D || !d_Scorr || !d_Fpsf || !d_Fpsferr) return BBX_ERR_ARG;
-    if (size < 1 || border < 0 || ny < size || nx < size || ny % size || nx % size || S < 1) return BBX_ERR_ARG;
     const int L = size + 2 * border;
-    if (!bbx_zogy_frame_supported(L) || S > L || (ny / size) * (nx / size) > 4096) return BBX_ERR_ARG;
+    if (!zgeom_ok(ny, nx, size, border, false) || S < 1 || S > L) return BBX_ERR_ARG;
     bbx_spl spn, spr;
     const bool spl = sig_new != nullptr;
     if (spl) {
@@ -1978,18 +1988,16 @@ static int zogy_frame_entry(bbx_ctx* ctx, int ny, int nx, int size, int border, 
         rc = bbx_spl_make(sig_ref, ny, nx, &spr); if (rc) return rc;
     }
     // prepared reference rows (bbx_zogy_refrows): only for the very reference, sigma map and geometry they were made of
-    if (ctx->zrows && (d_ref != ctx->zrows_ref || (spl ? (const void*)sig_ref->d_coef : (const void*)d_sig_ref) != ctx->zrows_sig || ny != ctx->zrows_geom[0] ||
-                       nx != ctx->zrows_geom[1] || size != ctx->zrows_geom[2] || border != ctx->zrows_geom[3]))
-        return BBX_ERR_ARG;
+    if (ctx->zrows.buf && !zprep_matches(ctx->zrows, d_ref, spl ? (const void*)sig_ref->d_coef : (const void*)d_sig_ref, 0, ny, nx, size, border)) return BBX_ERR_ARG;
     // prepared reference PSF spectra (bbx_zogy_refpsf): only with prepared rows, for the very stamps, S and geometry they were made of
-    if (ctx->zpsf && (!ctx->zrows || d_psf_r != ctx->zpsf_stamps || S != ctx->zpsf_S || ny != ctx->zpsf_geom[0] || nx != ctx->zpsf_geom[1] ||
-                      size != ctx->zpsf_geom[2] || border != ctx->zpsf_geom[3]))
-        return BBX_ERR_ARG;
+    if (ctx->zpsf.buf && (!ctx->zrows.buf || !zprep_matches(ctx->zpsf, d_psf_r, nullptr, S, ny, nx, size, border))) return BBX_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    zogy_tw_state* st;
-    int rc = zogy_tw(ctx, L, &st); if (rc) return rc;
-    return bbx_zogy3_run(ctx, st->d_tw, &st->plan, L, ny, nx, size, border, d_new, d_ref, d_sig_new, d_sig_ref, spl ? &spn : nullptr, spl ? &spr : nullptr,
-                         d_psf_n, d_psf_r, S, h_scal, d_D, d_S, d_Scorr, d_Fpsf, d_Fpsferr, s);
+    zogy_frame_tables* st;
+    int rc = zogy_tables(ctx, L, &st); if (rc) return rc;
+    return z3::with_plan(L, BBX_ERR_ARG, [&](auto p) {
+        return z3::run<decltype(p)>(ctx, st->d_tw, &st->plan, ny, nx, size, border, d_new, d_ref, d_sig_new, d_sig_ref, spl ? &spn : nullptr, spl ? &spr : nullptr,
+                                    d_psf_n, d_psf_r, S, h_scal, d_D, d_S, d_Scorr, d_Fpsf, d_Fpsferr, s);
+    });
 }
 
 extern "C" int bbx_zogy_frame(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_new, const float* d_ref,
@@ -2011,26 +2019,22 @@ extern "C" int bbx_zogy_frame_mini(bbx_ctx* ctx, int ny, int nx, int size, int b
 }
 
 // ---- prepared reference rows ---------------------------------------------------------------------------------------
-static bool refrows_geom_ok(int ny, int nx, int size, int border) {
-    if (size < 1 || border < 0 || ny < size || nx < size || ny % size || nx % size) return false;
-    const int L = size + 2 * border;
-    return bbx_zogy_frame_supported(L) && (ny / size) * (nx / size) <= 4096 && size % 4 == 0 && border % 4 == 0 && nx % 4 == 0 && L % 4 == 0;
-}
-
 extern "C" size_t bbx_zogy_refrows_bytes(int ny, int nx, int size, int border) {
-    if (!refrows_geom_ok(ny, nx, size, border)) return 0;
+    if (!zgeom_ok(ny, nx, size, border, true)) return 0;
     return 2 * (size_t)(ny / size) * (nx / size) * bbx_zogy3_unit(size + 2 * border) * sizeof(float2);
 }
 
 static int refrows_fill_entry(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_ref, const float* d_sig_ref, const bbx_spline_image* sig_ref,
                               void* d_rows, void* stream) {
-    if (!ctx || !d_ref || !d_rows || (!d_sig_ref && !sig_ref) || !refrows_geom_ok(ny, nx, size, border)) return BBX_ERR_ARG;
+    if (!ctx || !d_ref || !d_rows || (!d_sig_ref && !sig_ref) || !zgeom_ok(ny, nx, size, border, true)) return BBX_ERR_ARG;
     bbx_spl spr;
     if (sig_ref) { int rc = bbx_spl_make(sig_ref, ny, nx, &spr); if (rc) return rc; }
     const int L = size + 2 * border;
-    zogy_tw_state* st;
-    int rc = zogy_tw(ctx, L, &st); if (rc) return rc;
-    return bbx_zogy3_fill_ref_rows(ctx, st->d_tw, L, ny, nx, size, border, d_ref, d_sig_ref, sig_ref ? &spr : nullptr, (float2*)d_rows, (hipStream_t)stream);
+    zogy_frame_tables* st;
+    int rc = zogy_tables(ctx, L, &st); if (rc) return rc;
+    return z3::with_plan(L, BBX_ERR_ARG, [&](auto p) {
+        return z3::fill_ref_rows<decltype(p)>(ctx, st->d_tw, ny, nx, size, border, d_ref, d_sig_ref, sig_ref ? &spr : nullptr, (float2*)d_rows, (hipStream_t)stream);
+    });
 }
 
 extern "C" int bbx_zogy_refrows_fill(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_ref, const float* d_sig_ref, void* d_rows, void* stream) {
@@ -2046,36 +2050,28 @@ extern "C" int bbx_zogy_refrows_fill_mini(bbx_ctx* ctx, int ny, int nx, int size
 
 extern "C" int bbx_zogy_refrows(bbx_ctx* ctx, const void* d_rows, int ny, int nx, int size, int border, const float* d_ref, const void* ref_sigma) {
     if (!ctx) return BBX_ERR_ARG;
-    ctx->zrows = nullptr; ctx->zrows_ref = nullptr; ctx->zrows_sig = nullptr;
-    if (!d_rows) return BBX_OK;
-    if (!d_ref || !ref_sigma || !refrows_geom_ok(ny, nx, size, border) || (uintptr_t)d_rows % 16) return BBX_ERR_ARG;
-    ctx->zrows = (const float2*)d_rows; ctx->zrows_ref = d_ref; ctx->zrows_sig = ref_sigma;
-    ctx->zrows_geom[0] = ny; ctx->zrows_geom[1] = nx; ctx->zrows_geom[2] = size; ctx->zrows_geom[3] = border;
-    return BBX_OK;
+    return zprep_set(&ctx->zrows, d_rows, d_ref, ref_sigma, 0, d_ref && ref_sigma, ny, nx, size, border);
 }
 
 // ---- prepared reference PSF spectra ------------------------------------------------------------------------------
 extern "C" size_t bbx_zogy_refpsf_bytes(int ny, int nx, int size, int border) {
-    if (!refrows_geom_ok(ny, nx, size, border)) return 0;
+    if (!zgeom_ok(ny, nx, size, border, true)) return 0;
     return (size_t)(ny / size) * (nx / size) * bbx_zogy3_cunit(size + 2 * border) * sizeof(float2);
 }
 
 extern "C" int bbx_zogy_refpsf_fill(bbx_ctx* ctx, int ny, int nx, int size, int border, const float* d_psf_r, int S, void* d_out, void* stream) {
-    if (!ctx || !d_psf_r || !d_out || (uintptr_t)d_out % 16 || !refrows_geom_ok(ny, nx, size, border) || S < 1 || S > size + 2 * border) return BBX_ERR_ARG;
+    if (!ctx || !d_psf_r || !d_out || (uintptr_t)d_out % 16 || !zgeom_ok(ny, nx, size, border, true) || S < 1 || S > size + 2 * border) return BBX_ERR_ARG;
     const int L = size + 2 * border;
-    zogy_tw_state* st;
-    int rc = zogy_tw(ctx, L, &st); if (rc) return rc;
-    return bbx_zogy3_fill_ref_psf(ctx, st->d_tw, L, (ny / size) * (nx / size), d_psf_r, S, (float2*)d_out, (hipStream_t)stream);
+    zogy_frame_tables* st;
+    int rc = zogy_tables(ctx, L, &st); if (rc) return rc;
+    return z3::with_plan(L, BBX_ERR_ARG, [&](auto p) {
+        return z3::fill_ref_psf<decltype(p)>(ctx, st->d_tw, (ny / size) * (nx / size), d_psf_r, S, (float2*)d_out, (hipStream_t)stream);
+    });
 }
 
 extern "C" int bbx_zogy_refpsf(bbx_ctx* ctx, const void* d_spec, int ny, int nx, int size, int border, const float* d_psf_r, int S) {
     if (!ctx) return BBX_ERR_ARG;
-    ctx->zpsf = nullptr; ctx->zpsf_stamps = nullptr; ctx->zpsf_S = 0;
-    if (!d_spec) return BBX_OK;
-    if (!d_psf_r || !refrows_geom_ok(ny, nx, size, border) || S < 1 || S > size + 2 * border || (uintptr_t)d_spec % 16) return BBX_ERR_ARG;
-    ctx->zpsf = (const float2*)d_spec; ctx->zpsf_stamps = d_psf_r; ctx->zpsf_S = S;
-    ctx->zpsf_geom[0] = ny; ctx->zpsf_geom[1] = nx; ctx->zpsf_geom[2] = size; ctx->zpsf_geom[3] = border;
-    return BBX_OK;
+    return zprep_set(&ctx->zpsf, d_spec, d_psf_r, nullptr, S, d_psf_r && S >= 1 && (long long)S <= (long long)size + 2LL * border, ny, nx, size, border);
 }
 
 // bbx_build_flags (bbx_ctx.hip): any timing / diagnostic switch of this file compiled in?

@@ -18,7 +18,7 @@ if not torch.cuda.is_available():
 import zogy_core as Z                       # noqa: E402
 from blackbox_amd import reduce as R       # noqa: E402
 from blackbox_amd import zogy as G          # noqa: E402
-from blackbox_amd._lib import lib          # noqa: E402
+from blackbox_amd._lib import lib, BBX_OPT_ZOGY_KWIN_OFF          # noqa: E402
 
 F = np.float32
 
@@ -118,9 +118,6 @@ def test_frame_path_vs_rocfft_path(ctx):
     for name, x, y in zip(('D', 'S', 'Scorr', 'Fpsf', 'Fpsferr'), a, b):
         x, y = x.cpu().numpy(), y.cpu().numpy()
         assert np.abs(x - y).max() <= 2e-5 * np.abs(y).max(), name
-
-
-BBX_OPT_ZOGY_KWIN_OFF = 4
 
 
 def test_kernel_row_window_equals_full_transforms(ctx):

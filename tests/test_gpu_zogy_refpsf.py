@@ -88,7 +88,22 @@ def test_prepared_psf_equals_rows_only_and_unprepared(ctx, geom, form):
 def test_prepared_psf_equals_unprepared_at_1400(ctx, S, small):
     """the production side: NL = 4 column kernels with 768 threads, the zero-skip of the stamps' transform, and the k_n, k_r
     samples of the 280-point grid (small) or the two inverse transforms of the full grid"""
-    c = ZS.case(ctx, S)
+    at_1400(ctx, ZS.case(ctx, S), small)
+
+
+def test_prepared_psf_equals_unprepared_at_1400_mini(ctx):
+    """the same with the sigma maps read off their mini images: the small grid behind the mini form of the row kernel, unprepared,
+    with prepared rows, and with k_img_cols feeding it (prepared PSF)"""
+    c = dict(ZS.case(ctx, 25))
+    ny, nx, box = ZS.NSY * ZS.SIZE, ZS.NSX * ZS.SIZE, 60
+    yy, xx = np.mgrid[0:ny // box, 0:nx // box]
+    c['sn'] = G.MiniImage(ctx, (14 + 2 * np.sin(yy / 5.0) * np.cos(xx / 7.0)).astype(F), box, interp_Xchan=True)
+    c['sr'] = G.MiniImage(ctx, (6 + np.cos(yy / 6.0 + xx / 9.0)).astype(F), box, interp_Xchan=True)
+    assert G.mini_path_supported((ny, nx), ZS.SIZE, ZS.BORDER, box, c['sn'], c['sr'])
+    at_1400(ctx, c, True)
+
+
+def at_1400(ctx, c, small):
     if not small:
         assert lib.bbx_set_option(ctx.h, BBX_OPT_ZOGY_KSMALL_OFF, 1) == 0
     try:

@@ -17,12 +17,11 @@ import zogy_core as Z                      # noqa: E402
 import test_gpu_zogy_frame as ZF           # noqa: E402  (make, oracle, dev, moffat: the toy frames and the oracle chain of that file)
 from blackbox_amd import reduce as R       # noqa: E402
 from blackbox_amd import zogy as G          # noqa: E402
-from blackbox_amd._lib import lib, BBXError, BBX_OPT_ZOGY_KSMALL_OFF          # noqa: E402
+from blackbox_amd._lib import lib, BBXError, BBX_OPT_ZOGY_KSMALL_OFF, BBX_OPT_ZOGY_KWIN_OFF          # noqa: E402
 
 F = np.float32
 NAMES = ('D', 'S', 'Scorr', 'Fpsf', 'Fpsferr')
 SIZE, BORDER, NSY, NSX = 1320, 40, 1, 2
-BBX_OPT_ZOGY_KWIN_OFF = 4
 
 
 @pytest.fixture(scope='module')
@@ -35,21 +34,21 @@ def ctx():
 _CASES = {}
 
 
-def case(ctx, S):
-    """two frames (other pixels, other PSFs) against one reference; made once per stamp size, left unchanged"""
-    if S not in _CASES:
-        new0, ref, sig_n, sig_r, pn0, pr, scal0 = ZF.make(SIZE, BORDER, NSY, NSX, S, seed=1400 + S)
-        new1, _, _, _, pn1, _, scal1 = ZF.make(SIZE, BORDER, NSY, NSX, S, seed=1401 + S)
+def case(ctx, S, size=SIZE, border=BORDER):
+    """two frames (other pixels, other PSFs) against one reference; made once per stamp size and cut, left unchanged"""
+    if (S, size) not in _CASES:
+        new0, ref, sig_n, sig_r, pn0, pr, scal0 = ZF.make(size, border, NSY, NSX, S, seed=1400 + S)
+        new1, _, _, _, pn1, _, scal1 = ZF.make(size, border, NSY, NSX, S, seed=1401 + S)
         pn1 = pn1[::-1].copy()
-        _CASES[S] = dict(host=[(new0, pn0, scal0), (new1, pn1, scal1)], h_ref=ref, h_sn=sig_n, h_sr=sig_r, h_pr=pr,
+        _CASES[(S, size)] = dict(size=size, border=border, host=[(new0, pn0, scal0), (new1, pn1, scal1)], h_ref=ref, h_sn=sig_n, h_sr=sig_r, h_pr=pr,
                          ref=ZF.dev(ctx, ref), sn=ZF.dev(ctx, sig_n), sr=ZF.dev(ctx, sig_r), pr=ZF.dev(ctx, pr),
                          frames=[(ZF.dev(ctx, new0), ZF.dev(ctx, pn0), scal0), (ZF.dev(ctx, new1), ZF.dev(ctx, pn1), scal1)])
-    return _CASES[S]
+    return _CASES[(S, size)]
 
 
 def run(ctx, c, k, rows=None):
     new, pn, scal = c['frames'][k]
-    out = G.run_zogy_frame(ctx, new, c['ref'], c['sn'], c['sr'], pn, c['pr'], scal, SIZE, BORDER, want_S=True, ref_rows=rows)
+    out = G.run_zogy_frame(ctx, new, c['ref'], c['sn'], c['sr'], pn, c['pr'], scal, c['size'], c['border'], want_S=True, ref_rows=rows)
     ctx.sync()
     return [o.cpu().numpy() for o in out]
 
@@ -89,7 +88,17 @@ def test_prepared_equals_unprepared_at_1400(ctx, S):
 
 
 def test_small_grid_equals_window_path(ctx):
-    c = case(ctx, 49)
+    small_grid_equals_window_path(ctx, case(ctx, 49))
+
+
+def test_small_grid_equals_window_path_behind_the_two_image_row_kernel(ctx):
+    """another cut of L = 1400 (1322 + 2 * 39) whose groups of four pixels straddle the sub-image edges: the row pass of the
+    frames without the 16-byte paths"""
+    assert not G.RefRows.supported((NSY * 1322, NSX * 1322), 1322, 39)
+    small_grid_equals_window_path(ctx, case(ctx, 49, 1322, 39))
+
+
+def small_grid_equals_window_path(ctx, c):
     a = run(ctx, c, 0)
     assert lib.bbx_set_option(ctx.h, BBX_OPT_ZOGY_KSMALL_OFF, 1) == 0
     try:
