@@ -17,40 +17,15 @@
 #include "bbx_mednet.h"
 
 #define BOX_NS 4096                 // 64 lanes x 64 registers: boxes up to 64 x 64 pixels
-#define BOX_PAD 0xffffffffu         // key of a slot without usable pixel (above the key of +inf)
+#define BOX_PAD 0xffffffffu         // key of a slot without usable pixel (above the key of +inf): f2key of the NaN bit
+                                    // pattern 0x7fffffff, which no usable pixel can have (NaN pixels are not usable)
 
-__device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t o;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c));
-    return o;
-}
+// f2key / key2f (bbx_common.h) as one xor with a mask chosen by the sign, where the shared pair selects between two values:
+// the same bits, u ^ (s ? 0xffffffff : 0x80000000) = s ? ~u : (u | 0x80000000).  The spelling k_bkg_boxstats_fast and the
+// load loops of both box kernels were tuned with, and the only one they use (one vector instruction per key
+// less in the load loops; the fast kernel 0.2 - 1 % slower with the shared pair at any of its sites)
+__device__ __forceinline__ uint32_t box_float_key(float f) { const uint32_t u = __float_as_uint(f); return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u); }
 __device__ __forceinline__ float box_key_value(uint32_t u) { return __uint_as_float((u >> 31) ? (u ^ 0x80000000u) : ~u); }
-
-// compare-exchange stage between registers r and r^J of every lane, directions fixed by the
-// element index (levels of 2..32 elements of the bitonic network)
-template <int K, int J> __device__ __forceinline__ void box_stage_static(uint32_t (&k)[64]) {
-#pragma unroll
-    for (int r = 0; r < 64; r++) {
-        const int q = r ^ J;
-        if (q > r) {
-            const uint32_t a = k[r], b = k[q];
-            const uint32_t lo = min(a, b), hi = max(a, b);
-            if ((r & K) == 0) { k[r] = lo; k[q] = hi; } else { k[r] = hi; k[q] = lo; }
-        }
-    }
-}
-// the same with the direction of the lane: clo = 0 sorts ascending (med3(a,b,0) = min), ~0 descending
-template <int J> __device__ __forceinline__ void box_stage_lane(uint32_t (&k)[64], uint32_t clo) {
-    const uint32_t chi = ~clo;
-#pragma unroll
-    for (int r = 0; r < 64; r++) {
-        const int q = r ^ J;
-        if (q > r) {
-            const uint32_t a = k[r], b = k[q];
-            k[r] = umed3(a, b, clo); k[q] = umed3(a, b, chi);
-        }
-    }
-}
 
 // index of sorted element i in LDS: one word of padding per lane's 64 so that the lanes'
 // stores fall in different banks
@@ -110,7 +85,7 @@ __device__ __forceinline__ void box_full_sort(const float* __restrict__ data, co
             const uint32_t u = k[c];
             const float d = __uint_as_float(u);
             const bool ok = (c * 64 + lane < npx) & (mk[c] == 0) & (d != 0.f) & (d == d);
-            k[c] = ok ? (u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u)) : BOX_PAD;
+            k[c] = ok ? box_float_key(d) : BOX_PAD;
             cnt += ok;
         }
     }
@@ -119,26 +94,9 @@ __device__ __forceinline__ void box_full_sort(const float* __restrict__ data, co
         if (lane == 0) { const float nanv = __uint_as_float(0x7fc00000u); mini_med[ibox] = nanv; mini_std[ibox] = nanv; }
         return;
     }
-    // sorted position of element (lane, r) is lane*64 + r
-    box_stage_static<2, 1>(k);
-    box_stage_static<4, 2>(k); box_stage_static<4, 1>(k);
-    box_stage_static<8, 4>(k); box_stage_static<8, 2>(k); box_stage_static<8, 1>(k);
-    box_stage_static<16, 8>(k); box_stage_static<16, 4>(k); box_stage_static<16, 2>(k); box_stage_static<16, 1>(k);
-    box_stage_static<32, 16>(k); box_stage_static<32, 8>(k); box_stage_static<32, 4>(k); box_stage_static<32, 2>(k);
-    box_stage_static<32, 1>(k);
-    for (int ll = 0; ll <= 6; ll++) {                     // runs of 64 << ll elements
-        const bool asc = (lane & (1 << ll)) == 0;         // ll = 6: one ascending run
-        for (int m = (1 << ll) >> 1; m > 0; m >>= 1) {
-            const uint32_t c = (((lane & m) == 0) == asc) ? 0u : 0xffffffffu;   // keep the smaller / the larger
+    wave_sort<64>(k, lane);                               // sorted position of element (lane, r) is lane*64 + r
 #pragma unroll
-            for (int r = 0; r < 64; r++) k[r] = umed3(k[r], (uint32_t)__shfl_xor((int)k[r], m), c);
-        }
-        const uint32_t clo = asc ? 0u : 0xffffffffu;
-        box_stage_lane<32>(k, clo); box_stage_lane<16>(k, clo); box_stage_lane<8>(k, clo);
-        box_stage_lane<4>(k, clo); box_stage_lane<2>(k, clo); box_stage_lane<1>(k, clo);
-    }
-#pragma unroll
-    for (int r = 0; r < 64; r++) v[lane * 65 + r] = box_key_value(k[r]);
+    for (int r = 0; r < 64; r++) v[lane * 65 + r] = key2f(k[r]);
     __syncthreads();
     // sums about a pivot close to the final mean (the median of all usable pixels); the clip
     // iterations subtract what they remove
@@ -146,7 +104,7 @@ __device__ __forceinline__ void box_full_sort(const float* __restrict__ data, co
     double s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int r = 0; r < 64; r++) {
-        const double t = (k[r] != BOX_PAD) ? (double)box_key_value(k[r]) - piv : 0.0;
+        const double t = (k[r] != BOX_PAD) ? (double)key2f(k[r]) - piv : 0.0;
         s1 += t; s2 += t * t;
     }
     s1 = wave_sum_f64(s1); s2 = wave_sum_f64(s2);
@@ -217,46 +175,6 @@ __global__ __launch_bounds__(64) void k_bkg_boxstats_list(const float* __restric
 #define BOXF_QHI 0.56f            // (0.42 / 0.58: 16 boxes of a frame's 30 976 fall back instead of 209, but 9 % slower; 0.45 / 0.55: 676)
 #endif
 #define BOXF_NT 1024
-template <int NR, int K, int J> __device__ __forceinline__ void bs_static(uint32_t (&k)[NR]) {
-#pragma unroll
-    for (int r = 0; r < NR; r++) {
-        const int q = r ^ J;
-        if (q > r) {
-            const uint32_t a = k[r], b = k[q];
-            const uint32_t lo = min(a, b), hi = max(a, b);
-            if ((r & K) == 0) { k[r] = lo; k[q] = hi; } else { k[r] = hi; k[q] = lo; }
-        }
-    }
-}
-template <int NR, int J> __device__ __forceinline__ void bs_lane(uint32_t (&k)[NR], uint32_t clo) {
-    const uint32_t chi = ~clo;
-#pragma unroll
-    for (int r = 0; r < NR; r++) {
-        const int q = r ^ J;
-        if (q > r) {
-            const uint32_t a = k[r], b = k[q];
-            k[r] = umed3(a, b, clo); k[q] = umed3(a, b, chi);
-        }
-    }
-}
-// 64 * NR keys, NR per lane, ascending: sorted position of (lane, r) is lane * NR + r
-template <int NR> __device__ __forceinline__ void bs_sort(uint32_t (&k)[NR], int lane) {
-    bs_static<NR, 2, 1>(k);
-    bs_static<NR, 4, 2>(k); bs_static<NR, 4, 1>(k);
-    if (NR >= 16) { bs_static<NR, 8, 4>(k); bs_static<NR, 8, 2>(k); bs_static<NR, 8, 1>(k); }
-    for (int ll = 0; ll <= 6; ll++) {                     // runs of NR << ll elements
-        const bool asc = (lane & (1 << ll)) == 0;
-        for (int m = (1 << ll) >> 1; m > 0; m >>= 1) {
-            const uint32_t c = (((lane & m) == 0) == asc) ? 0u : 0xffffffffu;
-#pragma unroll
-            for (int r = 0; r < NR; r++) k[r] = umed3(k[r], (uint32_t)__shfl_xor((int)k[r], m), c);
-        }
-        const uint32_t clo = asc ? 0u : 0xffffffffu;
-        if (NR >= 16) bs_lane<NR, 8>(k, clo);
-        bs_lane<NR, 4>(k, clo); bs_lane<NR, 2>(k, clo); bs_lane<NR, 1>(k, clo);
-    }
-}
-__device__ __forceinline__ uint32_t box_float_key(float f) { const uint32_t u = __float_as_uint(f); return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u); }
 __device__ __forceinline__ int box_bslot(int i) { return i + (i >> 4); }       // sorted bracket in LDS: one pad word per lane's 16
 
 #ifndef BOXF_MINW
@@ -300,7 +218,7 @@ __global__ __launch_bounds__(64, BOXF_MINW) void k_bkg_boxstats_fast(const float
             const uint32_t u = k[c];
             const float d = __uint_as_float(u);
             const bool ok = col & (mk[c] == 0) & (d != 0.f) & (d == d);
-            k[c] = ok ? (u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u)) : BOX_PAD;
+            k[c] = ok ? box_float_key(d) : BOX_PAD;
             cnt += ok;
         }
     }
@@ -327,7 +245,7 @@ __global__ __launch_bounds__(64, BOXF_MINW) void k_bkg_boxstats_fast(const float
         const int nsv = wave_sum_i32(nv);
         if (nsv < 128) BOXF_LEAVE(1);
 #ifndef BOXK_NOSAMP
-        bs_sort<8>(sm, lane);
+        wave_sort<8>(sm, lane);
 #endif
 #pragma unroll
         for (int j = 0; j < 8; j++) s_br[lane * 8 + j] = sm[j];
@@ -361,7 +279,7 @@ __global__ __launch_bounds__(64, BOXF_MINW) void k_bkg_boxstats_fast(const float
             const bool inw = (u < tl_key) || ((u - th_key - 1u) < wth);          // below the low limit, or th_key < u < BOX_PAD
             nbl += inb ? 1 : 0; ntl += inw ? 1 : 0;
             c_lo += (u < lo_key) ? 1 : 0;
-            const uint32_t xb = u ^ ((uint32_t)((int32_t)~u >> 31) | 0x80000000u);          // box_key_value
+            const uint32_t xb = u ^ ((uint32_t)((int32_t)~u >> 31) | 0x80000000u);          // box_key_value(u) = key2f(u), shaped by hand for this loop
             const float t = (inw || u == BOX_PAD) ? 0.f : __uint_as_float(xb) - pivf;
             f1 += t; f2 = fmaf(t, t, f2);
         }
@@ -409,7 +327,7 @@ __global__ __launch_bounds__(64, BOXF_MINW) void k_bkg_boxstats_fast(const float
         for (int r = 0; r < 8; r++) kb[r] = (r * 64 + lane < nb) ? s_br[r * 64 + lane] : BOX_PAD;
         __syncthreads();
 #ifndef BOXK_NOBR
-        bs_sort<8>(kb, lane);
+        wave_sort<8>(kb, lane);
 #endif
 #pragma unroll
         for (int r = 0; r < 8; r++) s_br[box_bslot(lane * 8 + r)] = kb[r];
@@ -420,7 +338,7 @@ __global__ __launch_bounds__(64, BOXF_MINW) void k_bkg_boxstats_fast(const float
         for (int r = 0; r < 16; r++) kb[r] = (r * 64 + lane < nb) ? s_br[r * 64 + lane] : BOX_PAD;
         __syncthreads();
 #ifndef BOXK_NOBR
-        bs_sort<16>(kb, lane);
+        wave_sort<16>(kb, lane);
 #endif
 #pragma unroll
         for (int r = 0; r < 16; r++) s_br[lane * 17 + r] = kb[r];
@@ -604,7 +522,7 @@ __global__ __launch_bounds__(1024) void k_mini_median_regs(const float* __restri
 #pragma unroll
     for (int r = 0; r < 32; r++) {
         k[r] = 0xffffffffu;
-        if (r < nk) { const float v = a[tid + 1024 * r]; nan |= !(v == v); const unsigned u = __float_as_uint(v); k[r] = (u >> 31) ? ~u : (u | 0x80000000u); }
+        if (r < nk) { const float v = a[tid + 1024 * r]; nan |= !(v == v); k[r] = f2key(v); }
     }
     if (tid == 0) s_nan = 0;
     __syncthreads();
@@ -636,7 +554,7 @@ __global__ __launch_bounds__(1024) void k_mini_median_regs(const float* __restri
         }
     }
     if (tid == 0) {
-        const float v1 = __uint_as_float((ans >> 31) ? (ans & 0x7fffffffu) : ~ans), v2 = __uint_as_float((ans2 >> 31) ? (ans2 & 0x7fffffffu) : ~ans2);
+        const float v1 = key2f(ans), v2 = key2f(ans2);
         out[0] = (n & 1) ? v1 : (v1 + v2) * 0.5f;
     }
 }
@@ -660,8 +578,7 @@ __global__ __launch_bounds__(1024) void k_mini_median(const float* __restrict__ 
             __syncthreads();
             const unsigned pre = s_prefix;
             for (int i = tid; i < n; i += 1024) {
-                const unsigned u = __float_as_uint(a[i]);
-                const unsigned k = (u >> 31) ? ~u : (u | 0x80000000u);
+                const unsigned k = f2key(a[i]);
                 if (shift == 24 || (k >> (shift + 8)) == (pre >> (shift + 8))) atomicAdd(&hist[(k >> shift) & 255u], 1u);
             }
             __syncthreads();
@@ -672,7 +589,7 @@ __global__ __launch_bounds__(1024) void k_mini_median(const float* __restrict__ 
             }
             __syncthreads();
         }
-        if (tid == 0) { const unsigned k = s_prefix; s_val[which] = __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
+        if (tid == 0) s_val[which] = key2f(s_prefix);
         __syncthreads();
     }
     if (tid == 0) out[0] = (n & 1) ? s_val[0] : (s_val[0] + s_val[1]) * 0.5f;

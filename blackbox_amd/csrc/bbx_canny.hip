@@ -34,12 +34,6 @@ struct canny_par {
     int radius;
 };
 
-__device__ __forceinline__ unsigned fkey(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
 __global__ void k_canny_init(canny_par* p, size_t n, double q1, double q2, const double* __restrict__ w, int radius, unsigned* hist) {
     const int t = threadIdx.x;
     for (int i = t; i < 4 * 4096; i += blockDim.x) hist[i] = 0;
@@ -69,7 +63,7 @@ __global__ __launch_bounds__(256) void k_canny_hist(const float* __restrict__ b,
     const size_t n4 = n >> 2, stride = (size_t)gridDim.x * blockDim.x;
     const float4* b4 = (const float4*)b;
     auto count = [&](float f) {
-        const unsigned k = fkey(f);
+        const unsigned k = f2key(f);
         if (PASS == 0) {
             // the top 12 key bits of a sky frame fall into two or three bins: 64 lanes adding to one LDS word queue up one
             // after the other (this pass took 60 us for 111 MB).  Up to two rounds in which the bin of the first pending lane
@@ -144,7 +138,7 @@ __global__ __launch_bounds__(256) void k_canny_scan(canny_par* p, unsigned* hist
 __global__ void k_canny_params(canny_par* p, size_t n, double q1, double q2, double low_frac, double high_frac) {
     if (threadIdx.x != 0) return;
     float os[4];
-    for (int q = 0; q < 4; q++) os[q] = fkey_inv(p->prefix[q]);
+    for (int q = 0; q < 4; q++) os[q] = key2f(p->prefix[q]);
     double pc[2];
     for (int j = 0; j < 2; j++) {
         const double v = (double)(n - 1) * (j ? q2 : q1), g = v - floor(v);

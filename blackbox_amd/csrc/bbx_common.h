@@ -175,6 +175,9 @@ struct f64x256 { double v[256]; };
 template <int CTRL> __device__ __forceinline__ int dpp_mov_i32(int v) {
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
 }
+template <int CTRL> __device__ __forceinline__ float dpp_mov_f32(float v) {
+    return __int_as_float(dpp_mov_i32<CTRL>(__float_as_int(v)));
+}
 template <int CTRL> __device__ __forceinline__ double dpp_mov_f64(double v) {
     const int lo = dpp_mov_i32<CTRL>(__double2loint(v)), hi = dpp_mov_i32<CTRL>(__double2hiint(v));
     return __hiloint2double(hi, lo);
@@ -182,6 +185,7 @@ template <int CTRL> __device__ __forceinline__ double dpp_mov_f64(double v) {
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
 }
+__device__ __forceinline__ float readlane_f32(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 #define BBX_DPP_ROR(n) (0x120 + (n))          // row_ror:n
 __device__ __forceinline__ double wave_sum_f64(double v) {
     v += dpp_mov_f64<BBX_DPP_ROR(1)>(v);
@@ -189,6 +193,13 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     v += dpp_mov_f64<BBX_DPP_ROR(4)>(v);
     v += dpp_mov_f64<BBX_DPP_ROR(8)>(v);
     return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+}
+__device__ __forceinline__ float wave_sum_f32(float v) {
+    v += dpp_mov_f32<BBX_DPP_ROR(1)>(v);
+    v += dpp_mov_f32<BBX_DPP_ROR(2)>(v);
+    v += dpp_mov_f32<BBX_DPP_ROR(4)>(v);
+    v += dpp_mov_f32<BBX_DPP_ROR(8)>(v);
+    return (readlane_f32(v, 0) + readlane_f32(v, 16)) + (readlane_f32(v, 32) + readlane_f32(v, 48));
 }
 __device__ __forceinline__ int wave_sum_i32(int v) {
     v += dpp_mov_i32<BBX_DPP_ROR(1)>(v);
@@ -202,6 +213,9 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
     // counts: two 32-bit halves would need carries; the callers' totals fit 2^53 exactly
     return (long long)wave_sum_f64((double)v);
 }
+
+// neither inf nor NaN: the exponent field is not all ones
+__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // byte-wide atomic OR through the aligned 32-bit word (little endian)
 __device__ __forceinline__ unsigned atomic_or_u8(uint8_t* base, size_t idx, unsigned bits) {
@@ -227,4 +241,78 @@ __device__ __forceinline__ uint32_t f2key(float f) {
 __device__ __forceinline__ float key2f(uint32_t k) {
     uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return __uint_as_float(u);
+}
+
+// ---- a wave sorts 64 * NR keys held NR per lane in registers, ascending: the sorted position of register r of lane l is
+// l * NR + r.  Bitonic network: a stage between registers of a lane is v_min / v_max where the element index fixes the
+// direction (wave_sort_static: levels of 2 .. NR / 2 elements) and v_med3 against a per-lane 0 / ~0 where the lane does
+// (wave_sort_lane: clo = 0 sorts ascending, med3(a, b, 0) = min; ~0 descending); a stage between lanes fetches the partner
+// through ds_bpermute (__shfl_xor).
+__device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t o;
+    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c));
+    return o;
+}
+template <int NR, int K, int J> __device__ __forceinline__ void wave_sort_static(uint32_t (&k)[NR]) {
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+        const int q = r ^ J;
+        if (q > r) {
+            const uint32_t a = k[r], b = k[q];
+            const uint32_t lo = min(a, b), hi = max(a, b);
+            if ((r & K) == 0) { k[r] = lo; k[q] = hi; } else { k[r] = hi; k[q] = lo; }
+        }
+    }
+}
+template <int NR, int J> __device__ __forceinline__ void wave_sort_lane(uint32_t (&k)[NR], uint32_t clo) {
+    const uint32_t chi = ~clo;
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+        const int q = r ^ J;
+        if (q > r) {
+            const uint32_t a = k[r], b = k[q];
+            k[r] = umed3(a, b, clo); k[q] = umed3(a, b, chi);
+        }
+    }
+}
+// the two halves of a merge level: every register against lane ^ m (keep the smaller / the larger), then the lane's own
+template <int NR> __device__ __forceinline__ void wave_sort_cross(uint32_t (&k)[NR], int lane, int m, bool asc) {
+    const uint32_t c = (((lane & m) == 0) == asc) ? 0u : 0xffffffffu;
+#pragma unroll
+    for (int r = 0; r < NR; r++) k[r] = umed3(k[r], (uint32_t)__shfl_xor((int)k[r], m), c);
+}
+template <int NR> __device__ __forceinline__ void wave_sort_own(uint32_t (&k)[NR], bool asc) {
+    const uint32_t clo = asc ? 0u : 0xffffffffu;
+    if constexpr (NR >= 64) wave_sort_lane<NR, 32>(k, clo);
+    if constexpr (NR >= 32) wave_sort_lane<NR, 16>(k, clo);
+    if constexpr (NR >= 16) wave_sort_lane<NR, 8>(k, clo);
+    wave_sort_lane<NR, 4>(k, clo); wave_sort_lane<NR, 2>(k, clo); wave_sort_lane<NR, 1>(k, clo);
+}
+// NR = 8, 16, 32, 64.  ROLLED keeps the two loops over the merge levels as loops (k_fp_tile, which is long as it is);
+// otherwise the compiler decides.  (A pragma cannot depend on a template argument: two loop nests around the same calls.)
+template <int NR, bool ROLLED = false> __device__ __forceinline__ void wave_sort(uint32_t (&k)[NR], int lane) {
+    static_assert(NR == 8 || NR == 16 || NR == 32 || NR == 64, "wave_sort: 8, 16, 32 or 64 keys per lane");
+    wave_sort_static<NR, 2, 1>(k);
+    wave_sort_static<NR, 4, 2>(k); wave_sort_static<NR, 4, 1>(k);
+    if constexpr (NR >= 16) { wave_sort_static<NR, 8, 4>(k); wave_sort_static<NR, 8, 2>(k); wave_sort_static<NR, 8, 1>(k); }
+    if constexpr (NR >= 32) { wave_sort_static<NR, 16, 8>(k); wave_sort_static<NR, 16, 4>(k); wave_sort_static<NR, 16, 2>(k); wave_sort_static<NR, 16, 1>(k); }
+    if constexpr (NR >= 64) {
+        wave_sort_static<NR, 32, 16>(k); wave_sort_static<NR, 32, 8>(k); wave_sort_static<NR, 32, 4>(k); wave_sort_static<NR, 32, 2>(k);
+        wave_sort_static<NR, 32, 1>(k);
+    }
+    if constexpr (ROLLED) {
+#pragma unroll 1
+        for (int ll = 0; ll <= 6; ll++) {                 // runs of NR << ll elements
+            const bool asc = (lane & (1 << ll)) == 0;     // ll = 6: one ascending run
+#pragma unroll 1
+            for (int m = (1 << ll) >> 1; m > 0; m >>= 1) wave_sort_cross<NR>(k, lane, m, asc);
+            wave_sort_own<NR>(k, asc);
+        }
+    } else {
+        for (int ll = 0; ll <= 6; ll++) {
+            const bool asc = (lane & (1 << ll)) == 0;
+            for (int m = (1 << ll) >> 1; m > 0; m >>= 1) wave_sort_cross<NR>(k, lane, m, asc);
+            wave_sort_own<NR>(k, asc);
+        }
+    }
 }

@@ -85,54 +85,6 @@ __device__ __forceinline__ unsigned rice_diff(const int* vals, int i) {
     return d;
 }
 
-// ---- a wave sorts 1024 keys held 16 per lane (sorted position of register r of lane l: 16 l + r): bitonic network,
-// stages between registers of a lane as v_min / v_max (v_med3 against a per-lane 0 / ~0 where the direction depends on the
-// lane), stages between lanes through ds_bpermute (the machinery of k_bkg_boxstats with 16 instead of 64 keys per lane)
-__device__ __forceinline__ uint32_t fp_umed3(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t o;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c));
-    return o;
-}
-template <int K, int J> __device__ __forceinline__ void fp_stage_static(uint32_t (&k)[16]) {
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int q = r ^ J;
-        if (q > r) {
-            const uint32_t a = k[r], b = k[q];
-            const uint32_t lo = min(a, b), hi = max(a, b);
-            if ((r & K) == 0) { k[r] = lo; k[q] = hi; } else { k[r] = hi; k[q] = lo; }
-        }
-    }
-}
-template <int J> __device__ __forceinline__ void fp_stage_lane(uint32_t (&k)[16], uint32_t clo) {
-    const uint32_t chi = ~clo;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int q = r ^ J;
-        if (q > r) {
-            const uint32_t a = k[r], b = k[q];
-            k[r] = fp_umed3(a, b, clo); k[q] = fp_umed3(a, b, chi);
-        }
-    }
-}
-__device__ __forceinline__ void fp_wave_sort1024(uint32_t (&k)[16], int lane) {
-    fp_stage_static<2, 1>(k);
-    fp_stage_static<4, 2>(k); fp_stage_static<4, 1>(k);
-    fp_stage_static<8, 4>(k); fp_stage_static<8, 2>(k); fp_stage_static<8, 1>(k);
-#pragma unroll 1
-    for (int ll = 0; ll <= 6; ll++) {                     // runs of 16 << ll elements
-        const bool asc = (lane & (1 << ll)) == 0;         // ll = 6: one ascending run
-#pragma unroll 1
-        for (int m = (1 << ll) >> 1; m > 0; m >>= 1) {
-            const uint32_t c = (((lane & m) == 0) == asc) ? 0u : 0xffffffffu;   // keep the smaller / the larger
-#pragma unroll
-            for (int r = 0; r < 16; r++) k[r] = fp_umed3(k[r], (uint32_t)__shfl_xor((int)k[r], m), c);
-        }
-        const uint32_t clo = asc ? 0u : 0xffffffffu;
-        fp_stage_lane<8>(k, clo); fp_stage_lane<4>(k, clo); fp_stage_lane<2>(k, clo); fp_stage_lane<1>(k, clo);
-    }
-}
-
 // (the result of an asm statement counts as a per-lane value: without this a population count of the mask is done in the
 // vector unit, two instructions per word and one more to add)
 __device__ __forceinline__ unsigned long long fp_uniform64(unsigned long long m) {
@@ -377,7 +329,7 @@ __global__ __launch_bounds__(FP_THREADS, MODE == 1 ? FP_MINW : 4) void k_fp_tile
                     uint32_t k[16];
 #pragma unroll
                     for (int r = 0; r < 16; r++) k[r] = samp[1024 * wave + 64 * r + lane];  // any assignment of keys to slots will do
-                    fp_wave_sort1024(k, lane);
+                    wave_sort<16, true>(k, lane);                          // (ROLLED: the merge levels stay loops)
                     // sorted[16 l + r]: the order statistics 512 - H and 512 + H
                     constexpr int A = FP_NSAMP / 2 - FP_SAMP_HALF, B = FP_NSAMP / 2 + FP_SAMP_HALF;
                     if (lane == A / 16) br_lo[wave] = k[A % 16];

@@ -12,7 +12,7 @@
 #define CEN_NREG      7                                  // ceil((2 * 10 + 1)^2 / 64)
 
 // ---------------------------------------------------------------------------------------------------------------------
-// windowed centroid (the wave sum: bbx_stats.h)
+// windowed centroid (the wave sum: bbx_common.h)
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MATCH_BLOCK) void k_win_centroid(int ny, int nx, const float* __restrict__ img, int nsrc,
                                                               const int32_t* __restrict__ ys, const int32_t* __restrict__ xs,
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(MATCH_BLOCK) void k_win_centroid(int ny, int nx, co
     const float inv = 1.0f / (2.0f * sg * sg);
     const float lim = 0.5f * (float)R;
     float cy = 0.f, cx = 0.f;
-    bool ok = sg > 0.f && match_finite(sg) && match_finite(inv);
+    bool ok = sg > 0.f && finite_f32(sg) && finite_f32(inv);
     for (int it = 0; it < niter && ok; it++) {                       // (ok is the same in every lane: it follows from wave sums)
         float sw = 0.f, sy = 0.f, sx = 0.f;
 #pragma unroll
@@ -48,11 +48,11 @@ __global__ __launch_bounds__(MATCH_BLOCK) void k_win_centroid(int ny, int nx, co
             sw += w; sy += w * dy; sx += w * dx;
         }
         sw = wave_sum_f32(sw); sy = wave_sum_f32(sy); sx = wave_sum_f32(sx);
-        ok = sw > 0.f && match_finite(sw) && match_finite(sy) && match_finite(sx);
+        ok = sw > 0.f && finite_f32(sw) && finite_f32(sy) && finite_f32(sx);
         if (ok) {
             cy = cy + 2.0f * (sy / sw);
             cx = cx + 2.0f * (sx / sw);
-            ok = match_finite(cy) && match_finite(cx) && fabsf(cy) <= lim && fabsf(cx) <= lim;
+            ok = finite_f32(cy) && finite_f32(cx) && fabsf(cy) <= lim && fabsf(cx) <= lim;
         }
     }
     if (lane == 0) {

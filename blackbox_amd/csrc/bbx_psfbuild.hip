@@ -35,7 +35,7 @@ __global__ __launch_bounds__(PSB_BLOCK) void k_psf_reason(psf_sel_in in, uint8_t
     const float* sh = in.shapes + 8 * (size_t)i;
     bool fin = true;
 #pragma unroll
-    for (int k = 0; k < 8; k++) fin = fin && match_finite(sh[k]);
+    for (int k = 0; k < 8; k++) fin = fin && finite_f32(sh[k]);
     const float pk = in.pk[i];
     const float fmed = in.d_fwhm_med ? (float)in.d_fwhm_med[0] : in.fwhm_med;
     const int y = in.ys[i], x = in.xs[i], h = in.V / 2, m = h + 3;
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(PSB_BLOCK) void k_psf_stamps(int ny, int nx, const 
     if (live) {
         const float cy = shapes[8 * (size_t)src], cx = shapes[8 * (size_t)src + 1];
         sg = sig[src];
-        live = match_finite(cy) && match_finite(cx) && fabsf(cy) <= 16.f && fabsf(cx) <= 16.f && match_finite(sg);
+        live = finite_f32(cy) && finite_f32(cx) && fabsf(cy) <= 16.f && fabsf(cx) <= 16.f && finite_f32(sg);
         if (live) {
             const float ly = floorf(cy), lx = floorf(cx);
             fy = cy - ly; fx = cx - lx;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(PSB_BLOCK) void k_psf_stamps(int ny, int nx, const 
             if (y < 0 || y >= ny || x < 0 || x >= nx) bad = 1;
             else {
                 v = img[(size_t)y * nx + x];
-                if (!match_finite(v)) bad = 1;
+                if (!finite_f32(v)) bad = 1;
                 if (mask && a >= 2 && a < V + 2 && b >= 2 && b < V + 2 && mask[(size_t)y * nx + x]) bad = 1;
             }
             s_win[k] = v;

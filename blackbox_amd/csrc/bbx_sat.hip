@@ -45,8 +45,6 @@ struct sat_state {
 #define SAT_SUBW 200
 struct sat_rect { int r0, r1, c0, c1; };
 
-__device__ __forceinline__ unsigned fkey(float f) { const unsigned u = __float_as_uint(f); return (u >> 31) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float fkey_inv(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
 
 // 2 x 2 sums (blackbox.py:4171-4172)
 __global__ __launch_bounds__(256) void k_bin2(const float* __restrict__ d, int nyb, int nxb, float* __restrict__ b) {
@@ -68,9 +66,9 @@ __global__ __launch_bounds__(256) void k_bin_minmax(const float* __restrict__ b,
         const float4 q = b4[i];
         const float f[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-        for (int u = 0; u < 4; u++) if (isfinite(f[u])) { const unsigned k = fkey(f[u]); hi = k > hi ? k : hi; lo = k < lo ? k : lo; }
+        for (int u = 0; u < 4; u++) if (isfinite(f[u])) { const unsigned k = f2key(f[u]); hi = k > hi ? k : hi; lo = k < lo ? k : lo; }
     }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float f = b[(n4 << 2) + threadIdx.x]; if (isfinite(f)) { const unsigned k = fkey(f); hi = k > hi ? k : hi; lo = k < lo ? k : lo; } }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float f = b[(n4 << 2) + threadIdx.x]; if (isfinite(f)) { const unsigned k = f2key(f); hi = k > hi ? k : hi; lo = k < lo ? k : lo; } }
     for (int o = 32; o > 0; o >>= 1) { const unsigned a = __shfl_xor(hi, o, 64), c = __shfl_xor(lo, o, 64); hi = a > hi ? a : hi; lo = c < lo ? c : lo; }
     __shared__ unsigned shi[4], slo[4];
     if ((threadIdx.x & 63) == 0) { shi[threadIdx.x >> 6] = hi; slo[threadIdx.x >> 6] = lo; }
@@ -318,7 +316,7 @@ __global__ __launch_bounds__(1024) void k_trail_segment(const uint32_t* __restri
     st->seg[0] = x0; st->seg[1] = y0; st->seg[2] = x1; st->seg[3] = y1;
     if (x0 == x1 && y0 == y1) { st->accept = 0; return; }
     // geometry of make_mask
-    const float top = fkey_inv(st->bmax_key), bmin = fkey_inv(st->bmin_key);
+    const float top = key2f(st->bmax_key), bmin = key2f(st->bmin_key);
     if (!(top > 0.f)) { st->accept = 0; return; }                           // "Image has no positive values"
     float lof = bmin / top; if (lof < 0.f) lof = 0.f;
     st->top = (double)top; st->clip_lo = (double)lof; st->clip_hi = (double)(top / top);
@@ -549,7 +547,7 @@ __global__ __launch_bounds__(256) void k_sat_paint(uint8_t* mask, int nyb, int n
 
 __global__ void k_sat_info(const sat_state* __restrict__ st, float* info) {
     if (threadIdx.x == 0) {
-        info[0] = fkey_inv(st->bmax_key); info[1] = fkey_inv(st->bmin_key); info[2] = (float)st->votes; info[3] = (float)st->k;
+        info[0] = key2f(st->bmax_key); info[1] = key2f(st->bmin_key); info[2] = (float)st->votes; info[3] = (float)st->k;
         info[4] = (float)st->rho; info[5] = (float)st->nwin; info[6] = (float)st->seg_ok; info[7] = (float)st->found;
     }
 }

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(SHP_BLOCK) void k_src_shapes(int ny, int nx, const 
     float cy = off[2 * (size_t)src], cx = off[2 * (size_t)src + 1];
     float ayy = 1.0f / (sg * sg), axx = ayy, axy = 0.f;              // W^-1
     float Tyy = 0.f, Txx = 0.f, Txy = 0.f;
-    bool ok = match_finite(cy) && match_finite(cx) && sg > 0.f && match_finite(sg) && match_finite(ayy);
+    bool ok = finite_f32(cy) && finite_f32(cx) && sg > 0.f && finite_f32(sg) && finite_f32(ayy);
     for (int it = 0; it < niter && ok; it++) {                       // (ok is the same in every lane: it follows from wave sums)
         float s0 = 0.f, sy = 0.f, sx = 0.f, syy = 0.f, sxx = 0.f, sxy = 0.f;
 #pragma unroll
@@ -60,21 +60,21 @@ __global__ __launch_bounds__(SHP_BLOCK) void k_src_shapes(int ny, int nx, const 
         }
         s0 = wave_sum_f32(s0); sy = wave_sum_f32(sy); sx = wave_sum_f32(sx);
         syy = wave_sum_f32(syy); sxx = wave_sum_f32(sxx); sxy = wave_sum_f32(sxy);
-        ok = s0 > 0.f && match_finite(s0) && match_finite(sy) && match_finite(sx) && match_finite(syy) && match_finite(sxx) &&
-             match_finite(sxy);
+        ok = s0 > 0.f && finite_f32(s0) && finite_f32(sy) && finite_f32(sx) && finite_f32(syy) && finite_f32(sxx) &&
+             finite_f32(sxy);
         if (!ok) break;
         const float my = sy / s0, mx = sx / s0;
         const float Myy = syy / s0 - my * my, Mxx = sxx / s0 - mx * mx, Mxy = sxy / s0 - my * mx;
         const float dM = Myy * Mxx - Mxy * Mxy;
         cy = cy + 2.0f * my; cx = cx + 2.0f * mx;
-        ok = dM > 0.f && Myy > 0.f && match_finite(dM) && match_finite(cy) && match_finite(cx) && fabsf(cy) <= lim && fabsf(cx) <= lim;
+        ok = dM > 0.f && Myy > 0.f && finite_f32(dM) && finite_f32(cy) && finite_f32(cx) && fabsf(cy) <= lim && fabsf(cx) <= lim;
         if (!ok) break;
         const float byy = Mxx / dM - ayy, bxx = Myy / dM - axx, bxy = -Mxy / dM - axy;        // T^-1 = M^-1 - W^-1
         const float dT = byy * bxx - bxy * bxy;
-        ok = dT > 0.f && byy > 0.f && match_finite(dT);
+        ok = dT > 0.f && byy > 0.f && finite_f32(dT);
         if (!ok) break;
         Tyy = bxx / dT; Txx = byy / dT; Txy = -bxy / dT;
-        ok = match_finite(Tyy) && match_finite(Txx) && match_finite(Txy) && Tyy + Txx <= tmax;
+        ok = finite_f32(Tyy) && finite_f32(Txx) && finite_f32(Txy) && Tyy + Txx <= tmax;
         ayy = byy; axx = bxx; axy = bxy;                             // W <- T
     }
     const float tr = Tyy + Txx, df = Txx - Tyy;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(SHP_BLOCK) void k_src_shapes(int ny, int nx, const 
     const float fwhm = 2.0f * sqrtf(0.6931471805599453f * tr);
     const float elong = sqrtf(A2 / B2);
     const float theta = (0.5f * atan2f(2.0f * Txy, df)) * 57.29577951308232f;
-    ok = ok && match_finite(fwhm) && match_finite(elong) && match_finite(theta);
+    ok = ok && finite_f32(fwhm) && finite_f32(elong) && finite_f32(theta);
     if (lane == 0) {
         flags[src] = (uint8_t)wfl;                                   // (for failed sources too)
         const float nan = __builtin_nanf("");
@@ -126,7 +126,7 @@ struct shape_item {
         const int y = in.ys[i], x = in.xs[i];
         const float f = in.flux[i], e = in.err[i];
         fw = in.shapes[8 * (size_t)i + 5]; el = in.shapes[8 * (size_t)i + 6];
-        return match_finite(fw) && match_finite(el) && in.flags[i] == 0 && e > 0.f && f / e >= in.snr_min &&
+        return finite_f32(fw) && finite_f32(el) && in.flags[i] == 0 && e > 0.f && f / e >= in.snr_min &&
                y >= sg.y0 && y < sg.y1 && x >= sg.x0 && x < sg.x1;
     }
     __device__ __forceinline__ void put(int, int pos) { vals[pos] = Q == SQ_FWHM ? fw : el; }

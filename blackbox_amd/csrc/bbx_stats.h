@@ -1,27 +1,11 @@
-// bbx_stats.h -- device code shared by bbx_match.hip and bbx_shapes.hip: the float32 wave sum of the one-wave-per-source
-// window kernels, and clipped statistics of a (y, x)-sorted source list per sub-image tile and of the frame (one workgroup of
-// STATS_BLOCK threads per segment: count, strided selection in list order, LDS sort, sigma clipping on the sorted sample,
-// float64 sums in a fixed order).
+// bbx_stats.h -- device code shared by bbx_match.hip, bbx_shapes.hip and bbx_psfbuild.hip: clipped statistics of a
+// (y, x)-sorted source list per sub-image tile and of the frame (one workgroup of STATS_BLOCK threads per segment: count,
+// strided selection in list order, LDS sort, sigma clipping on the sorted sample, float64 sums in a fixed order).
 #pragma once
 #include "bbx_common.h"
 
 #define STATS_BLOCK   1024
 #define STATS_WAVES   (STATS_BLOCK / 64)
-
-// ---- one wave per source -----------------------------------------------------------------------------------------------
-template <int CTRL> __device__ __forceinline__ float dpp_mov_f32(float v) {
-    return __int_as_float(dpp_mov_i32<CTRL>(__float_as_int(v)));
-}
-__device__ __forceinline__ float readlane_f32(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-// wave sum in a fixed order (row rotations, then the four row totals in row order), the same value in every lane
-__device__ __forceinline__ float wave_sum_f32(float v) {
-    v += dpp_mov_f32<BBX_DPP_ROR(1)>(v);
-    v += dpp_mov_f32<BBX_DPP_ROR(2)>(v);
-    v += dpp_mov_f32<BBX_DPP_ROR(4)>(v);
-    v += dpp_mov_f32<BBX_DPP_ROR(8)>(v);
-    return (readlane_f32(v, 0) + readlane_f32(v, 16)) + (readlane_f32(v, 32) + readlane_f32(v, 48));
-}
-__device__ __forceinline__ bool match_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // ---- segments of a list sorted by y ------------------------------------------------------------------------------------
 __device__ __forceinline__ int match_lower_bound(const int32_t* __restrict__ ys, int n, int y) {     // first i with ys[i] >= y

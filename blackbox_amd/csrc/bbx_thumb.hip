@@ -72,7 +72,6 @@ extern "C" int bbx_thumbnails(bbx_ctx* ctx, int ny, int nx, const float* const* 
 // ---------------------------------------------------------------------------------------------------------------------
 // display planes: flipud, zscale limits (float64), scale_data (float32, three separately rounded operations)
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool thumb_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // sums of N doubles over the workgroup, the same value in every thread; wave sums by DPP, the four wave totals through LDS and
 // added in a fixed order.  red[2][3][4] is used alternately, so one barrier per call is enough.
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(THUMB_BLOCK) void k_thumb_png8(int size, const floa
     int run = 0;
     for (int b = beg; b < end; b += 64) {
         const int i = b + lane;
-        const bool fin = i < end && thumb_finite(s_px[i]);
+        const bool fin = i < end && finite_f32(s_px[i]);
         run += __popcll(__ballot(fin));
     }
     if (lane == 0) s_cnt[wave] = run;
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(THUMB_BLOCK) void k_thumb_png8(int size, const floa
     for (int b = beg; b < end; b += 64) {
         const int i = b + lane;
         const float v = i < end ? s_px[i] : __builtin_nanf("");
-        const bool fin = thumb_finite(v);
+        const bool fin = finite_f32(v);
         const unsigned long long mask = __ballot(fin);
         const int rank = run + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
         if (fin) {

@@ -68,6 +68,27 @@ def boxstats_kernels(box, full_sort):
     return ('k_bkg_boxstats_fast', 'k_bkg_boxstats_list'), 'k_bkg_boxstats_list' if box_sample_count(box) < 128 else 'k_bkg_boxstats_fast'
 
 
+def box_bracket_counts(boxpix):
+    """k_bkg_boxstats_fast on a box without unusable pixels -> (nb, nt), the keys it lists for the bracket and for the wings.
+    The sorted sample s of n keys sets the bracket's ends lo, hi (sample ranks 0.44 n and 0.56 n + 1) and the wing limits
+    (ranks 0.05 n and 0.85 n), all in float32 as the kernel computes them; the bracket holds the box's keys in [lo, hi],
+    the wing list those below the low limit or above the high one.  nb <= 512 is sorted 8 keys per lane, 512 < nb <= 1024
+    16 per lane; nb > 1024 or nt > 1024 leaves the box to the full sort"""
+    F = np.float32
+    s = np.sort(boxpix[0:64:8].ravel())
+    n = s.size
+    lo, hi = s[int(F(n) * F(0.44))], s[min(int(F(n) * F(0.56)) + 1, n - 1)]
+    tl, th = s[int(F(n) * F(0.05))], s[min(int(F(n) * F(0.85)), n - 1)]
+    return int(((boxpix >= lo) & (boxpix <= hi)).sum()), int(((boxpix < tl) | (boxpix > th)).sum())
+
+
+def wide_bracket_frame(box=60, nbx=24):
+    """one row of boxes of integer-valued pixels (sigma 2: a fifth of a box sits on the median's value), so that the bracket
+    of most boxes holds more than 512 keys"""
+    rs = np.random.RandomState(11)
+    return np.concatenate([np.round(rs.normal(300, 2.0, (box, box))) for _ in range(nbx)], axis=1).astype(np.float32)
+
+
 def prefilter_refused(nby, nbx, channels=None):
     cy, cx = (nby, nbx) if channels is None else channels
     return cy + 2 * G.NPAD > SPF_MAXLEN or cx + 2 * G.NPAD > SPF_MAXLEN
@@ -229,3 +250,11 @@ def test_median_and_box_statistics_kernels_by_size():
     assert boxstats_kernels(8, False)[1] == 'k_bkg_boxstats_list' and boxstats_kernels(60, False)[1] == 'k_bkg_boxstats_fast'
     assert boxstats_kernels(32, False)[1] == 'k_bkg_boxstats_fast' and boxstats_kernels(31, False)[1] == 'k_bkg_boxstats_list'
     assert boxstats_kernels(60, True) == (('k_bkg_boxstats',), 'k_bkg_boxstats')
+
+
+def test_wide_bracket_frame_reaches_the_16_register_bracket_sort():
+    """necessary for the path (a clip limit inside the unlisted middle may still hand a box to the full sort later)"""
+    data = wide_bracket_frame()
+    assert data.shape == (60, 1440) and box_sample_count(60) == 480
+    counts = [box_bracket_counts(data[:, 60 * b:60 * b + 60]) for b in range(24)]
+    assert sum(512 < nb <= 1024 and nt <= 1024 for nb, nt in counts) >= 12, counts

@@ -453,6 +453,39 @@ def test_box_statistics_kernels(ctx, box, nby, nbx, full_sort):
     np.testing.assert_allclose(sh[ok], std_o[ok], rtol=2e-6, atol=0)
 
 
+def test_box_statistics_wide_bracket(ctx):
+    """the 16-register bracket sort of k_bkg_boxstats_fast (a bracket of 513 to 1024 keys): 24 boxes of 60 x 60 integer-valued
+    pixels.  Medians bit for bit from the default path, from BBX_OPT_BKG_FULL_SORT and from the oracle; std to 2e-6"""
+    box, nbx = 60, 24
+    data = S.wide_bracket_frame(box, nbx)
+    counts = [S.box_bracket_counts(data[:, box * b:box * b + box]) for b in range(nbx)]
+    print('BOXVAR (nb, nt) per box:', counts)
+    assert sum(512 < nb <= 1024 and nt <= 1024 for nb, nt in counts) >= 12
+    ny, nx = data.shape
+    mask = np.zeros((ny, nx), np.uint8)
+    med_o, std_o = Z.get_back_mini(data, mask, None, box=box)
+    assert med_o.shape == (1, nbx) and not np.isnan(med_o).any()
+    t_data, t_mask = dev(ctx, data), dev(ctx, mask)
+    got = {}
+    try:
+        for full_sort in (0, 1):
+            m = torch.full((1, nbx), -1.0, dtype=torch.float32, device=ctx.device)
+            s = torch.full((1, nbx), -1.0, dtype=torch.float32, device=ctx.device)
+            check(lib.bbx_set_option(ctx.h, 8, full_sort), 'bbx_set_option', ctx.h)
+            check(lib.bbx_bkg_boxstats(ctx.h, ny, nx, box, G._p(t_data), G._p(t_mask), G._p(None), 0.5, G._p(m), G._p(s), ctx.stream()),
+                  'bbx_bkg_boxstats', ctx.h)
+            ctx.sync()
+            got[full_sort] = m.cpu().numpy(), s.cpu().numpy()
+    finally:
+        check(lib.bbx_set_option(ctx.h, 8, 0), 'bbx_set_option', ctx.h)
+    for full_sort in (0, 1):
+        mh, sh = got[full_sort]
+        print('BOXVAR full_sort=%d std max rel diff %.3e' % (full_sort, np.max(np.abs(sh - std_o) / std_o)))
+        assert np.array_equal(mh.view(np.uint32), med_o.view(np.uint32))
+        np.testing.assert_allclose(sh, std_o, rtol=2e-6, atol=1e-7)
+    assert np.array_equal(got[0][0].view(np.uint32), got[1][0].view(np.uint32))
+
+
 @pytest.mark.parametrize('n', [1, 2, 1025, 32768, 32769, 40000])
 def test_mini_median_kernels(ctx, n):
     """k_mini_median_regs up to 32768 values, k_mini_median above: np.median of float32 values, odd and even counts, ties
