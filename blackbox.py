@@ -400,6 +400,10 @@ class Reducer:
             if par(a.zogy_match, 'zogy_match'):
                 sub['match'] = True
                 sub['match_dist'] = par(a.match_dist, 'match_dist_pix')
+        if (sub['cat_extract'] or sub.get('match')) and par(a.phot_centroid, 'phot_centroid'):
+            # the PSF on the centroids wherever photometry runs (the catalogue, the star match's two lists); the keyword is only
+            # passed when switched on
+            sub['phot_centroid'] = True
         return sub
 
     def _build_ref_psf(self, sub):
@@ -1088,6 +1092,10 @@ def build_parser():
     ap.add_argument('--cat_shapes', type=str2bool, default=None,
                     help='with --cat_extract: FWHM, ELONGATION, A, B, THETA, X2, Y2, XY, FLAGS_MASK and sub-pixel X_POS / Y_POS in '
                          '_cat.fits, S-NOBJ S-FWHM S-FWSTD S-SEEING S-SEESTD S-ELONG S-ELOSTD in the header (default: settings.cat_shapes)')
+    ap.add_argument('--phot_centroid', type=str2bool, default=None,
+                    help='catalogue photometry (--cat_extract, --zogy_match) with the PSF shifted to each source\'s windowed centroid and '
+                         'masked pixels left out: FLAGS_OPT and sub-pixel X_POS / Y_POS in _cat.fits, PHOT-CEN in the header (default: '
+                         'settings.phot_centroid)')
     ap.add_argument('--force_reproc_new', type=str2bool, default=False)
     ap.add_argument('--master_date', type=str, default=None,
                     help='make the masters of this evening date yyyymmdd, or of the dates in this file (one per line, '

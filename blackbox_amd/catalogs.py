@@ -16,6 +16,9 @@ above; save_png_thumbnails writes the reference's {NUMBER}_{RED,REF,D,SCORR}.png
 
 Source shapes (settings.cat_shapes, off by default): a 'new' table that carries them is written with FWHM, ELONGATION, A, B,
 THETA, X2, Y2, XY and FLAGS_MASK (SHAPE_COLUMNS) after the seven columns above; the dummy catalogue keeps the seven.
+
+Photometry with the PSF on the centroid (settings.phot_centroid, off by default): a 'new' table that carries it is written with
+FLAGS_OPT (PHOT_COLUMNS: 1 no centroid, 2 masked pixels left out, 4 no PSF sum) after those.
 """
 import os
 import shutil
@@ -38,6 +41,8 @@ COLUMNS['ref'] = COLUMNS['new']
 SHAPE_COLUMNS = (('FWHM', np.float32, 'pix'), ('ELONGATION', np.float32, ''), ('A', np.float32, 'pix'), ('B', np.float32, 'pix'),
                  ('THETA', np.float32, 'deg'), ('X2', np.float32, 'pix2'), ('Y2', np.float32, 'pix2'), ('XY', np.float32, 'pix2'),
                  ('FLAGS_MASK', np.uint8, ''))
+# photometry with the PSF on the centroid (settings.phot_centroid; zogy.optimal_subtraction(phot_centroid=True)): likewise
+PHOT_COLUMNS = (('FLAGS_OPT', np.uint8, ''),)
 THUMBNAILS = ('RED', 'REF', 'D', 'SCORR')                     # plane order of zogy.thumbnail_stamps; blackbox.py:2701
 THUMBNAIL_COLUMNS = tuple('THUMBNAIL_' + c for c in THUMBNAILS)
 
@@ -59,6 +64,10 @@ def format_cat(table, cat_output, cat_type='new', header2add=None):
         units[name] = unit
     if cat_type != 'trans' and table is not None and SHAPE_COLUMNS[0][0] in table:
         for name, dt, unit in SHAPE_COLUMNS:
+            cols[name] = np.asarray(table[name]).astype(dt)
+            units[name] = unit
+    if cat_type != 'trans' and table is not None and PHOT_COLUMNS[0][0] in table:
+        for name, dt, unit in PHOT_COLUMNS:
             cols[name] = np.asarray(table[name]).astype(dt)
             units[name] = unit
     if cat_type == 'trans' and table is not None and THUMBNAIL_COLUMNS[0] in table:

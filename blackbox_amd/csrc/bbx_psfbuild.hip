@@ -103,37 +103,7 @@ extern "C" int bbx_psf_select(bbx_ctx* ctx, int n, const int32_t* d_ys, const in
 // ---------------------------------------------------------------------------------------------------------------------
 // vignettes
 // ---------------------------------------------------------------------------------------------------------------------
-// sum of one double per thread over a workgroup of NW waves, the same value in every thread: wave sums by DPP, the wave totals
-// through LDS, added in wave order.  red[NW]; the caller's next use of red is behind a barrier of its own
-template <int NW>
-__device__ __forceinline__ double psb_block_sum(double v, double* red) {
-    v = wave_sum_f64(v);
-    __syncthreads();                                                 // (red may still be read from the call before)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; w++) t += red[w];
-    return t;
-}
-
-// oracle/coadd.py lanczos3_taps: k(t) = sinc(t) sinc(t / 3) at t = frac - (-2 .. 3), 0 for |t| >= 3, divided by their sum in
-// float64, then float32
-__device__ __forceinline__ void psb_taps(float frac, float w[6]) {
-    const double pi = 3.141592653589793;
-    double k[6], s = 0.0;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        const double t = (double)frac - (double)(j - 2);
-        const double a = pi * t, b = pi * (t / 3.0);
-        double v = (t == 0.0 ? 1.0 : sin(a) / a) * (t == 0.0 ? 1.0 : sin(b) / b);
-        if (fabs(t) >= 3.0) v = 0.0;
-        k[j] = v; s += v;
-    }
-#pragma unroll
-    for (int j = 0; j < 6; j++) w[j] = (float)(k[j] / s);
-}
-
+// (psb_block_sum, psb_taps: bbx_common.h -- bbx_psfphot.hip shifts its stamps with the same taps)
 __global__ __launch_bounds__(PSB_BLOCK) void k_psf_stamps(int ny, int nx, const float* __restrict__ img, const uint8_t* __restrict__ mask,
                                                           int nsrc, const int32_t* __restrict__ ys, const int32_t* __restrict__ xs,
                                                           const float* __restrict__ shapes, const float* __restrict__ sig,

@@ -98,6 +98,11 @@ shape_nmin = 15                # fewer unflagged stars than this in the frame: t
 pixscale = 0.564               # [arcsec/pix] S-SEEING = S-FWHM x pixscale (finding_chart.py:502)
 # the window radius and the number of iterations are the centroid's: centroid_radius, centroid_niter
 
+# ---- catalogue photometry with the PSF placed on the windowed centroid instead of the integer peak (bbx_psf_optflux_shift,
+# DESIGN.md 4h; what zogy.get_psfoptflux does, [EXT]) ----
+# Off by default: the fluxes keep their bits, `_cat.fits` its columns.
+phot_centroid = False          # E_FLUX_OPT / E_FLUXERR_OPT / SNR_OPT with the shifted PSF, masked pixels left out, FLAGS_OPT, sub-pixel X_POS / Y_POS, PHOT-CEN
+
 # ---- PSF model from the frame's own stars (`_psf.fits`, header keys PSF-*: blackbox.py:3085-3110, set_qc.py:293-296;
 # [EXT] PSFEx in zogy: the rules of include/bbx.h here; this project's own unless a PSFEx parameter is named) ----
 # Off by default: a frame without --psf_new is processed without a PSF as before.

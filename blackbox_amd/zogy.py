@@ -433,9 +433,10 @@ class RefCatalog:
     builds = 0                                   # catalogues made so far (tests: once per run, not per frame)
 
     def __init__(self, ctx, ref, sig_ref, ref_mask, psf_ref, size, border, cat_nsigma=5.0, sigma_median=None, sub_psfs=None,
-                 max_sources=200000):
+                 max_sources=200000, phot_centroid=False):
         if ref.dim() != 2 or ref.dtype != torch.float32 or not ref.is_contiguous():
             raise ValueError('contiguous 2-D float32 reference expected')
+        self.phot_centroid = bool(phot_centroid)
         ny, nx = ref.shape
         size, border = int(size), int(border)
         nsy, nsx = ny // size, nx // size
@@ -457,7 +458,13 @@ class RefCatalog:
         ys, xs = ys[keep], xs[keep]
         self.n = int(ys.size)
         dev = ctx.device
-        if self.n:
+        if self.n and self.phot_centroid:
+            # the centroids first: the photometry places the PSF on them, as the new frame's does (both sides of a pair alike)
+            self.ys, self.xs = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
+            self.off = win_centroid(ctx, ref, self.ys, self.xs, window_sigma(sub_pr), size, nsy, nsx)
+            self.flux, self.err, _ = psf_optflux_centroid(ctx, ref, sig_ref, psf_ref, sub_pr, ys, xs, self.off, ref_mask, nsx, size,
+                                                             d_peaks=(self.ys, self.xs))
+        elif self.n:
             stamps = source_psfs(ctx, psf_ref, sub_pr, ys, xs, nsx, size)
             self.flux, self.err = psf_optflux(ctx, ref, sig_ref, stamps, ys, xs, v_is_sigma=True)
             self.ys, self.xs = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
@@ -471,10 +478,10 @@ class RefCatalog:
     def lists(self):
         return self.ys, self.xs, self.off, self.flux, self.err
 
-    def matches(self, ref, sig_ref, size, border):
-        """made of these very tensors, for this geometry?"""
+    def matches(self, ref, sig_ref, size, border, phot_centroid=False):
+        """made of these very tensors, for this geometry, with its PSFs placed the same way (phot_centroid)?"""
         return (ref is self.ref or (ref.data_ptr() == self.ref.data_ptr() and ref.shape == self.ref.shape)) and sig_ref is self.sig_ref \
-            and (ref.shape[0], ref.shape[1], int(size), int(border)) == self.geom
+            and (ref.shape[0], ref.shape[1], int(size), int(border)) == self.geom and bool(phot_centroid) == self.phot_centroid
 
 
 def match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, dist_max=None, snr_min=None, peaks_off=None):
@@ -863,6 +870,56 @@ def psf_optflux(ctx, D, V, psfs, ys, xs, v_is_sigma=False):
     return flux, err
 
 
+PHOT_NO_CENTROID, PHOT_MASKED, PHOT_NO_SUM = 1, 2, 4                # FLAGS_OPT bits (include/bbx.h, bbx_psf_optflux_shift)
+
+
+def psf_optflux_centroid(ctx, D, sigma, psf, sub_psfs, ys, xs, d_off, mask, nsx, size, d_peaks=None):
+    """bbx_psf_optflux_shift: the photometry of psf_optflux(source_psfs(...)) with every source's PSF shifted to its centroid
+    d_off [n, 2] (win_centroid: relative to the integer peak; device float32) inside the kernel -- no stamp is written.
+    psf: a PSFEx model dict (its terms at the integer peaks, as source_psfs) or anything else, and then sub_psfs [nsub, S, S],
+    of which each source takes the plane of its sub-image; sigma: the sigma frame of D or a MiniImage; mask: uint8 frame or
+    None, its pixels are left out of the sums; ys, xs: host arrays; d_peaks: (d_ys, d_xs), the same as int32 device tensors
+    where the caller has them.
+    -> device (flux float32 [n], err float32 [n], flags uint8 [n]: PHOT_NO_CENTROID | PHOT_MASKED | PHOT_NO_SUM).  No host wait"""
+    if D.dim() != 2 or D.dtype != torch.float32 or not D.is_contiguous():
+        raise ValueError('contiguous 2-D float32 frame expected')
+    ny, nx = D.shape
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (ny, nx) or not mask.is_contiguous()):
+        raise ValueError('the mask must be a contiguous uint8 frame of the image shape')
+    dev = ctx.device
+    ys, xs = np.asarray(ys), np.asarray(xs)
+    if d_peaks is not None:
+        d_ys, d_xs = d_peaks
+        if d_ys.dtype != torch.int32 or d_xs.dtype != torch.int32 or d_ys.numel() != ys.size or d_xs.numel() != xs.size:
+            raise ValueError('d_peaks: the int32 device copies of ys, xs expected')
+    else:
+        d_ys, d_xs = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
+    n = int(ys.size)
+    if d_off.dtype != torch.float32 or tuple(d_off.shape) != (n, 2) or not d_off.is_contiguous():
+        raise ValueError('contiguous float32 offsets [n, 2] expected')
+    terms = idx = None
+    if isinstance(psf, dict):
+        cube = psf['basis'].contiguous()
+        terms = torch.from_numpy(psf_poly_terms(np.asarray(xs) + 1.0, np.asarray(ys) + 1.0, psf['polzero'], psf['polscal'], psf['poldeg'])).to(dev)
+        if terms.shape[1] != cube.shape[0]:
+            raise ValueError('basis has %d planes, polynomial degree %d needs %d' % (cube.shape[0], psf['poldeg'], terms.shape[1]))
+    else:
+        cube = sub_psfs.contiguous()
+        idx = ((d_ys // int(size)) * int(nsx) + d_xs // int(size)).to(torch.int32)
+    if cube.dim() != 3 or cube.dtype != torch.float32 or cube.shape[1] != cube.shape[2]:
+        raise ValueError('float32 PSF planes [n, S, S] expected')
+    if not isinstance(sigma, MiniImage) and (sigma.dtype != torch.float32 or tuple(sigma.shape) != (ny, nx) or not sigma.is_contiguous()):
+        raise ValueError('sigma: a contiguous float32 frame of the image shape or a MiniImage expected')
+    flux = torch.empty(n, dtype=torch.float32, device=dev)
+    err = torch.empty(n, dtype=torch.float32, device=dev)
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    mini = isinstance(sigma, MiniImage)
+    check(lib.bbx_psf_optflux_shift(ctx.h, ny, nx, _p(D), None if mini else _p(sigma), sigma.ref() if mini else None,
+                                    _p(mask) if mask is not None else None, int(cube.shape[1]), int(cube.shape[0]), _p(cube), _p(terms), _p(idx),
+                                    n, _p(d_ys), _p(d_xs), _p(d_off), _p(flux), _p(err), _p(flags), ctx.stream()), 'bbx_psf_optflux_shift', ctx.h)
+    return flux, err, flags
+
+
 def psf_poly_terms(x, y, polzero, polscal, poldeg):
     """PSFEx polynomial terms of the source positions (pixel coordinates x, y; one
     polynomial group over (x, y)): x' = (x - polzero[0]) / polscal[0], same for y; order
@@ -1107,7 +1164,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          cat_extract=False, cat_nsigma=5.0, trans_extract=True, frame_stats=True, max_sources=200000,
                          zogy_gate=None, ref_bkg_std=None, sigma_frames=False, thumbnails=False, thumbnail_size=None,
                          thumbnail_pngs=False, ref_rows=None, ref_psf=None, match=False, ref_catalog=None, match_dist=None, match_nmin=None,
-                         match_snr_min=None, shapes=False, shape_snr_min=None, psf_build=False, psf_size=None, psf_poldeg=None):
+                         match_snr_min=None, shapes=False, shape_snr_min=None, psf_build=False, psf_size=None, psf_poldeg=None,
+                         phot_centroid=False):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -1157,6 +1215,12 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       PSF-NOBJ, PSF-CHI2, PSF-FWHM, PSF-SEE, PSF-SIZE, PSF-CFGS, PSF-SAMP, PSF-PLDG, PSF-FIX.  A build that fails
                       (PSF-P False): the frame goes on as one without a PSF (background products only).  With psf_new given, or
                       False: no kernel of bbx_psfbuild.hip is launched, no such keys.  psf_size, psf_poldeg: settings
+      phot_centroid : True: the catalogue photometry (cat_extract, and the star match's two lists) places every source's PSF on
+                      its windowed centroid instead of its integer peak (bbx_psf_optflux_shift in place of source_psfs +
+                      psf_optflux; the centroids are taken first and shared with shapes and match) and leaves the masked pixels
+                      of new_mask out of the sums: res['catalog'] gains FLAGS_OPT (PHOT_NO_CENTROID | PHOT_MASKED | PHOT_NO_SUM)
+                      and sub-pixel X_POS / Y_POS (peak + 1 + offset; the integer peak where there is no centroid), header_new
+                      gets PHOT-CEN.  False: no kernel of bbx_psfphot.hip is launched, no such key or column
       ref_catalog   : a RefCatalog made of the reference and of ref_bkg_std by the caller that keeps both for many frames (used
                       only where it was made of this call's very reference, sigma map and geometry; same result bit for bit)
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
@@ -1174,6 +1238,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     have_psf = psf_new is not None or build_here
     do_match = bool(match) and have_ref and have_psf and psf_ref is not None
     do_shapes = bool(shapes) and bool(cat_extract) and have_psf
+    phot_centroid = bool(phot_centroid)
 
     # ---- new frame: mesh, subtraction, sigma image, variance
     mini, mini_std = get_back(ctx, new, new_mask, bkg_boxsize=box)
@@ -1314,28 +1379,37 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             # of the few masked ones is made and thrown away)
             d_ys, d_xs = push(ctx, ys.astype(np.int64), xs.astype(np.int64))
             d_mk = new_mask[d_ys, d_xs]
-            stamps = source_psfs(ctx, psf_new, sub_pn, ys, xs, nsx, size)
-            f, e = psf_optflux(ctx, work, bstd, stamps, ys, xs, v_is_sigma=True)        # (bstd: frame or MiniImage)
-            back = [d_mk, f, e]
             peaks_off = None
-            if do_shapes:
-                # the windowed centroids once, for the shapes and for the star match; the moments and their statistics are
-                # queued behind the photometry and come back with it
+            if phot_centroid or do_shapes:
+                # the windowed centroids once: for the photometry (phot_centroid), the shapes and the star match
                 d_y32, d_x32 = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
                 sigw = window_sigma(sub_pn)
+            if phot_centroid:
                 peaks_off = (d_y32, d_x32, win_centroid(ctx, work, d_y32, d_x32, sigw, size, nsy, nsx))
+                f, e, d_pfl = psf_optflux_centroid(ctx, work, bstd, psf_new, sub_pn, ys, xs, peaks_off[2], new_mask, nsx, size, d_peaks=(d_y32, d_x32))
+            else:
+                stamps = source_psfs(ctx, psf_new, sub_pn, ys, xs, nsx, size)
+                f, e = psf_optflux(ctx, work, bstd, stamps, ys, xs, v_is_sigma=True)        # (bstd: frame or MiniImage)
+            back = [d_mk, f, e]
+            if do_shapes:
+                # the moments and their statistics are queued behind the photometry and come back with it
+                if peaks_off is None:
+                    peaks_off = (d_y32, d_x32, win_centroid(ctx, work, d_y32, d_x32, sigw, size, nsy, nsx))
                 d_shp, d_sfl = src_shapes(ctx, work, new_mask, d_y32, d_x32, peaks_off[2], sigw, size, nsy, nsx)
                 d_stab = shape_stats(ctx, d_y32, d_x32, d_shp, d_sfl, f, e, size, nsy, nsx, shape_snr_min)
             if do_match:
                 # the star match rides on the same copy back: centroids, match against the reference's catalogue (the run's,
                 # or made here) and the table of clipped statistics are queued behind the photometry
-                rc = ref_catalog if ref_catalog is not None and ref_catalog.matches(ref_side[0], ref_side[1], size, border) else \
+                rc = ref_catalog if ref_catalog is not None and ref_catalog.matches(ref_side[0], ref_side[1], size, border, phot_centroid) else \
                     RefCatalog(ctx, ref_side[0], ref_side[1], ref_mask if ref_grid is None else None, psf_ref, size, border,
-                               cat_nsigma=cat_nsigma, sigma_median=hdr_t['S-BKGSTDR'][0], sub_psfs=ref_side[3], max_sources=max_sources)
+                               cat_nsigma=cat_nsigma, sigma_median=hdr_t['S-BKGSTDR'][0], sub_psfs=ref_side[3], max_sources=max_sources,
+                               phot_centroid=phot_centroid)
                 back += match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, match_dist, match_snr_min,
                                       peaks_off=peaks_off)
             if do_shapes:
                 back += [d_shp, d_sfl, d_stab]
+            if phot_centroid:
+                back += [peaks_off[2], d_pfl]
             got = fetch(ctx, *back)
             mk, f, e = got[:3]
             if do_match:
@@ -1344,17 +1418,28 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                 res['match'] = dict(n_new=int((mk == 0).sum()), n_ref=rc.n, n_pairs=int(npairs[0]))
             ok = mk == 0
             ys, xs, pk, f, e = ys[ok], xs[ok], pk[ok], f[ok], e[ok]
+            if phot_centroid:
+                pfl, poff = got.pop()[ok], got.pop()[ok]              # (the last two: the flags, then the offsets)
             if do_shapes:
                 shp, sfl, stab = got[-3][ok], got[-2][ok], got[-1]
         else:
             f = e = np.zeros(0, np.float32)
             shp, sfl, stab = np.zeros((0, 8), np.float32), np.zeros(0, np.uint8), empty_shape_table(nsub)
+            poff, pfl = np.zeros((0, 2), np.float32), np.zeros(0, np.uint8)
         if cat_extract:
             peaks = ys
             res['catalog'] = dict(Y_POS=ys.astype(np.float32) + 1, X_POS=xs.astype(np.float32) + 1,
                                   E_FLUX_PEAK=pk.astype(np.float32), E_FLUX_OPT=f, E_FLUXERR_OPT=e,
                                   SNR_OPT=np.where(e > 0, f / np.where(e > 0, e, 1), 0).astype(np.float32))
             hdr['NOBJECTS'] = (len(peaks), 'number of objects detected')
+            if phot_centroid:
+                # positions as shape_columns forms them: peak + 1 + offset, the integer peak where there is no centroid
+                cen = ((pfl & PHOT_NO_CENTROID) == 0)[:, None]
+                o = np.where(cen, poff, np.float32(0)).astype(np.float32)
+                res['catalog'].update(Y_POS=(ys.astype(np.float32) + np.float32(1)) + o[:, 0], X_POS=(xs.astype(np.float32) + np.float32(1)) + o[:, 1],
+                                      FLAGS_OPT=pfl.astype(np.uint8))
+        if phot_centroid:
+            hdr['PHOT-CEN'] = (True, 'PSF placed on the centroids in the catalogue photometry?')
         if do_shapes:
             res['catalog'].update(shape_columns(ys, xs, shp, sfl))
             res['shapes'] = dict(table=stab, n_good=int(stab[nsub, _SC['n_fwhm']]))

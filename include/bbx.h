@@ -858,6 +858,38 @@ int bbx_psf_fit(bbx_ctx *ctx, int nstar, int V, int ncoef, const float *d_I, con
 int bbx_psf_chi2(bbx_ctx *ctx, int nstar, int V, int ncoef, const float *d_I, const float *d_w, const float *d_terms,
                  const float *d_basis, const uint8_t *d_ok, float *d_chi2, void *stream);
 
+/* ---- catalogue photometry with the PSF on the source's CENTROID (bbx_psfphot.hip): bbx_psf_optflux_sigma /
+ * _mini with the stamp formed, shifted and normalised inside the kernel -- zogy.get_psfoptflux shifts the PSF image to the
+ * source position ([EXT]: not in the reference tree; the rules below are THIS PROJECT'S OWN).  Per source s < nsrc at the
+ * integer peak (d_ys, d_xs) of the background-subtracted frame d_D[ny][nx], S odd, <= 49:
+ *  1 the stamp P[S][S]: with d_terms[nsrc][nplane] (model form, nplane = ncoef <= 64) the float32 fma chain over k of
+ *    d_terms[s][k] d_cube[k][p] in k order (bbx_psf_model's arithmetic; the terms are those of the integer peak); with
+ *    d_idx[nsrc] (plane form) the plane d_cube[d_idx[s]] of d_cube[nplane][S * S] (an index outside [0, nplane) is clamped).
+ *    Exactly one of d_terms, d_idx is given.
+ *  2 the shift to (dy, dx) = d_off[s] (bbx_win_centroid: relative to the integer peak), separable, a row pass (along x) then
+ *    a column pass: per axis l = floor(-d), frac = -d - l in float32, out[i] = sum_{t = -2..3} w_t(frac) P[i + l + t] with P = 0
+ *    outside [0, S), w = the six LANCZOS3 taps normalised to unit sum (float64, then float32: bbx_psf_stamps's, the co-add's
+ *    kernel), float32 products added in float32 in tap order.  frac == 0: the taps are (0, 0, 1, 0, 0, 0) and the pass is the
+ *    copy out[i] = P[i + l], so a zero offset leaves the stamp bit for bit.  An offset that is not finite or beyond 16 pixels
+ *    in either axis is no centroid: the stamp stays unshifted, flag 1.
+ *  3 norm = sum of the S x S pixels in float64; P / norm in float64.  A norm that is not positive and finite: flux = err =
+ *    0, flag 4.
+ *  4 num = sum P D / V, den = sum P^2 / V in float64 with V = max(D, 0) + sigma^2 in float32 (bbx_variance's), sigma from
+ *    the frame d_sigma[ny][nx] or read off the mini image sigma_mini at the pixel (bbx_psf_optflux_mini's; within 3e-7
+ *    of the frame's value) -- exactly one of the two is given.  Skipped: pixels off the frame; on the frame, in this order,
+ *    d_mask != 0 (d_mask may be NULL; flag 2), D not finite, V not positive (a NaN sigma included).  The estimator is
+ *    unbiased on any subset of the pixels.
+ *  5 d_flux[s] = num / den, d_err[s] = 1 / sqrt(den) as float32, both 0 where den is not positive; d_flags[s] u8 = 1 (no
+ *    centroid) | 2 (a masked pixel was skipped) | 4 (the stamp has no sum).
+ * Deterministic: no atomics, every sum in a fixed order (per thread over pixels tid, tid + 256, ..., then the wave, then
+ * the four waves in order), same input -> same bits.  nsrc == 0: nothing is launched.  One workgroup of 256 per source, the
+ * stamp in LDS (19.2 KB): nothing but flux, err and flags is written.                                                   */
+int bbx_psf_optflux_shift(bbx_ctx *ctx, int ny, int nx, const float *d_D, const float *d_sigma,
+                          const bbx_spline_image *sigma_mini, const uint8_t *d_mask, int S, int nplane,
+                          const float *d_cube, const float *d_terms, const int32_t *d_idx, int nsrc,
+                          const int32_t *d_ys, const int32_t *d_xs, const float *d_off, float *d_flux, float *d_err,
+                          uint8_t *d_flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
