@@ -225,6 +225,11 @@ __device__ __forceinline__ unsigned atomic_or_u8(uint8_t* base, size_t idx, unsi
     unsigned old = atomicOr(w, bits << sh);
     return (old >> sh) & 0xffu;
 }
+// ... and its counterpart: clears [bits] of one byte
+__device__ __forceinline__ void atomic_clear_u8(uint8_t* base, size_t idx, unsigned bits) {
+    size_t a = (size_t)(base + idx);
+    atomicAnd((unsigned*)(a & ~(size_t)3), ~(bits << ((unsigned)(a & 3) * 8)));
+}
 
 // raw pixel fetch: u16 or f32 -> float
 template <int RAW_T>

@@ -505,7 +505,8 @@ __device__ __forceinline__ bool good_px(const uint8_t* mask, size_t o) { return 
 // candidate list of iteration k (L+ > T is still necessary) lies within distance 5 of a CR-list
 // pixel: test the 11x11 neighbourhoods of the list instead of the whole frame.  Duplicates
 // are dropped through a bit of the flag plane; the result is a superset of what matters and
-// a subset of the dense list, so the outcome is identical.
+// a subset of the dense list, so the outcome is identical.  Every bit set here is cleared
+// again: by k_lac_unflag through the list, or on the spot when the list is full.
 #define F_QUEUED 32u
 #define SPC_CHUNK 4096
 __global__ __launch_bounds__(256) void k_lac_cand_sparse(const float* __restrict__ a, lac_par p,
@@ -533,7 +534,13 @@ __global__ __launch_bounds__(256) void k_lac_cand_sparse(const float* __restrict
         __syncthreads();
         for (unsigned k = threadIdx.x; k < qn; k += 256) {
             const unsigned pos = qbase + k;
-            if (pos < cap) cand_raw[pos] = q[k]; else atomicOr(err, BBX_DERR_LIST_OVERFLOW);
+            if (pos < cap) cand_raw[pos] = q[k];
+            else {
+                // dropped: k_lac_unflag clears the flag plane by list and will never see this pixel, so
+                // its bit is taken back here -- the plane has to be all-zero again for the next frame
+                atomicOr(err, BBX_DERR_LIST_OVERFLOW);
+                atomic_clear_u8(flags, q[k], F_QUEUED);
+            }
         }
         __syncthreads();
     }
