@@ -8,7 +8,7 @@ FITS in -> `{tel}_{yyyymmdd}_{hhmmss}_red.fits` (float32, e-), `..._mask.fits` (
 `..._red_hdr.fits`, `..._red.log`; with --cat_extract / --trans_extract the products of
 zogy.optimal_subtraction that the hot path covers (set_blackbox.py:157-164): `_red_bkg_mini`,
 `_red_bkg_std_mini`, `_red_cat` (+ `_red_cat_hdr`), `_red_D`, `_red_Scorr`, `_red_Fpsf`,
-`_red_trans` (+ `_red_trans_hdr`).  The reference image, its mask and the PSFs are explicit
+`_red_trans` (+ `_red_trans_hdr`), and with --objmask True `_red_objmask`.  The reference image, its mask and the PSFs are explicit
 inputs (--ref, --ref_mask, --psf_new, --psf_ref), like the masters (--mflat, --mbias, --bpm):
 their selection / creation (reference building, PSFEx, astrometry) is orchestration.
 `--master_date D --red_dir R --master_dir M` makes the masters of the evening date D (or of a file
@@ -390,6 +390,12 @@ class Reducer:
         if sub['cat_extract'] and par(a.cat_shapes, 'cat_shapes'):
             # source shapes of the catalogue and the frame's seeing / elongation keys; the keyword is only passed when switched on
             sub['shapes'] = True
+        if par(a.objmask, 'objmask'):
+            # object mask + second background pass, whenever the subtraction stage runs; the keywords are only passed when switched on
+            sub['objmask'] = True
+            for k in ('objmask_nsigma', 'objmask_minarea', 'objmask_grow'):
+                if getattr(a, k) is not None:
+                    sub[k] = getattr(a, k)
         if sub['ref'] is not None:
             if par(a.save_thumbnails, 'save_thumbnails'):
                 sub['thumbnails'] = True
@@ -639,6 +645,9 @@ class Reducer:
         products.small('image', base + '_bkg_mini.fits', np.asarray(res['bkg_mini_new']), bkg_hdr)
         products.small('image', base + '_bkg_std_mini.fits', np.asarray(res['bkg_std_mini_new']), bkg_hdr)
         qc_flag = qc.run_qc_check(header, self.tel, check_key_type='full')
+        if res.get('objmask') is not None:
+            # the object mask the second background pass left out (set_blackbox.py:157), written as `_mask.fits` is
+            products.image(base + '_objmask.fits', res['objmask'], {k: v for k, v in hnew.items() if k.startswith(('OBJM-', 'BKG-SIZE'))})
         if res.get('psf') is not None and res['psf']['model'] is not None:
             # the model built from the frame's own stars, in PSFEx's form: --psf_new takes it
             m = res['psf']['model']
@@ -833,7 +842,9 @@ class _ListRun:
         kw = {}
         self.source = _SerialSource(self)
         if r.args.fpack:
-            self.stage = outstage.OutputStage(r.ctx.device, 2 * geom.ysize_chan, 8 * geom.xsize_chan, nwriters=nwriters)
+            # (output slots: the images of two frames per lane, one more image per frame with the object mask)
+            nslots = 14 if r.sub is not None and r.sub.get('objmask') else 12
+            self.stage = outstage.OutputStage(r.ctx.device, 2 * geom.ysize_chan, 8 * geom.xsize_chan, nwriters=nwriters, nslots=nslots)
             kw = dict(outstage=self.stage, out_base=self.out_base, on_written=self.on_written,
                       header_hook=self.header_hook, stage_limmag=r._limmag_is_flux)
         self.pipe = pipeline.FramePipeline(r.ctx, r.tel, geom, mflat=r.mflat, mbias=r.mbias, bpm=r.bpm, xtalk_coeffs=r.xtalk,
@@ -1096,6 +1107,13 @@ def build_parser():
                     help='catalogue photometry (--cat_extract, --zogy_match) with the PSF shifted to each source\'s windowed centroid and '
                          'masked pixels left out: FLAGS_OPT and sub-pixel X_POS / Y_POS in _cat.fits, PHOT-CEN in the header (default: '
                          'settings.phot_centroid)')
+    ap.add_argument('--objmask', type=str2bool, default=None,
+                    help='subtraction stage: object mask from the first background pass, the mesh measured again without the masked '
+                         'pixels; _objmask.fits, OBJM-P OBJM-THR OBJM-MIN OBJM-GRW OBJM-NPX OBJM-NOB OBJM-FRC S-BKG1 S-BKGSD1 in the '
+                         'header (default: settings.objmask)')
+    ap.add_argument('--objmask_nsigma', type=float, default=None, help='[sigma] --objmask: detection threshold (settings.objmask_nsigma)')
+    ap.add_argument('--objmask_minarea', type=int, default=None, help='[pix] --objmask: smallest component kept (settings.objmask_minarea)')
+    ap.add_argument('--objmask_grow', type=int, default=None, help='[pix] --objmask: growth radius, 0 ... 8 (settings.objmask_grow)')
     ap.add_argument('--force_reproc_new', type=str2bool, default=False)
     ap.add_argument('--master_date', type=str, default=None,
                     help='make the masters of this evening date yyyymmdd, or of the dates in this file (one per line, '

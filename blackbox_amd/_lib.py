@@ -135,6 +135,7 @@ SIGNATURES = {
     'bbx_psf_optflux_sigma': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'bbx_find_peaks': (_i, [_vp, _i, _i, _vp, _f, _i, _vp, _vp, _vp, _vp]),
     'bbx_count_objects': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    'bbx_object_mask': (_i, [_vp, _i, _i, _vp, _vp, _i, C.c_double, _i, _i, _i, C.c_int64, _vp, _vp, _vp]),
     'bbx_thumbnails': (_i, [_vp, _i, _i, C.POINTER(_vp), _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     'bbx_thumb_png8': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     'bbx_win_centroid': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

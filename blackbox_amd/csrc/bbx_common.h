@@ -214,6 +214,22 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
     return (long long)wave_sum_f64((double)v);
 }
 
+// size[root] += 1 for every lane with [on] set, one add per distinct root and wave: neighbours in a pixel list mostly belong
+// to the same component, and an add per pixel on the few roots of large components queues up at ~11 ns each.  Called by
+// all lanes of the wave
+__device__ __forceinline__ void wave_add_per_root(bool on, uint32_t root, uint32_t* size) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long m = __builtin_amdgcn_ballot_w64(on);
+    while (m) {
+        const int leader = (int)__builtin_ctzll(m);
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)root, leader);
+        const unsigned long long same = __builtin_amdgcn_ballot_w64(on && root == r0);
+        if (lane == leader) atomicAdd(&size[r0], (unsigned)__popcll(same));
+        on = on && root != r0;
+        m &= ~same;
+    }
+}
+
 // neither inf nor NaN: the exponent field is not all ones
 __device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 

@@ -743,6 +743,8 @@ class FramePipeline:
         names['mask'] = st.submit(ctx, g, mask, base.replace('_red', '_mask') + '.fits') if base.endswith('_red') else \
             st.submit(ctx, g, mask, base + '_mask.fits')
         sub = f.sub
+        if sub is not None and sub.get('objmask') is not None:
+            names['objmask'] = st.submit(ctx, g, sub['objmask'], base + '_objmask.fits')
         if sub is not None and sub.get('D') is not None:
             for ext in ('D', 'Scorr', 'Fpsf'):
                 names[ext] = st.submit(ctx, g, sub[ext], '{}_{}.fits'.format(base, ext))

@@ -120,6 +120,16 @@ psf_accuracy = 0.01            # relative error of the model added to the pixel 
 psf_chi2_clip = 3.0            # stars with a chi^2 above this many times the median leave the fit
 psf_nclip = 2                  # rounds of that
 
+# ---- object mask and a second, object-free background pass (`_objmask.fits`, set_blackbox.py:157; SURVEY 3.5: run_sextractor
+# (2 passes, object mask) -> get_back; [EXT] SExtractor in zogy: the rules of DESIGN.md 4i here, this project's own) ----
+# Off by default: the background mesh is measured once, with sigma clipping alone, as before.
+objmask = False                # detect on the first pass's frame, mask the objects, measure the mesh again; OBJM-* S-BKG1 S-BKGSD1
+objmask_nsigma = 1.5           # a pixel is listed at this many of its box's sigma (SExtractor DETECT_THRESH)
+objmask_minarea = 5            # [pix] components with fewer listed pixels are dropped (DETECT_MINAREA)
+objmask_grow = 3               # [pix] radius of the disk every pixel of a kept component masks (0 ... 8)
+objmask_filter = True          # detection on the 3x3 pyramid-smoothed frame (SExtractor's default.conv)
+objmask_max_frac = 0.5         # a mask that covers more of the frame than this is not used: the frame keeps its first pass
+
 # calibration files of a reduction (explicit paths; the date-based master selection
 # of master_prep, blackbox.py:4625-4905, is blackbox_amd.masters, run by --master_date)
 bad_pixel_mask = None      # path containing 'bpm' -> 'bpm_{filt}' (blackbox.py:4386)

@@ -43,6 +43,87 @@ def get_back(ctx, data, data_mask, objmask=None, bkg_boxsize=None, limfrac=0.5):
     return med, std
 
 
+def object_mask_enqueue(ctx, img, sig_mini, box, nsigma=None, minarea=None, grow=None, filter=None, max_pixels=None):
+    """queue bbx_object_mask -> (objmask, d_counts): device uint8 [ny, nx] and device int32 [3] (pixels listed, components
+    kept, pixels set); no host wait.  The defaults are the settings'"""
+    nsigma = settings.objmask_nsigma if nsigma is None else nsigma
+    minarea = settings.objmask_minarea if minarea is None else minarea
+    grow = settings.objmask_grow if grow is None else grow
+    filter = settings.objmask_filter if filter is None else filter
+    if img.dim() != 2 or img.dtype != torch.float32 or not img.is_contiguous():
+        raise ValueError('contiguous 2-D float32 frame expected')
+    ny, nx = img.shape
+    box = int(box)
+    if box < 1 or ny % box or nx % box or tuple(sig_mini.shape) != (ny // box, nx // box):
+        raise ValueError('sigma mini image of {} x {} boxes of {} px expected'.format(ny // max(box, 1), nx // max(box, 1), box))
+    if not (float(nsigma) > 0) or int(minarea) < 1 or not 0 <= int(grow) <= 8:
+        raise ValueError('object mask: nsigma > 0, minarea >= 1 and 0 <= grow <= 8 expected')
+    sig = sig_mini if torch.is_tensor(sig_mini) else push(ctx, np.ascontiguousarray(sig_mini, np.float32))
+    if sig.dtype != torch.float32 or not sig.is_contiguous():
+        sig = sig.to(torch.float32).contiguous()
+    objmask = torch.empty((ny, nx), dtype=torch.uint8, device=ctx.device)
+    d_counts = torch.empty(3, dtype=torch.int32, device=ctx.device)
+    check(lib.bbx_object_mask(ctx.h, ny, nx, _p(img), _p(sig), box, float(nsigma), int(minarea), int(grow), int(bool(filter)),
+                              int(max_pixels or 0), _p(objmask), _p(d_counts), ctx.stream()), 'bbx_object_mask', ctx.h)
+    return objmask, d_counts
+
+
+def _objmask_counts(c, npix):
+    return dict(n_listed=int(c[0]), n_objects=int(c[1]), n_masked=int(c[2]), frac=int(c[2]) / float(npix))
+
+
+def object_mask(ctx, img, sig_mini, box, nsigma=None, minarea=None, grow=None, filter=None, max_pixels=None):
+    """Object mask of a background-subtracted frame: the pixels of the 3x3-smoothed frame [img] at or above
+    nsigma x the sigma of their box ([sig_mini]: the filled and filtered sigma mini image of get_back), their 8-connected
+    components of at least [minarea] pixels, each pixel of those grown by a disk of radius [grow]
+    -> (objmask: device uint8 [ny, nx], 1 = object; counts: dict(n_listed, n_objects, n_masked, frac)).
+    One host wait, which also reads the context's device error word: more listed pixels than [max_pixels] (default:
+    max(npix / 8, min(npix, 65536))) raise BBXError (BBX_ERR_OVERFLOW) here"""
+    objmask, d_counts = object_mask_enqueue(ctx, img, sig_mini, box, nsigma, minarea, grow, filter, max_pixels)
+    return objmask, _objmask_counts(fetch(ctx, d_counts, check_device_errors=True), img.numel())
+
+
+def _objmask_stage(ctx, new, new_mask, work, mini, mini_std, box, nsigma=None, minarea=None, grow=None, max_frac=None):
+    """the object-mask stage of optimal_subtraction: [work] holds the first pass's background-subtracted frame, (mini, mini_std)
+    that pass's mesh.  -> dict(header, objmask, mini, mini_std, bkg_mini_pass1, bkg_std_mini_pass1); objmask None: the frame
+    keeps its first pass (list overflow, an exception, a mask over more than max_frac of the frame; one log line says which).
+    One host wait: the counters, the device error word and the first pass's mini images come back together.  [work] is not written"""
+    import logging
+    log = logging.getLogger(__name__)
+    nsigma = float(settings.objmask_nsigma if nsigma is None else nsigma)
+    minarea = int(settings.objmask_minarea if minarea is None else minarea)
+    grow = int(settings.objmask_grow if grow is None else grow)
+    max_frac = float(settings.objmask_max_frac if max_frac is None else max_frac)
+    hdr = {'OBJM-P': (False, 'object mask made and used for the background?'),
+           'OBJM-THR': (nsigma, '[sigma] object mask detection threshold'),
+           'OBJM-MIN': (minarea, '[pix] object mask minimum area'),
+           'OBJM-GRW': (grow, '[pix] object mask growth radius'),
+           'OBJM-NPX': ('None', 'number of pixels above the threshold'),
+           'OBJM-NOB': ('None', 'number of objects in the object mask'),
+           'OBJM-FRC': ('None', 'fraction of the frame in the object mask'),
+           'S-BKG1': ('None', '[e-] median background, first pass'),
+           'S-BKGSD1': ('None', '[e-] sigma (STD) background, first pass')}
+    out = dict(header=hdr, objmask=None)
+    try:
+        om, d_counts = object_mask_enqueue(ctx, work, mini_std, box, nsigma, minarea, grow)
+        c, m1, s1 = fetch(ctx, d_counts, mini, mini_std, check_device_errors=True)
+        counts = _objmask_counts(c, work.numel())
+        hdr['OBJM-NPX'] = (counts['n_listed'],) + hdr['OBJM-NPX'][1:]
+        hdr['OBJM-NOB'] = (counts['n_objects'],) + hdr['OBJM-NOB'][1:]
+        hdr['OBJM-FRC'] = (counts['frac'],) + hdr['OBJM-FRC'][1:]
+        hdr['S-BKG1'] = (float(np.median(m1)),) + hdr['S-BKG1'][1:]
+        hdr['S-BKGSD1'] = (float(np.median(s1)),) + hdr['S-BKGSD1'][1:]
+        if counts['frac'] > max_frac:
+            log.warning('object mask covers %.3f of the frame, more than %.3f: the frame keeps its first background pass', counts['frac'], max_frac)
+            return out
+        mini2, std2 = get_back(ctx, new, new_mask, om, bkg_boxsize=box)
+        out.update(objmask=om, mini=mini2, mini_std=std2, bkg_mini_pass1=m1, bkg_std_mini_pass1=s1)
+        hdr['OBJM-P'] = (True,) + hdr['OBJM-P'][1:]
+    except Exception as e:
+        log.warning('object mask failed (%s): the frame keeps its first background pass', e)
+    return out
+
+
 def _bspline_weights(t):
     return np.stack([(1 - t) ** 3 / 6, (3 * t ** 3 - 6 * t ** 2 + 4) / 6, (-3 * t ** 3 + 3 * t ** 2 + 3 * t + 1) / 6,
                      t ** 3 / 6], -1)
@@ -1165,7 +1246,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          zogy_gate=None, ref_bkg_std=None, sigma_frames=False, thumbnails=False, thumbnail_size=None,
                          thumbnail_pngs=False, ref_rows=None, ref_psf=None, match=False, ref_catalog=None, match_dist=None, match_nmin=None,
                          match_snr_min=None, shapes=False, shape_snr_min=None, psf_build=False, psf_size=None, psf_poldeg=None,
-                         phot_centroid=False):
+                         phot_centroid=False, objmask=False, objmask_nsigma=None, objmask_minarea=None, objmask_grow=None,
+                         objmask_max_frac=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -1221,6 +1303,15 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       of new_mask out of the sums: res['catalog'] gains FLAGS_OPT (PHOT_NO_CENTROID | PHOT_MASKED | PHOT_NO_SUM)
                       and sub-pixel X_POS / Y_POS (peak + 1 + offset; the integer peak where there is no centroid), header_new
                       gets PHOT-CEN.  False: no kernel of bbx_psfphot.hip is launched, no such key or column
+      objmask       : True: the new frame's background mesh is measured twice: the first pass's background-subtracted frame
+                      gives the object mask (object_mask; objmask_nsigma, objmask_minarea, objmask_grow: settings), the second pass
+                      leaves the masked pixels out, and everything from there on (S-BKG, S-BKGSTD, the sigma image, the catalogue,
+                      the PSF build, the match, the subtraction) rests on the second pass.  res['objmask'] (device uint8),
+                      res['bkg_mini_pass1'], res['bkg_std_mini_pass1']; header_new gets OBJM-P, OBJM-THR, OBJM-MIN, OBJM-GRW,
+                      OBJM-NPX, OBJM-NOB, OBJM-FRC, S-BKG1, S-BKGSD1.  One more host wait.  A pixel list that overflows, an
+                      exception in the stage or a mask over more than objmask_max_frac (settings) of the frame: the frame goes
+                      on with its first pass, OBJM-P False, no res['objmask'].  False: no kernel of bbx_objmask.hip is
+                      launched, no such keys
       ref_catalog   : a RefCatalog made of the reference and of ref_bkg_std by the caller that keeps both for many frames (used
                       only where it was made of this call's very reference, sigma map and geometry; same result bit for bit)
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
@@ -1245,13 +1336,26 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     work = torch.empty_like(new)
     want_phot = cat_extract or do_match
     want_cat = (want_phot or (build_here and have_ref)) and have_psf
-    if want_cat:
+    second_pass = False
+    if objmask:
+        # the first pass's frame (no candidate list: it is not the frame the catalogue is searched on), the object mask made of
+        # it, and -- when the mask is usable -- the mesh once more without the masked pixels
+        mini2back(ctx, mini, (ny, nx), bkg_boxsize=box, interp_Xchan=True, subtract_from=new, subtract_into=work)
+        om = _objmask_stage(ctx, new, new_mask, work, mini, mini_std, box, objmask_nsigma, objmask_minarea, objmask_grow, objmask_max_frac)
+        hdr.update(om['header'])
+        if om['objmask'] is not None:
+            second_pass = True
+            mini, mini_std = om['mini'], om['mini_std']
+            res['objmask'], res['bkg_mini_pass1'], res['bkg_std_mini_pass1'] = om['objmask'], om['bkg_mini_pass1'], om['bkg_std_mini_pass1']
+    if want_cat and (second_pass or not objmask):
         # the kernel that writes the background-subtracted frame lists the pixels above cat_nsigma x S-BKGSTD for the
         # catalogue's peak search; S-BKGSTD = median of the sigma mini image, taken on the device for that
+        # (a frame that fell back to its first pass has that frame already: bbx_find_peaks makes its own pass)
         d_sstd = torch.empty(1, dtype=torch.float32, device=ctx.device)
         check(lib.bbx_mini_median(ctx.h, mini_std.numel(), _p(mini_std), _p(d_sstd), ctx.stream()), 'bbx_mini_median', ctx.h)
         check(lib.bbx_zoom_candidates(ctx.h, _p(d_sstd), float(cat_nsigma)), 'bbx_zoom_candidates', ctx.h)
-    mini2back(ctx, mini, (ny, nx), bkg_boxsize=box, interp_Xchan=True, subtract_from=new, subtract_into=work)
+    if second_pass or not objmask:
+        mini2back(ctx, mini, (ny, nx), bkg_boxsize=box, interp_Xchan=True, subtract_from=new, subtract_into=work)
     # the sigma image of the new frame: read off its mini image by the kernels that need it (catalogue photometry, the cut
     # into sub-images) where the geometry allows, a frame otherwise
     import os

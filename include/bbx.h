@@ -689,6 +689,22 @@ int bbx_find_peaks(bbx_ctx *ctx, int ny, int nx, const float *d_img, float thr, 
 int bbx_count_objects(bbx_ctx *ctx, int ny, int nx, const uint8_t *d_mask,
                       int bit, int32_t *d_count, void *stream);
 
+/* ---- object mask of a background-subtracted frame (zogy's `_objmask` product, whose SExtractor rules
+ * are [EXT]: the rules here are THIS PROJECT'S OWN).  d_img[ny][nx] f32: the frame minus its first-pass background;
+ * d_sig_mini[ny/box][nx/box] f32: that pass's sigma mini image (box divides ny and nx).
+ *   detection image: filter != 0: the 3x3 pyramid (1 2 1 / 2 4 2 / 1 2 1) / 16 with the frame's edge replicated, in float32 as
+ *     (((nw+ne)+(sw+se)) + 2((n+s)+(w+e)) + 4c) * 0.0625; filter == 0: the pixel itself
+ *   a pixel is listed iff thr = (float)nsigma * sigma[y/box][x/box] > 0 and thr <= filt < inf (a NaN or non-positive sigma lists
+ *     nothing in its box, a NaN or an infinity under the 3x3 nothing there); no mask is consulted
+ *   8-connected components of the listed pixels with fewer than minarea pixels are dropped
+ *   d_objmask[ny][nx] u8 = 1 within dy^2 + dx^2 <= grow^2 (0 <= grow <= 8) of a pixel of a component that stays, 0 elsewhere
+ * d_counts[3] i32: pixels listed, components kept, pixels set.  The pixel list holds max_pixels entries (<= 0: max(npix / 8,
+ * min(npix, 65536))); more listed pixels raise the device's list-overflow flag (bbx_sync: BBX_ERR_OVERFLOW) and the mask
+ * is then that of the pixels that fit: not to be used. */
+int bbx_object_mask(bbx_ctx *ctx, int ny, int nx, const float *d_img, const float *d_sig_mini, int box,
+                    double nsigma, int minarea, int grow, int filter, int64_t max_pixels,
+                    uint8_t *d_objmask, int32_t *d_counts, void *stream);
+
 /* ---- a17: transient thumbnails (THUMBNAIL_RED / _REF / _D / _SCORR of the transient catalogue, qc.py:480-485;
  * [EXT] zogy.get_trans cuts them) and FLAGS_MASK.  d_img: HOST array of the four device frames [ny][nx] f32 in the
  * order RED (background-subtracted new frame), REF (background-subtracted reference on the new frame's grid), D,
