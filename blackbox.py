@@ -406,6 +406,14 @@ class Reducer:
             if par(a.zogy_match, 'zogy_match'):
                 sub['match'] = True
                 sub['match_dist'] = par(a.match_dist, 'match_dist_pix')
+            # the PSF of D fitted to every transient candidate; the keywords are only passed when switched on
+            if par(a.trans_psffit, 'trans_psffit'):
+                sub['trans_psffit'] = True
+                if a.trans_fit_size is not None:
+                    sub['trans_fit_size'] = a.trans_fit_size
+                chi2_max = par(a.trans_chi2_max, 'trans_chi2_max')
+                if chi2_max is not None:
+                    sub['trans_chi2_max'] = chi2_max
         if (sub['cat_extract'] or sub.get('match')) and par(a.phot_centroid, 'phot_centroid'):
             # the PSF on the centroids wherever photometry runs (the catalogue, the star match's two lists); the keyword is only
             # passed when switched on
@@ -1103,6 +1111,13 @@ def build_parser():
     ap.add_argument('--cat_shapes', type=str2bool, default=None,
                     help='with --cat_extract: FWHM, ELONGATION, A, B, THETA, X2, Y2, XY, FLAGS_MASK and sub-pixel X_POS / Y_POS in '
                          '_cat.fits, S-NOBJ S-FWHM S-FWSTD S-SEEING S-SEESTD S-ELONG S-ELOSTD in the header (default: settings.cat_shapes)')
+    ap.add_argument('--trans_psffit', type=str2bool, default=None,
+                    help='fit the PSF of D to D at every transient candidate: X_PSF_D Y_PSF_D E_FLUX_PSF_D E_FLUXERR_PSF_D CHI2_PSF_D '
+                         'FLAGS_PSF_D in `_trans.fits`, T-PSFD T-FITSZ T-NFIT T-PDFOLD T-CHI2MD in its header (default: '
+                         'settings.trans_psffit)')
+    ap.add_argument('--trans_fit_size', type=int, default=None, help='[pix] side of the window of that fit (default: settings.trans_fit_size)')
+    ap.add_argument('--trans_chi2_max', type=float, default=None,
+                    help='drop the candidates without a fit or with CHI2_PSF_D above this, T-NVET (default: settings.trans_chi2_max)')
     ap.add_argument('--phot_centroid', type=str2bool, default=None,
                     help='catalogue photometry (--cat_extract, --zogy_match) with the PSF shifted to each source\'s windowed centroid and '
                          'masked pixels left out: FLAGS_OPT and sub-pixel X_POS / Y_POS in _cat.fits, PHOT-CEN in the header (default: '

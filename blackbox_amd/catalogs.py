@@ -43,6 +43,10 @@ SHAPE_COLUMNS = (('FWHM', np.float32, 'pix'), ('ELONGATION', np.float32, ''), ('
                  ('FLAGS_MASK', np.uint8, ''))
 # photometry with the PSF on the centroid (settings.phot_centroid; zogy.optimal_subtraction(phot_centroid=True)): likewise
 PHOT_COLUMNS = (('FLAGS_OPT', np.uint8, ''),)
+# the fit of P_D to D at every transient candidate (settings.trans_psffit; zogy.optimal_subtraction(trans_psffit=True)): appended to the
+# 'trans' columns of a table that carries them
+TRANSFIT_COLUMNS = (('X_PSF_D', np.float32, 'pix'), ('Y_PSF_D', np.float32, 'pix'), ('E_FLUX_PSF_D', np.float32, 'e-'),
+                    ('E_FLUXERR_PSF_D', np.float32, 'e-'), ('CHI2_PSF_D', np.float32, ''), ('FLAGS_PSF_D', np.uint8, ''))
 THUMBNAILS = ('RED', 'REF', 'D', 'SCORR')                     # plane order of zogy.thumbnail_stamps; blackbox.py:2701
 THUMBNAIL_COLUMNS = tuple('THUMBNAIL_' + c for c in THUMBNAILS)
 
@@ -68,6 +72,10 @@ def format_cat(table, cat_output, cat_type='new', header2add=None):
             units[name] = unit
     if cat_type != 'trans' and table is not None and PHOT_COLUMNS[0][0] in table:
         for name, dt, unit in PHOT_COLUMNS:
+            cols[name] = np.asarray(table[name]).astype(dt)
+            units[name] = unit
+    if cat_type == 'trans' and table is not None and TRANSFIT_COLUMNS[0][0] in table:
+        for name, dt, unit in TRANSFIT_COLUMNS:
             cols[name] = np.asarray(table[name]).astype(dt)
             units[name] = unit
     if cat_type == 'trans' and table is not None and THUMBNAIL_COLUMNS[0] in table:
@@ -97,10 +105,17 @@ def transient_table(transients, thumbnails=None):
 
 
 def _transient_columns(t):
-    return dict(X_PEAK=np.array([d['x'] + 1 for d in t], np.int32), Y_PEAK=np.array([d['y'] + 1 for d in t], np.int32),
-                SNR_ZOGY=np.array([d['scorr'] for d in t], np.float32),
-                E_FLUX_ZOGY=np.array([d['fpsf'] for d in t], np.float32),
-                E_FLUXERR_ZOGY=np.array([d['fpsferr'] for d in t], np.float32))
+    tab = dict(X_PEAK=np.array([d['x'] + 1 for d in t], np.int32), Y_PEAK=np.array([d['y'] + 1 for d in t], np.int32),
+               SNR_ZOGY=np.array([d['scorr'] for d in t], np.float32),
+               E_FLUX_ZOGY=np.array([d['fpsf'] for d in t], np.float32),
+               E_FLUXERR_ZOGY=np.array([d['fpsferr'] for d in t], np.float32))
+    if t and all('chi2_psf_d' in d for d in t):
+        # the fit of P_D to D (zogy.trans_psffit): sub-pixel FITS coordinates, 1-based
+        tab.update(X_PSF_D=np.array([d['x_psf_d'] + 1.0 for d in t], np.float32), Y_PSF_D=np.array([d['y_psf_d'] + 1.0 for d in t], np.float32),
+                   E_FLUX_PSF_D=np.array([d['flux_psf_d'] for d in t], np.float32),
+                   E_FLUXERR_PSF_D=np.array([d['fluxerr_psf_d'] for d in t], np.float32),
+                   CHI2_PSF_D=np.array([d['chi2_psf_d'] for d in t], np.float32), FLAGS_PSF_D=np.array([d['flags_psf_d'] for d in t], np.uint8))
+    return tab
 
 
 def _png_gray8(plane):

@@ -135,6 +135,7 @@ enum {
 enum {
     WS_HASH = 0, WS_CCLIST, WS_PARENT, WS_BITS_M, WS_BITS_C, WS_BITS_R, WS_TILES,
     WS_CAND, WS_FLAGS, WS_STAGE2, WS_CRLIST, WS_HIST, WS_SEL, WS_MISC, WS_STRIP, WS_HVALS, WS_CRORIG, WS_CANNY, WS_ZCAND, WS_BCAND, WS_FPHINT, WS_BOXFAIL, WS_ZSPL,
+    WS_TRANSFIT,
     WS_MAX
 };
 
@@ -338,7 +339,7 @@ template <int NR, bool ROLLED = false> __device__ __forceinline__ void wave_sort
     }
 }
 
-// ---- shared by bbx_psfbuild.hip and bbx_psfphot.hip ----
+// ---- shared by bbx_psfbuild.hip, bbx_psfphot.hip and bbx_transfit.hip ----
 // sum of one double per thread over a workgroup of NW waves, the same value in every thread: wave sums by DPP, the wave totals
 // through LDS, added in wave order.  red[NW]; the caller's next use of red is behind a barrier of its own
 template <int NW>
@@ -368,4 +369,51 @@ __device__ __forceinline__ void psb_taps(float frac, float w[6]) {
     }
 #pragma unroll
     for (int j = 0; j < 6; j++) w[j] = (float)(k[j] / s);
+}
+
+// ---- shared by bbx_psfphot.hip and bbx_transfit.hip: steps 2 and 3 of bbx_psf_optflux_shift (include/bbx.h) ----
+// one pass of the shift by d along one axis of the S x S stamp: out[i] = sum_j w[j] in[i + l + j - 2], in = 0 outside [0, S),
+// float32 products added in float32 in tap order.  frac == 0: the taps are the kernel's own limit (0, 0, 1, 0, 0, 0), applied
+// as the copy out[i] = in[i + l] that they stand for (no 0 * x, so the pixels keep their bits)
+template <bool ALONG_X, int BLOCK>
+__device__ __forceinline__ void psb_shift_pass(const float* in, float* out, int S, float d) {
+    const float nd = -d, fl = floorf(nd), frac = nd - fl;
+    const int l = (int)fl;                                           // (|d| <= 16)
+    float w[6];
+    psb_taps(frac, w);
+    for (int k = threadIdx.x; k < S * S; k += BLOCK) {
+        const int r = k / S, c = k - r * S;
+        const int pos = (ALONG_X ? c : r) + l;
+        const float* line = ALONG_X ? in + r * S : in + c;
+        const int step = ALONG_X ? 1 : S;
+        float t;
+        if (frac == 0.f)
+            t = (pos >= 0 && pos < S) ? line[pos * step] : 0.f;
+        else {
+            t = 0.f;
+#pragma unroll
+            for (int j = 0; j < 6; j++) {
+                const int q = pos + j - 2;
+                const float p = (q >= 0 && q < S) ? line[q * step] : 0.f;
+                t = j ? t + w[j] * p : w[0] * p;
+            }
+        }
+        out[k] = t;
+    }
+}
+// the stamp in a[S * S] (LDS, behind a barrier) moved by (dy, dx): the row pass (along x) into b, the column pass back into a;
+// a is ready for every thread on return
+template <int BLOCK>
+__device__ __forceinline__ void psb_shift_stamp(float* a, float* b, int S, float dy, float dx) {
+    psb_shift_pass<true, BLOCK>(a, b, S, dx);
+    __syncthreads();
+    psb_shift_pass<false, BLOCK>(b, a, S, dy);
+    __syncthreads();
+}
+// sum of the stamp's pixels in float64: per thread over pixels tid, tid + BLOCK, ..., then psb_block_sum
+template <int BLOCK>
+__device__ __forceinline__ double psb_stamp_sum(const float* a, int npx, double* red) {
+    double part = 0.0;
+    for (int k = threadIdx.x; k < npx; k += BLOCK) part += (double)a[k];
+    return psb_block_sum<BLOCK / 64>(part, red);
 }

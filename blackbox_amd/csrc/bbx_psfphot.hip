@@ -5,8 +5,8 @@
 //   k_psf_optflux_shift : one workgroup of 256 per source
 //     1 stamp   lane = stamp pixel: the PSFEx model's k-ordered float32 fmaf chain (k_psf_model's arithmetic; the basis reads
 //               coalesce, the cube of <= 64 planes stays in L2), or a copy of the plane d_idx[s] picks
-//     2 shift   LANCZOS3, separable: row pass (along x) into the second buffer, column pass back; psb_taps (bbx_common.h)
-//     3 norm    sum of the S x S pixels in float64
+//     2 shift   LANCZOS3, separable: row pass (along x) into the second buffer, column pass back (psb_shift_stamp, bbx_common.h)
+//     3 norm    sum of the S x S pixels in float64 (psb_stamp_sum)
 //     4 sums    num = sum P D / V, den = sum P^2 / V in float64, V = max(D, 0) + sigma^2 in float32 (k_variance's)
 //   Block sums: per-thread partial sums over pixels tid, tid + 256, ..., the waves' totals through LDS in wave order
 //   (psb_block_sum): no atomics, the same input gives the same bits.
@@ -24,36 +24,6 @@ struct pph_args {
     float* flux; float* err; uint8_t* flags;
     int ny, nx, S, nplane;
 };
-
-// one pass of the shift by d along one axis of the S x S stamp: out[i] = sum_j w[j] in[i + l + j - 2], in = 0 outside [0, S),
-// float32 products added in float32 in tap order.  frac == 0: the taps are the kernel's own limit (0, 0, 1, 0, 0, 0), applied
-// as the copy out[i] = in[i + l] that they stand for (no 0 * x, so the pixels keep their bits)
-template <bool ALONG_X>
-__device__ __forceinline__ void pph_pass(const float* in, float* out, int S, float d) {
-    const float nd = -d, fl = floorf(nd), frac = nd - fl;
-    const int l = (int)fl;                                           // (|d| <= 16)
-    float w[6];
-    psb_taps(frac, w);
-    for (int k = threadIdx.x; k < S * S; k += PPH_BLOCK) {
-        const int r = k / S, c = k - r * S;
-        const int pos = (ALONG_X ? c : r) + l;
-        const float* line = ALONG_X ? in + r * S : in + c;
-        const int step = ALONG_X ? 1 : S;
-        float t;
-        if (frac == 0.f)
-            t = (pos >= 0 && pos < S) ? line[pos * step] : 0.f;
-        else {
-            t = 0.f;
-#pragma unroll
-            for (int j = 0; j < 6; j++) {
-                const int q = pos + j - 2;
-                const float p = (q >= 0 && q < S) ? line[q * step] : 0.f;
-                t = j ? t + w[j] * p : w[0] * p;
-            }
-        }
-        out[k] = t;
-    }
-}
 
 template <bool MINI>
 __global__ __launch_bounds__(PPH_BLOCK) void k_psf_optflux_shift(pph_args a, bbx_spl sp) {
@@ -85,16 +55,9 @@ __global__ __launch_bounds__(PPH_BLOCK) void k_psf_optflux_shift(pph_args a, bbx
     const bool cen = finite_f32(dy) && finite_f32(dx) && fabsf(dy) <= PPH_OFFMAX && fabsf(dx) <= PPH_OFFMAX;      // (uniform)
     unsigned fl = cen ? 0u : 1u;
     __syncthreads();
-    if (cen) {
-        pph_pass<true>(s_a, s_b, S, dx);
-        __syncthreads();
-        pph_pass<false>(s_b, s_a, S, dy);
-        __syncthreads();
-    }
+    if (cen) psb_shift_stamp<PPH_BLOCK>(s_a, s_b, S, dy, dx);
     // ---- 3: unit sum
-    double part = 0.0;
-    for (int k = tid; k < npx; k += PPH_BLOCK) part += (double)s_a[k];
-    const double norm = psb_block_sum<PPH_BLOCK / 64>(part, s_red);
+    const double norm = psb_stamp_sum<PPH_BLOCK>(s_a, npx, s_red);
     const bool ok = norm > 0.0 && norm < 1.0e300;                    // (uniform: every thread holds the same norm)
     if (!ok) fl |= 4u;
     // ---- 4: the two sums

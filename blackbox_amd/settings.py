@@ -80,6 +80,16 @@ size_thumbnails = 100          # [pix] side of the square cut-outs
 thumbnails_dir = None          # PNGs go to {thumbnails_dir}/{image base name}/; None: `thumbnails/` next to the products
 trans_flags_window = 5         # [pix] side of the window around the peak whose mask values make FLAGS_MASK (this project's own)
 
+# ---- transient vetting: the PSF of D fitted to D at every candidate with free position (bbx_zogy_pd_stamps, bbx_trans_psffit,
+# DESIGN.md 4j; zogy's E_FLUX_PSF_D / X_PSF_D / Y_PSF_D / CHI2_PSF_D, [EXT]: the rules are this project's own) ----
+# Off by default: `_trans.fits` keeps its columns, `_trans_hdr.fits` its keys.
+trans_psffit = False           # X_PSF_D Y_PSF_D E_FLUX_PSF_D E_FLUXERR_PSF_D CHI2_PSF_D FLAGS_PSF_D columns, T-PSFD T-FITSZ T-NFIT T-PDFOLD T-CHI2MD keys
+trans_fit_size = 11            # [pix] side of the (square, odd) window of the fit, 3 .. PSF stamp side - 10
+trans_fit_niter = 8            # linearised steps of the position, always all of them
+trans_fit_maxshift = 2.0       # [pix] the position stays within this of the integer peak in either axis
+trans_pd_grid = 256            # side of the grid P_D is formed on, >= 4 x the PSF stamp side, even, <= 512
+trans_chi2_max = None          # rows without a fit or with CHI2_PSF_D above this are dropped (T-NVET); None: no row is dropped
+
 # ---- flux ratio and dx, dy from matched stars (buildref.py:2782-3014 get_fratio; [EXT] zogy.get_fratio_dxdy) ----
 # Off by default: the subtraction then takes the caller's fratio, dx, dy (--fratio --zogy_dx --zogy_dy) as before.
 zogy_match = False             # measure fratio, dx, dy per sub-image from the stars matched between new frame and reference

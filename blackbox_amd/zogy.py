@@ -951,6 +951,98 @@ def psf_optflux(ctx, D, V, psfs, ys, xs, v_is_sigma=False):
     return flux, err
 
 
+PD_FOLD_WARN = 0.01             # a T-PDFOLD above this is logged: P_D does not fit its stamp (Moffat pairs fold 1e-4 at most, a point / box pair 0.15)
+TRANS_AT_BOUND, TRANS_MASKED, TRANS_NO_FIT, TRANS_NOT_CONVERGED = 1, 2, 4, 8       # FLAGS_PSF_D bits (include/bbx.h, bbx_trans_psffit)
+
+
+def pd_stamps(ctx, sub_pn, sub_pr, scal, M=None):
+    """bbx_zogy_pd_stamps: the PSF of the difference image of every sub-image from its two PSF stamps [nsub, S, S] (device float32,
+    unit sum) and scal [nsub, 6] = (sn, sr, fn, fr, dx, dy) (host), on a grid of M x M (settings.trans_pd_grid)
+    -> device (pd float32 [nsub, S, S], fold float32 [nsub]: the share of sum |p| on the grid that the stamp leaves out).  No host wait"""
+    M = int(settings.trans_pd_grid if M is None else M)
+    if sub_pn.dim() != 3 or sub_pn.dtype != torch.float32 or sub_pr.dtype != torch.float32 or tuple(sub_pn.shape) != tuple(sub_pr.shape) or \
+            sub_pn.shape[1] != sub_pn.shape[2]:
+        raise ValueError('two float32 stamp tensors [nsub, S, S] of one shape expected')
+    nsub, S = int(sub_pn.shape[0]), int(sub_pn.shape[1])
+    scal = np.ascontiguousarray(scal, dtype=np.float32)
+    if scal.shape != (nsub, 6):
+        raise ValueError('scal [nsub, 6] expected')
+    sub_pn, sub_pr = sub_pn.contiguous(), sub_pr.contiguous()
+    pd = torch.empty((nsub, S, S), dtype=torch.float32, device=ctx.device)
+    fold = torch.empty(nsub, dtype=torch.float32, device=ctx.device)
+    check(lib.bbx_zogy_pd_stamps(ctx.h, nsub, S, M, _p(sub_pn), _p(sub_pr), scal.ctypes.data_as(C.POINTER(C.c_float)), _p(pd), _p(fold),
+                                 ctx.stream()), 'bbx_zogy_pd_stamps', ctx.h)
+    return pd, fold
+
+
+def trans_psffit(ctx, D, N, R, sig_n, sig_r, mask, pd, ys, xs, scal, size, nsx, fit_size=None, niter=None, maxshift=None, d_peaks=None):
+    """bbx_trans_psffit: the PSF of D (pd [nsub, S, S], pd_stamps) fitted to D with free position in a window of fit_size x fit_size
+    pixels around every candidate's integer peak (ys, xs: host arrays; d_peaks: the same as int32 device tensors where the caller
+    has them).  N, R: the background-subtracted new and reference frames; sig_n, sig_r: their sigma maps, two frames or two
+    MiniImage; mask: uint8 frame or None, its pixels are left out; scal [nsub, 6] (host); fit_size, niter, maxshift: settings.trans_fit_*
+    -> device (flux, err, dy, dx, chi2 float32 [n], flags uint8 [n]: TRANS_AT_BOUND | TRANS_MASKED | TRANS_NO_FIT |
+    TRANS_NOT_CONVERGED).  No host wait"""
+    ny, nx = D.shape
+    for f in (D, N, R):
+        if f.dim() != 2 or f.dtype != torch.float32 or not f.is_contiguous() or tuple(f.shape) != (ny, nx):
+            raise ValueError('contiguous 2-D float32 frames of one shape expected')
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (ny, nx) or not mask.is_contiguous()):
+        raise ValueError('the mask must be a contiguous uint8 frame of the image shape')
+    mini = isinstance(sig_n, MiniImage)
+    if mini != isinstance(sig_r, MiniImage):
+        raise ValueError('the two sigma maps must be of one form: two frames or two MiniImage')
+    if not mini:
+        for f in (sig_n, sig_r):
+            if f.dtype != torch.float32 or tuple(f.shape) != (ny, nx) or not f.is_contiguous():
+                raise ValueError('sigma: contiguous float32 frames of the image shape or MiniImage expected')
+    if pd.dim() != 3 or pd.dtype != torch.float32 or pd.shape[1] != pd.shape[2] or not pd.is_contiguous():
+        raise ValueError('contiguous float32 stamps [nsub, S, S] expected')
+    nsub, S = int(pd.shape[0]), int(pd.shape[1])
+    scal = np.ascontiguousarray(scal, dtype=np.float32)
+    if scal.shape != (nsub, 6):
+        raise ValueError('scal [nsub, 6] expected')
+    ys, xs = np.asarray(ys), np.asarray(xs)
+    n = int(ys.size)
+    if d_peaks is not None:
+        d_ys, d_xs = d_peaks
+        if d_ys.dtype != torch.int32 or d_xs.dtype != torch.int32 or d_ys.numel() != n or d_xs.numel() != n:
+            raise ValueError('d_peaks: the int32 device copies of ys, xs expected')
+    else:
+        d_ys, d_xs = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
+    dev = ctx.device
+    outs = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(5)] + [torch.empty(n, dtype=torch.uint8, device=dev)]
+    W = int(settings.trans_fit_size if fit_size is None else fit_size)
+    check(lib.bbx_trans_psffit(ctx.h, ny, nx, _p(D), _p(N), _p(R), None if mini else _p(sig_n), None if mini else _p(sig_r),
+                               sig_n.ref() if mini else None, sig_r.ref() if mini else None, _p(mask) if mask is not None else None, S, nsub,
+                               _p(pd), int(size), int(nsx), scal.ctypes.data_as(C.POINTER(C.c_float)), n, _p(d_ys), _p(d_xs), W,
+                               int(settings.trans_fit_niter if niter is None else niter),
+                               float(settings.trans_fit_maxshift if maxshift is None else maxshift), *[_p(o) for o in outs], ctx.stream()),
+          'bbx_trans_psffit', ctx.h)
+    return tuple(outs)
+
+
+_trans_psffit = trans_psffit                                         # (_optimal_subtraction's switch bears the name)
+
+
+def trans_fit_header(on, fit_size=None, rows=None, fold=None):
+    """the keys of `_trans_hdr.fits` for the fit of P_D to D: T-PSFD, and with it T-FITSZ, T-NFIT (rows with flags & 12 == 0),
+    T-PDFOLD (the largest fold over the sub-images), T-CHI2MD (the median chi2 of those rows; 'None' without any)"""
+    h = {'T-PSFD': (bool(on), 'PSF of D fitted to the transient candidates?')}
+    if on:
+        good = [r['chi2_psf_d'] for r in rows if not r['flags_psf_d'] & (TRANS_NO_FIT | TRANS_NOT_CONVERGED)]
+        h['T-FITSZ'] = (int(fit_size), '[pix] side of the window of the fit of P_D to D')
+        h['T-NFIT'] = (len(good), 'number of candidates with a converged fit')
+        h['T-PDFOLD'] = (float(np.max(fold)) if len(fold) else 'None', 'largest share of |P_D| outside its stamp')
+        h['T-CHI2MD'] = (float(np.median(good)) if good else 'None', 'median CHI2_PSF_D of the converged fits')
+    return h
+
+
+def vet_transients(rows, chi2_max):
+    """the rows that pass --trans_chi2_max: those with a fit (no TRANS_NO_FIT) and chi2_psf_d <= chi2_max -> (kept rows, their indices)"""
+    keep = [i for i, r in enumerate(rows) if not r['flags_psf_d'] & TRANS_NO_FIT and r['chi2_psf_d'] <= chi2_max]
+    return [rows[i] for i in keep], keep
+
+
 PHOT_NO_CENTROID, PHOT_MASKED, PHOT_NO_SUM = 1, 2, 4                # FLAGS_OPT bits (include/bbx.h, bbx_psf_optflux_shift)
 
 
@@ -1247,7 +1339,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          thumbnail_pngs=False, ref_rows=None, ref_psf=None, match=False, ref_catalog=None, match_dist=None, match_nmin=None,
                          match_snr_min=None, shapes=False, shape_snr_min=None, psf_build=False, psf_size=None, psf_poldeg=None,
                          phot_centroid=False, objmask=False, objmask_nsigma=None, objmask_minarea=None, objmask_grow=None,
-                         objmask_max_frac=None):
+                         objmask_max_frac=None, trans_psffit=False, trans_fit_size=None, trans_chi2_max=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -1314,6 +1406,13 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       launched, no such keys
       ref_catalog   : a RefCatalog made of the reference and of ref_bkg_std by the caller that keeps both for many frames (used
                       only where it was made of this call's very reference, sigma map and geometry; same result bit for bit)
+      trans_psffit  : True (with candidates and PSF stamps of one side): the PSF of D of every sub-image (pd_stamps) is fitted to D at
+                      every candidate with free position (bbx_trans_psffit; trans_fit_size: settings), queued behind the peak
+                      search with the Fpsf gather and read in the same copy back: every transient gains x_psf_d, y_psf_d (0-based,
+                      peak + offset), flux_psf_d, fluxerr_psf_d, chi2_psf_d, flags_psf_d; header_trans gets T-PSFD, T-FITSZ, T-NFIT,
+                      T-PDFOLD, T-CHI2MD (trans_fit_header).  trans_chi2_max: rows without a fit or with a chi2 above it are
+                      dropped, with their thumbnails; T-NVET = the rows kept, T-NTRANS stays.  An exception in the stage:
+                      today's table, T-PSFD False.  False: no kernel of bbx_transfit.hip is launched, no such keys
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
             header (= header_new additions), header_trans)"""
     size = subimage_size or settings.subimage_size
@@ -1639,6 +1738,20 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     if tys.size:
         d_ys, d_xs = push(ctx, tys.astype(np.int64), txs.astype(np.int64))
         d_fe = torch.stack([res['Fpsf'][d_ys, d_xs], res['Fpsferr'][d_ys, d_xs]])
+    d_tf = None
+    fit_size = int(settings.trans_fit_size if trans_fit_size is None else trans_fit_size)
+    if trans_psffit:
+        hdr_t['T-PSFD'] = trans_fit_header(False)['T-PSFD']          # until the fit has been read back
+    if trans_psffit and tys.size and sub_pn is not None and sub_pr is not None and tuple(sub_pn.shape) == tuple(sub_pr.shape):
+        try:
+            d_pd, d_fold = pd_stamps(ctx, sub_pn, sub_pr, scal)
+            fit = _trans_psffit(ctx, res['D'], res['data_bkgsub'], res['ref_bkgsub'], bstd, rbstd, new_mask, d_pd, tys, txs, scal, size, nsx,
+                                fit_size=fit_size)
+            d_tf = torch.cat([torch.stack(list(fit[:5]) + [fit[5].to(torch.float32)]).reshape(-1), d_fold])
+        except Exception as e:                                       # the frame keeps today's table
+            import logging
+            logging.getLogger(__name__).warning('fit of P_D to the transient candidates failed: %s', e)
+            d_tf = None
     if want_thumbs:
         # the cut-outs of the four frames, which are all still in HBM, and the mask flags under each peak in one pass; the
         # display planes from the cut-outs.  The reference's mask counts only where it shares the new frame's grid
@@ -1650,17 +1763,34 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                             frame_clipped_stats_enqueue(ctx, res['Fpsferr'], new_mask)])
     if d_fl is not None and not d_fl.numel():
         d_fl = None
-    back = [t for t in (d_fe, d_st, d_fl) if t is not None]
+    back = [t for t in (d_fe, d_st, d_fl, d_tf) if t is not None]
     got = (fetch(ctx, *back) if len(back) > 1 else [fetch(ctx, back[0])]) if back else []
     fe = got.pop(0) if d_fe is not None else None
     st = got.pop(0) if d_st is not None else None
     fl = got.pop(0) if d_fl is not None else None
+    tf = got.pop(0) if d_tf is not None else None
     if tys.size:
         res['transients'] = [dict(y=y, x=x, scorr=sc, fpsf=f, fpsferr=e)
                              for y, x, sc, f, e in zip(tys.tolist(), txs.tolist(), tsc.tolist(), fe[0].tolist(), fe[1].tolist())]
         if fl is not None:
             for d, v in zip(res['transients'], fl.tolist()):
                 d['flags'] = v
+        if tf is not None:
+            n = int(tys.size)
+            cols, fold = tf[:6 * n].reshape(6, n), tf[6 * n:]
+            for i, d in enumerate(res['transients']):
+                d.update(y_psf_d=float(d['y'] + cols[2, i]), x_psf_d=float(d['x'] + cols[3, i]), flux_psf_d=float(cols[0, i]),
+                         fluxerr_psf_d=float(cols[1, i]), chi2_psf_d=float(cols[4, i]), flags_psf_d=int(cols[5, i]))
+            hdr_t.update(trans_fit_header(True, fit_size, res['transients'], fold))
+            if len(fold) and float(np.max(fold)) > PD_FOLD_WARN:
+                import logging
+                logging.getLogger(__name__).warning('P_D leaves %.3g of its |sum| outside its stamp (T-PDFOLD)', float(np.max(fold)))
+            if trans_chi2_max is not None:
+                res['transients'], keep = vet_transients(res['transients'], float(trans_chi2_max))
+                for k in ('thumbnails', 'thumbnail_png8'):
+                    if k in res:
+                        res[k] = res[k][torch.as_tensor(keep, dtype=torch.int64, device=res[k].device)]
+                hdr_t['T-NVET'] = (len(keep), 'number of transient candidates that passed the vetting')
     else:
         res['transients'] = []
     hdr['Z-P'] = (True, 'successfully processed by ZOGY?')

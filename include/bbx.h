@@ -906,6 +906,55 @@ int bbx_psf_optflux_shift(bbx_ctx *ctx, int ny, int nx, const float *d_D, const 
                           const int32_t *d_ys, const int32_t *d_xs, const float *d_off, float *d_flux, float *d_err,
                           uint8_t *d_flags, void *stream);
 
+/* ---- transient vetting: the PSF of D per sub-image and its fit to D per candidate (bbx_transfit.hip).  zogy fits
+ * the PSF of the difference image to D at every candidate with free position (E_FLUX_PSF_D, X_PSF_D, Y_PSF_D, CHI2_PSF_D) ([EXT]:
+ * zogy is not in the reference tree; the rules below are THIS PROJECT'S OWN, parity is unpinned).
+ *
+ * bbx_zogy_pd_stamps: d_pd[nsub][S][S] float32, the PSF of D of every sub-image, from the stamps d_pn, d_pr [nsub][S][S] (unit
+ * sum, centre at S / 2; S odd, <= 49) and h_scal[nsub][6] = (sn, sr, fn, fr, dx, dy), a HOST array as bbx_zogy_frame takes it:
+ *  1 on an M x M grid (M even, 4 S <= M <= 512) both stamps are embedded with their centre on the origin and transformed;
+ *  2 PD^ = (fr fn / fD) Pr^ Pn^ / sqrt(sn^2 fr^2 |Pr^|^2 + sr^2 fn^2 |Pn^|^2), fD = fr fn / sqrt(sn^2 fr^2 + sr^2 fn^2); 0 where
+ *    the denominator is 0;
+ *  3 back to real space, p[M][M]; the S x S pixels around the origin, divided by their sum, are the stamp;
+ *  4 d_fold[sub] = (sum |p| over the grid - sum |p| over the stamp) / sum |p| over the grid: what the cut leaves out.
+ * Every step in float64 (plain matrix DFTs with twiddles from sincospi: rows over S taps, columns over S rows; only the columns
+ * kx <= M / 2 are made, p is real), sums in a fixed order, no atomics; the stamp is rounded to float32 at the end.  A sub-image
+ * whose sn, sr, fn or fr is not finite and positive, or whose stamps or p have no positive finite sum: a zero stamp, fold = 1.
+ * Workspace (nsub M (M / 2 + 1) complex128 and less) from the context.  nsub == 0: nothing is launched.
+ *
+ * bbx_trans_psffit: per candidate c < ncand at the integer peak (y0, x0) = (d_ys[c], d_xs[c]), sub-image k = min(y0 / size, nsy - 1)
+ * nsx + min(x0 / size, nsx - 1) (nsy = nsub / nsx), window of W x W pixels around the peak (W odd, 3 <= W <= S - 10):
+ *  - used pixels: on the frame, d_mask == 0 (d_mask may be NULL; a pixel left out for it: flag 2), D finite, V_D positive and
+ *    finite, V_D = (fr^2 Vn + fn^2 Vr) / (fr fn)^2 in float32 with Vn = max(N, 0) + sigma_n^2, Vr = max(R, 0) + sigma_r^2
+ *    (bbx_variance's: fmaxf, so a NaN in N or R counts 0): N = d_N, R = d_R the background-subtracted new and reference frames
+ *    on the new grid, the two sigma maps as
+ *    frames (d_sig_n, d_sig_r) or as mini images (mini_n, mini_r; read as bbx_psf_optflux_mini reads them) -- one form for both;
+ *    fr, fn from h_scal[k] (HOST array [nsub][6], as above).  On background alone V_D = 1 / fD^2, the variance ZOGY gives D;
+ *    elsewhere it is the unsmoothed approximation;
+ *  - theta = (dy, dx) float32 starts at (0, 0).  niter times (1 <= niter <= 64, never fewer on the data's account):
+ *      Ps = d_pd[k] shifted by theta with steps 2 and 3 of bbx_psf_optflux_shift (the same device function: row pass, column pass,
+ *      float32 taps; norm in float64, Ps / norm in float64); Gx[j][i] = (Ps[j][i + 1] - Ps[j][i - 1]) / 2, Gy likewise;
+ *      the weighted least squares D ~ F Ps - a Gx - b Gy over the used pixels, weights 1 / V_D: the nine sums in float64 (fixed
+ *      order), the 3 x 3 system by cofactors in float64; Delta = (b / F, a / F), each component clamped to +-0.5,
+ *      theta = float32(clamp(theta + Delta, +-maxshift)), 0 < maxshift <= 16.
+ *      det == 0 or not finite, F == 0 or not finite, Delta not finite: the stepping stops, theta stays (flag 8);
+ *  - the final pass at theta: F = sum Ps D / V / sum Ps^2 / V, err = 1 / sqrt(sum Ps^2 / V), chi2 = sum (D - F Ps)^2 / V /
+ *    (n_used - 3); d_flux, d_err, d_dy, d_dx, d_chi2 float32.
+ * d_flags[c] u8 = 1 (|theta| at maxshift in an axis) | 2 (a masked pixel was left out) | 4 (no fit: the peak off the frame,
+ * n_used < 4, a P_D stamp without a positive sum, sum Ps^2 / V not positive; all five outputs 0) | 8 (the last unclamped
+ * max(|Delta_y|, |Delta_x|) > 0.01 pixel, or the stepping stopped).  A negative candidate fits a negative F.
+ * Deterministic as bbx_psf_optflux_shift: no atomics, per thread over pixels tid, tid + 256, ..., then the wave, then the four
+ * waves in order.  One workgroup of 256 per candidate; the stamp, the row pass's output and the window's D and V_D in LDS
+ * (31.5 KB).  ncand == 0: nothing is launched.                                                                              */
+int bbx_zogy_pd_stamps(bbx_ctx *ctx, int nsub, int S, int M, const float *d_pn, const float *d_pr, const float *scal,
+                       float *d_pd, float *d_fold, void *stream);
+int bbx_trans_psffit(bbx_ctx *ctx, int ny, int nx, const float *d_D, const float *d_N, const float *d_R,
+                     const float *d_sig_n, const float *d_sig_r, const bbx_spline_image *mini_n,
+                     const bbx_spline_image *mini_r, const uint8_t *d_mask, int S, int nsub, const float *d_pd, int size,
+                     int nsx, const float *scal, int ncand, const int32_t *d_ys, const int32_t *d_xs, int W, int niter,
+                     float maxshift, float *d_flux, float *d_err, float *d_dy, float *d_dx, float *d_chi2,
+                     uint8_t *d_flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,121 @@
+"""What the transient vetting (zogy.optimal_subtraction(trans_psffit=True)) costs.
+
+    python tools/transfit_bench.py [--out profiles/transfit.json] [--warmup 10] [--frames 30]
+
+A frame of the benchmark's scene (tools/thumbs_bench.scene: 10560 x 10560, cat_extract and trans_extract on in both legs)
+through zogy.optimal_subtraction
+  off: without the keyword (no kernel of bbx_transfit.hip is launched: the parent's path)
+  on : trans_psffit=True: bbx_zogy_pd_stamps once, bbx_trans_psffit at the frame's candidates
+alternating, in this one process: each call between two HIP events, [warmup] untimed calls of each leg first, the median of
+[frames] calls per leg.  Then the two entries by themselves on that frame's images, stamps and candidate list, each between two
+HIP events with the host's part inside:
+  pd_stamps  : zogy.pd_stamps (settings.trans_pd_grid)
+  psffit     : zogy.trans_psffit with the stamps given
+The result goes to [out] and to stdout as one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+
+def stats(v):
+    v = sorted(v)
+    return dict(median_ms=statistics.median(v), min_ms=v[0], max_ms=v[-1], p25_ms=v[len(v) // 4], p75_ms=v[(3 * len(v)) // 4], n=len(v))
+
+
+def frames(ctx, torch, a):
+    import numpy as np
+    import thumbs_bench as T
+    from blackbox_amd import settings, zogy as G
+    from blackbox_amd._lib import push
+    data, mask, kw = T.scene(ctx)
+    legs = {'off': dict(kw), 'on': dict(kw, trans_psffit=True)}
+    res = G.optimal_subtraction(ctx, data, new_mask=mask, **legs['on'])
+    ctx.sync()
+    for leg in legs.values():
+        leg['ref_bkg_std'] = res['bkg_std_ref'] if 'bkg_std_ref' in res else None          # the reference's sigma map as a run keeps it
+    rows, ht = res['transients'], res['header_trans']
+    ys, xs = np.array([t['y'] for t in rows], np.int32), np.array([t['x'] for t in rows], np.int32)
+    size = kw['subimage_size']
+    nsy, nsx = data.shape[0] // size, data.shape[1] // size
+
+    def stamps(psf):
+        if isinstance(psf, dict):
+            return G.subimage_psfs(ctx, psf, nsy, nsx, size).contiguous()
+        return (psf if psf.dim() == 3 else psf[None].expand(nsy * nsx, -1, -1)).contiguous()
+    sub_pn, sub_pr = stamps(kw['psf_new']), stamps(kw['psf_ref'])
+    scal = res['scal']
+    frames_ = [res[k] for k in ('D', 'data_bkgsub', 'ref_bkgsub')]
+    sig = (res['bkg_std'], res['bkg_std_ref'])
+    if isinstance(sig[0], G.MiniImage) != isinstance(sig[1], G.MiniImage):
+        sig = tuple(s.frame(ctx) if isinstance(s, G.MiniImage) else s for s in sig)
+    d_pd, d_fold = G.pd_stamps(ctx, sub_pn, sub_pr, scal)
+    d_peaks = push(ctx, ys, xs)
+    flags = np.array([t['flags_psf_d'] for t in rows], np.uint8)
+    info = dict(candidates=int(len(rows)), stamp_side=int(sub_pn.shape[1]), sub_images=int(nsy * nsx), pd_grid=int(settings.trans_pd_grid),
+                fit_size=int(settings.trans_fit_size), fit_niter=int(settings.trans_fit_niter),
+                sigma_form='mini image' if isinstance(sig[0], G.MiniImage) else 'frame', flags_psf_d=np.bincount(flags, minlength=16).tolist(),
+                header={k: ht[k][0] for k in ('T-NTRANS', 'T-PSFD', 'T-FITSZ', 'T-NFIT', 'T-PDFOLD', 'T-CHI2MD')})
+    del res
+    times = {k: [] for k in legs}
+    stage = {'pd_stamps': [], 'psffit': []}
+
+    def timed(fn, sink):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = fn()
+        e1.record()
+        ctx.sync()
+        del r
+        if sink is not None:
+            sink.append(e0.elapsed_time(e1))
+    calls = {'pd_stamps': lambda: G.pd_stamps(ctx, sub_pn, sub_pr, scal),
+             'psffit': lambda: G.trans_psffit(ctx, frames_[0], frames_[1], frames_[2], sig[0], sig[1], mask, d_pd, ys, xs, scal, size, nsx,
+                                              d_peaks=d_peaks)}
+    for it in range(a.warmup + a.frames):
+        keep = it >= a.warmup
+        for leg in legs:
+            timed(lambda: G.optimal_subtraction(ctx, data, new_mask=mask, **legs[leg]), times[leg] if keep else None)
+        for name, fn in calls.items():
+            timed(fn, stage[name] if keep else None)
+    out = dict(what='zogy.optimal_subtraction(cat_extract=True, trans_extract=True) on bench.py\'s 10560 x 10560 scene, HIP events around each '
+                    'call, legs (trans_psffit off / on) alternating in one process; the two entries alone on that frame\'s candidates',
+               warmup_per_leg=a.warmup, **info, optimal_subtraction_ms={k: stats(v) for k, v in times.items()},
+               stage_ms={k: stats(v) for k, v in stage.items()})
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out['added_ms_per_frame'] = med['on'] - med['off']
+    out['added_fraction_of_off'] = out['added_ms_per_frame'] / med['off']
+    out['stages_added_ms'] = statistics.median(stage['pd_stamps']) + statistics.median(stage['psffit'])
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'transfit.json'))
+    ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--frames', type=int, default=30)
+    a = ap.parse_args()
+    if a.warmup < 10 or a.frames < 30:
+        ap.error('at least 10 warm-up and 30 timed samples per leg')
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit('transfit_bench.py needs a GPU: nothing is measured without one')
+    from blackbox_amd import reduce as R
+    ctx = R.Context(0)
+    out = dict(frame=frames(ctx, torch, a))
+    ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
