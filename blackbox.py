@@ -414,6 +414,14 @@ class Reducer:
                 chi2_max = par(a.trans_chi2_max, 'trans_chi2_max')
                 if chi2_max is not None:
                     sub['trans_chi2_max'] = chi2_max
+            # a Gauss and a Moffat fitted to every transient candidate, with or without the fit of P_D; likewise
+            if par(a.trans_shapefit, 'trans_shapefit'):
+                sub['trans_shapefit'] = True
+                if a.trans_shape_size is not None:
+                    sub['trans_shape_size'] = a.trans_shape_size
+                for k in ('trans_fwhm_gauss_min', 'trans_fwhm_gauss_max', 'trans_elong_gauss_max'):
+                    if par(getattr(a, k), k) is not None:
+                        sub[k] = par(getattr(a, k), k)
         if (sub['cat_extract'] or sub.get('match')) and par(a.phot_centroid, 'phot_centroid'):
             # the PSF on the centroids wherever photometry runs (the catalogue, the star match's two lists); the keyword is only
             # passed when switched on
@@ -1118,6 +1126,16 @@ def build_parser():
     ap.add_argument('--trans_fit_size', type=int, default=None, help='[pix] side of the window of that fit (default: settings.trans_fit_size)')
     ap.add_argument('--trans_chi2_max', type=float, default=None,
                     help='drop the candidates without a fit or with CHI2_PSF_D above this, T-NVET (default: settings.trans_chi2_max)')
+    ap.add_argument('--trans_shapefit', type=str2bool, default=None,
+                    help='fit an elliptical Gaussian and an elliptical Moffat to D at every transient candidate: X/Y_GAUSS_D FWHM_GAUSS_D '
+                         'ELONG_GAUSS_D CHI2_GAUSS_D FLAGS_GAUSS_D and the same of _MOFFAT_D in `_trans.fits`, T-SHAPE T-SHPSZ T-MBETA T-NGAUS '
+                         'T-NMOFF T-FWGMD T-ELGMD in its header (default: settings.trans_shapefit)')
+    ap.add_argument('--trans_shape_size', type=int, default=None, help='[pix] side of the window of those fits (default: settings.trans_shape_size)')
+    ap.add_argument('--trans_fwhm_gauss_min', type=float, default=None,
+                    help='[pix] drop the candidates without a Gauss fit or with FWHM_GAUSS_D below this, T-NVET (default: settings.trans_fwhm_gauss_min)')
+    ap.add_argument('--trans_fwhm_gauss_max', type=float, default=None, help='[pix] ... above this (default: settings.trans_fwhm_gauss_max)')
+    ap.add_argument('--trans_elong_gauss_max', type=float, default=None,
+                    help='... or with ELONG_GAUSS_D above this (default: settings.trans_elong_gauss_max)')
     ap.add_argument('--phot_centroid', type=str2bool, default=None,
                     help='catalogue photometry (--cat_extract, --zogy_match) with the PSF shifted to each source\'s windowed centroid and '
                          'masked pixels left out: FLAGS_OPT and sub-pixel X_POS / Y_POS in _cat.fits, PHOT-CEN in the header (default: '

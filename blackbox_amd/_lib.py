@@ -151,6 +151,8 @@ SIGNATURES = {
     'bbx_zogy_pd_stamps': (_i, [_vp, _i, _i, _i, _vp, _vp, _pf, _vp, _vp, _vp]),
     'bbx_trans_psffit': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _pf, _i, _vp, _vp, _i, _i, _f,
                               _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'bbx_trans_shapefit': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _pf, _vp, _i, _vp, _vp, _i, _i, _f, _i, _f, _f, _f,
+                                _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError if the export is missing

@@ -47,6 +47,10 @@ PHOT_COLUMNS = (('FLAGS_OPT', np.uint8, ''),)
 # 'trans' columns of a table that carries them
 TRANSFIT_COLUMNS = (('X_PSF_D', np.float32, 'pix'), ('Y_PSF_D', np.float32, 'pix'), ('E_FLUX_PSF_D', np.float32, 'e-'),
                     ('E_FLUXERR_PSF_D', np.float32, 'e-'), ('CHI2_PSF_D', np.float32, ''), ('FLAGS_PSF_D', np.uint8, ''))
+# the Gauss and Moffat fits to D at every transient candidate (settings.trans_shapefit; zogy.optimal_subtraction(trans_shapefit=True)):
+# appended after TRANSFIT_COLUMNS to the 'trans' columns of a table that carries them
+TRANSSHAPE_COLUMNS = tuple((n + '_' + m + '_D', np.uint8 if n == 'FLAGS' else np.float32, '' if n in ('ELONG', 'CHI2', 'FLAGS') else 'pix')
+                           for m in ('GAUSS', 'MOFFAT') for n in ('X', 'XERR', 'Y', 'YERR', 'FWHM', 'ELONG', 'CHI2', 'FLAGS'))
 THUMBNAILS = ('RED', 'REF', 'D', 'SCORR')                     # plane order of zogy.thumbnail_stamps; blackbox.py:2701
 THUMBNAIL_COLUMNS = tuple('THUMBNAIL_' + c for c in THUMBNAILS)
 
@@ -76,6 +80,10 @@ def format_cat(table, cat_output, cat_type='new', header2add=None):
             units[name] = unit
     if cat_type == 'trans' and table is not None and TRANSFIT_COLUMNS[0][0] in table:
         for name, dt, unit in TRANSFIT_COLUMNS:
+            cols[name] = np.asarray(table[name]).astype(dt)
+            units[name] = unit
+    if cat_type == 'trans' and table is not None and TRANSSHAPE_COLUMNS[0][0] in table:
+        for name, dt, unit in TRANSSHAPE_COLUMNS:
             cols[name] = np.asarray(table[name]).astype(dt)
             units[name] = unit
     if cat_type == 'trans' and table is not None and THUMBNAIL_COLUMNS[0] in table:
@@ -115,6 +123,11 @@ def _transient_columns(t):
                    E_FLUX_PSF_D=np.array([d['flux_psf_d'] for d in t], np.float32),
                    E_FLUXERR_PSF_D=np.array([d['fluxerr_psf_d'] for d in t], np.float32),
                    CHI2_PSF_D=np.array([d['chi2_psf_d'] for d in t], np.float32), FLAGS_PSF_D=np.array([d['flags_psf_d'] for d in t], np.uint8))
+    if t and all('chi2_gauss_d' in d for d in t):
+        # the Gauss and Moffat fits to D (zogy.trans_shapefit): sub-pixel FITS coordinates, 1-based
+        for name, dt, _ in TRANSSHAPE_COLUMNS:
+            key = name.lower()
+            tab[name] = np.array([d[key] + 1.0 if name[:2] in ('X_', 'Y_') else d[key] for d in t], dt)
     return tab
 
 

@@ -46,6 +46,8 @@ static inline int bbx_make_dims(const bbx_geom* g, bbx_dims* d) {
 // made of -- two inputs by address, the stamp side S (rows: 0) and the geometry (ny, nx, size, border)
 struct bbx_zprep { const float2* buf; const void* id[2]; int S; int geom[4]; };
 
+#define BBX_WS_SLOTS 32              // room for the workspace slots of the enum below (WS_MAX; checked there)
+
 struct bbx_ctx {
     int device;
     char hip_err[256];
@@ -61,8 +63,8 @@ struct bbx_ctx {
     size_t    hash_clean_n;
     int32_t*  d_counters;      // [CNT_MAX] device counters (see enum below)
     // --- scratch, (re)allocated on demand by bbx_ws()
-    void*  d_ws[24];
-    size_t ws_bytes[24];
+    void*  d_ws[BBX_WS_SLOTS];
+    size_t ws_bytes[BBX_WS_SLOTS];
     int    lac_feed;           // BBX_OPT_LAC_LEVEL_FEED (bbx_set_option)
     int    debug_listcap;      // BBX_OPT_DEBUG_LISTCAP: capacity the LA-Cosmic kernels see (0 = the allocated one)
     void*  zogy_state;         // per-context FFT plans / work buffer of bbx_zogy.hip (NULL until first use)
@@ -136,8 +138,10 @@ enum {
     WS_HASH = 0, WS_CCLIST, WS_PARENT, WS_BITS_M, WS_BITS_C, WS_BITS_R, WS_TILES,
     WS_CAND, WS_FLAGS, WS_STAGE2, WS_CRLIST, WS_HIST, WS_SEL, WS_MISC, WS_STRIP, WS_HVALS, WS_CRORIG, WS_CANNY, WS_ZCAND, WS_BCAND, WS_FPHINT, WS_BOXFAIL, WS_ZSPL,
     WS_TRANSFIT,
+    WS_TRANSSHAPE,       // bbx_trans_shapefit's scalars: a slot of its own, so that the call may be queued beside bbx_trans_psffit's
     WS_MAX
 };
+static_assert(WS_MAX <= BBX_WS_SLOTS, "bbx_ctx::d_ws holds BBX_WS_SLOTS slots");
 
 int bbx_hip_fail(bbx_ctx* ctx, hipError_t e, const char* what, int line);
 // entries of a candidate pixel list of a frame of npix pixels (bbx_find_peaks and the kernels that list for it: WS_CCLIST,

@@ -1,5 +1,6 @@
-// bbx_transfit.hip -- transient vetting (include/bbx.h, bbx_zogy_pd_stamps and bbx_trans_psffit): the PSF of the
-// difference image D per sub-image, and per transient candidate a fit of that PSF to D with free position.
+// bbx_transfit.hip -- transient vetting (include/bbx.h, bbx_zogy_pd_stamps, bbx_trans_psffit and bbx_trans_shapefit):
+// the PSF of the difference image D per sub-image, per transient candidate a fit of that PSF to D with free position, and
+// per candidate an elliptical Gaussian and an elliptical Moffat fitted to D by Levenberg-Marquardt (at the end of the file).
 //
 //   bbx_zogy_pd_stamps : P_D^ = (fr fn / fD) Pr^ Pn^ / sqrt(sn^2 fr^2 |Pr^|^2 + sr^2 fn^2 |Pn^|^2) on an M x M grid, back to real
 //                        space, cut to S x S.  The stamps have S x S pixels, so the forward transforms are plain matrix DFTs
@@ -18,7 +19,7 @@
 
 #define TF_BLOCK 256
 #define TF_SMAX  49
-#define TF_WMAX  39                                                  // W <= S - 10
+#define TF_WMAX  39                                                  // bbx_trans_psffit: W <= S - 10; bbx_trans_shapefit: W <= TF_WMAX
 #define TF_MMAX  512
 #define TF_NSUM  9
 
@@ -194,12 +195,57 @@ extern "C" int bbx_zogy_pd_stamps(bbx_ctx* ctx, int nsub, int S, int M, const fl
 }
 
 // ---- the fit ----------------------------------------------------------------------------------------------------------------
+// what the window of a candidate is read from: the frames, the two sigma maps as frames (the mini images travel beside it), the
+// mask, the sub-images' scalars and their grid
+struct tf_win {
+    const float *D, *N, *R, *sig_n, *sig_r; const uint8_t* mask; const tf_scal* sc;
+    int ny, nx, size, nsx, nsy;
+};
 struct tf_args {
-    const float *D, *N, *R, *sig_n, *sig_r; const uint8_t* mask; const float* pd; const tf_scal* sc;
+    tf_win w; const float* pd;
     const int32_t *ys, *xs;
     float *flux, *err, *dy, *dx, *chi2; uint8_t* flags;
-    int ny, nx, S, size, nsx, nsy, W, niter; float maxshift;
+    int S, W, niter; float maxshift;
 };
+
+__device__ __forceinline__ int tf_sub_index(const tf_win& w, int py, int px) {
+    return min(max(py, 0) / w.size, w.nsy - 1) * w.nsx + min(max(px, 0) / w.size, w.nsx - 1);
+}
+
+// The window of W x W pixels around the peak (py, px), pixels first, first + stride, ... : D into s_d, V_D = (fr^2 Vn + fn^2 Vr) /
+// (fr fn)^2 in float32 into s_v (0: the pixel is not used -- off the frame, masked, D not finite, V_D not positive and finite;
+// s_d is 0 there).  hit: a masked pixel was left out; the return value counts the used pixels of this thread.  The one place
+// where the used-pixel rule and V_D are written down: bbx_trans_psffit and bbx_trans_shapefit both fit on this window
+template <bool MINI>
+__device__ __forceinline__ double tf_window(const tf_win& w, const bbx_spl& spn, const bbx_spl& spr, const tf_scal& z, int py, int px, bool nofit, int W,
+                                            int first, int stride, float* s_d, float* s_v, int& hit) {
+    const int nw = W * W, hw = W / 2;
+    const float fr2 = z.fr * z.fr, fn2 = z.fn * z.fn, ff = z.fr * z.fn, ff2 = ff * ff;
+    double cnt = 0.0;
+    for (int k = first; k < nw; k += stride) {
+        const int wy = k / W, wx = k - wy * W;
+        const long long y = (long long)py - hw + wy, x = (long long)px - hw + wx;
+        float d = 0.f, v = 0.f;
+        if (!nofit && y >= 0 && y < w.ny && x >= 0 && x < w.nx) {
+            const size_t ix = (size_t)y * w.nx + (size_t)x;
+            if (w.mask && w.mask[ix]) hit = 1;
+            else {
+                d = w.D[ix];
+                if (finite_f32(d)) {
+                    const float sn = MINI ? bbx_spl_eval(spn, (int)y, (int)x) : w.sig_n[ix];
+                    const float sr = MINI ? bbx_spl_eval(spr, (int)y, (int)x) : w.sig_r[ix];
+                    const float vn = fmaxf(w.N[ix], 0.f) + sn * sn, vr = fmaxf(w.R[ix], 0.f) + sr * sr;
+                    v = (fr2 * vn + fn2 * vr) / ff2;
+                    if (!(v > 0.f) || !finite_f32(v)) v = 0.f;
+                }
+                if (v == 0.f) d = 0.f;
+            }
+        }
+        s_d[k] = d; s_v[k] = v;
+        if (v > 0.f) cnt += 1.0;
+    }
+    return cnt;
+}
 
 template <bool MINI>
 __global__ __launch_bounds__(TF_BLOCK) void k_trans_psffit(tf_args a, bbx_spl spn, bbx_spl spr) {
@@ -212,37 +258,14 @@ __global__ __launch_bounds__(TF_BLOCK) void k_trans_psffit(tf_args a, bbx_spl sp
     const int S = a.S, npx = S * S, h = S / 2, W = a.W, nw = W * W, hw = W / 2;
     const int py = a.ys[c], px = a.xs[c];
     unsigned fl = 0;
-    bool nofit = py < 0 || py >= a.ny || px < 0 || px >= a.nx;       // (uniform, like everything that steers the flow below)
-    const int ky = min(max(py, 0) / a.size, a.nsy - 1), kx = min(max(px, 0) / a.size, a.nsx - 1);
-    const int sub = ky * a.nsx + kx;
-    const tf_scal z = a.sc[sub];
+    bool nofit = py < 0 || py >= a.w.ny || px < 0 || px >= a.w.nx;   // (uniform, like everything that steers the flow below)
+    const int sub = tf_sub_index(a.w, py, px);
+    const tf_scal z = a.w.sc[sub];
     const float* pd = a.pd + (size_t)sub * npx;
-    // ---- the window: D, V_D = (fr^2 Vn + fn^2 Vr) / (fr fn)^2 in float32
-    const float fr2 = z.fr * z.fr, fn2 = z.fn * z.fn, ff = z.fr * z.fn, ff2 = ff * ff;
+    // ---- the window: D and V_D in float32
     int hit = 0;
-    double cnt[1] = {0.0};
-    for (int k = tid; k < nw; k += TF_BLOCK) {
-        const int wy = k / W, wx = k - wy * W;
-        const long long y = (long long)py - hw + wy, x = (long long)px - hw + wx;
-        float d = 0.f, v = 0.f;
-        if (!nofit && y >= 0 && y < a.ny && x >= 0 && x < a.nx) {
-            const size_t ix = (size_t)y * a.nx + (size_t)x;
-            if (a.mask && a.mask[ix]) hit = 1;
-            else {
-                d = a.D[ix];
-                if (finite_f32(d)) {
-                    const float sn = MINI ? bbx_spl_eval(spn, (int)y, (int)x) : a.sig_n[ix];
-                    const float sr = MINI ? bbx_spl_eval(spr, (int)y, (int)x) : a.sig_r[ix];
-                    const float vn = fmaxf(a.N[ix], 0.f) + sn * sn, vr = fmaxf(a.R[ix], 0.f) + sr * sr;
-                    v = (fr2 * vn + fn2 * vr) / ff2;
-                    if (!(v > 0.f) || !finite_f32(v)) v = 0.f;
-                }
-                if (v == 0.f) d = 0.f;
-            }
-        }
-        s_d[k] = d; s_v[k] = v;
-        if (v > 0.f) cnt[0] += 1.0;
-    }
+    double cnt[1];
+    cnt[0] = tf_window<MINI>(a.w, spn, spr, z, py, px, nofit, W, tid, TF_BLOCK, s_d, s_v, hit);
     if (__syncthreads_or(hit)) fl |= 2u;
     tf_block_sums<1>(cnt, s_red);
     const int n_used = (int)cnt[0];
@@ -362,12 +385,280 @@ extern "C" int bbx_trans_psffit(bbx_ctx* ctx, int ny, int nx, const float* d_D, 
     int rc;
     tf_scal* sc = (tf_scal*)bbx_ws(ctx, WS_TRANSFIT, tf_up((size_t)nsub * sizeof(tf_scal)), &rc); if (rc) return rc;
     BBX_HIP(hipMemcpyAsync(sc, h_scal, (size_t)nsub * sizeof(tf_scal), hipMemcpyHostToDevice, s));               // pageable source: staged before the call returns
-    const tf_args a = {d_D, d_N, d_R, d_sig_n, d_sig_r, d_mask, d_pd, sc, d_ys, d_xs, d_flux, d_err, d_dy, d_dx, d_chi2, d_flags,
-                       ny, nx, S, size, nsx, nsub / nsx, W, niter, maxshift};
+    const tf_args a = {{d_D, d_N, d_R, d_sig_n, d_sig_r, d_mask, sc, ny, nx, size, nsx, nsub / nsx}, d_pd, d_ys, d_xs,
+                       d_flux, d_err, d_dy, d_dx, d_chi2, d_flags, S, W, niter, maxshift};
     if (mini)
         hipLaunchKernelGGL(k_trans_psffit<true>, dim3(ncand), dim3(TF_BLOCK), 0, s, a, spn, spr);
     else
         hipLaunchKernelGGL(k_trans_psffit<false>, dim3(ncand), dim3(TF_BLOCK), 0, s, a, spn, spr);
+    BBX_LAUNCH_CHECK();
+    return BBX_OK;
+}
+
+// ---- the shape fits: an elliptical Gaussian and an elliptical Moffat fitted to D per candidate (bbx_trans_shapefit) ----
+// One wave per candidate, TS_WAVES candidates per workgroup.  Every lane keeps the pixels lane, lane + 64, ... of its wave's
+// window; the 36 sums of a pass go per lane over those pixels, then over the wave by DPP (wave_sum_f64: the result in every
+// lane), so the reductions need no workgroup barrier and every lane runs the same small float64 algebra on the same numbers.
+#define TS_WAVES 4
+#define TS_NPAR  7                                                   // A, B, y0, x0, cyy, cxy, cxx
+#define TS_NH    28
+#define TS_NSUM  36                                                  // H (upper triangle by rows), g, chi2
+#define TS_NMIN  8
+
+struct ts_args {
+    tf_win w; const float* fwhm0; const int32_t *ys, *xs; float* out; uint8_t* flags;
+    int ncand, W, niter, models; float maxshift, beta, lo, hi;
+};
+
+__device__ __forceinline__ constexpr int ts_h(int i, int j) { return i * TS_NPAR - i * (i - 1) / 2 + (j - i); }       // i <= j
+__device__ __forceinline__ constexpr int ts_l(int i, int j) { return i * (i + 1) / 2 + j; }                           // j <= i
+
+// the sums at p over the wave's window: H = sum J J^T / V, g = sum J r / V, chi2 = sum r^2 / V; m = B + A g(q),
+// q = cyy dy^2 + 2 cxy dy dx + cxx dx^2 about (y0, x0), g = exp(-q / 2) or (1 + q)^-beta
+__device__ __forceinline__ void ts_pass(bool moffat, double beta, const double (&p)[TS_NPAR], const float* s_d, const float* s_v, int W, int lane,
+                                        double (&s)[TS_NSUM]) {
+    const int nw = W * W, hw = W / 2;
+#pragma unroll
+    for (int q = 0; q < TS_NSUM; q++) s[q] = 0.0;
+    for (int k = lane; k < nw; k += 64) {
+        const float vf = s_v[k];
+        if (!(vf > 0.f)) continue;
+        const int wy = k / W, wx = k - wy * W;
+        const double v = (double)vf, d = (double)s_d[k];
+        const double dy = (double)(wy - hw) - p[2], dx = (double)(wx - hw) - p[3];
+        const double q = p[4] * dy * dy + 2.0 * p[5] * dy * dx + p[6] * dx * dx;
+        double g, gq;
+        if (moffat) { g = pow(1.0 + q, -beta); gq = -beta * g / (1.0 + q); }
+        else { g = exp(-0.5 * q); gq = -0.5 * g; }
+        const double a = p[0] * gq;
+        const double J[TS_NPAR] = {g, 1.0, a * (-2.0 * (p[4] * dy + p[5] * dx)), a * (-2.0 * (p[5] * dy + p[6] * dx)), a * (dy * dy), a * (2.0 * dy * dx),
+                                   a * (dx * dx)};
+        const double r = d - (p[1] + p[0] * g);
+        double Jw[TS_NPAR];
+#pragma unroll
+        for (int i = 0; i < TS_NPAR; i++) Jw[i] = J[i] / v;
+#pragma unroll
+        for (int i = 0; i < TS_NPAR; i++) {
+#pragma unroll
+            for (int j = i; j < TS_NPAR; j++) s[ts_h(i, j)] += J[i] * Jw[j];
+            s[TS_NH + i] += Jw[i] * r;
+        }
+        s[TS_NSUM - 1] += r * r / v;
+    }
+#pragma unroll
+    for (int q = 0; q < TS_NSUM; q++) s[q] = wave_sum_f64(s[q]);
+}
+
+// L of H + lam diag H (lower triangle by rows); false at a pivot that is not positive and finite.  hold2, hold3: y0, x0 are held --
+// their rows and columns count 0 off the diagonal
+__device__ __forceinline__ bool ts_chol(const double (&H)[TS_NSUM], double lam, double (&L)[TS_NH], bool hold2 = false, bool hold3 = false) {
+#pragma unroll
+    for (int j = 0; j < TS_NPAR; j++) {
+        double s = H[ts_h(j, j)] * (1.0 + lam);
+#pragma unroll
+        for (int k = 0; k < j; k++) s -= L[ts_l(j, k)] * L[ts_l(j, k)];
+        if (!(s > 0.0 && s <= 1.0e300)) return false;
+        L[ts_l(j, j)] = sqrt(s);
+#pragma unroll
+        for (int i = j + 1; i < TS_NPAR; i++) {
+            double t = H[ts_h(j, i)];
+            if ((hold2 && (i == 2 || j == 2)) || (hold3 && (i == 3 || j == 3))) t = 0.0;
+#pragma unroll
+            for (int k = 0; k < j; k++) t -= L[ts_l(i, k)] * L[ts_l(j, k)];
+            L[ts_l(i, j)] = t / L[ts_l(j, j)];
+        }
+    }
+    return true;
+}
+
+__device__ __forceinline__ void ts_solve(const double (&L)[TS_NH], const double* b, double (&x)[TS_NPAR]) {
+#pragma unroll
+    for (int i = 0; i < TS_NPAR; i++) {
+        double t = b[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) t -= L[ts_l(i, k)] * x[k];
+        x[i] = t / L[ts_l(i, i)];
+    }
+#pragma unroll
+    for (int i = TS_NPAR - 1; i >= 0; i--) {
+        double t = x[i];
+#pragma unroll
+        for (int k = i + 1; k < TS_NPAR; k++) t -= L[ts_l(k, i)] * x[k];
+        x[i] = t / L[ts_l(i, i)];
+    }
+}
+
+// sqrt diag (L L^T)^-1: M = L^-1 column by column, diag_i = sum_{k >= i} M[k][i]^2
+__device__ __forceinline__ void ts_errors(const double (&L)[TS_NH], double (&e)[TS_NPAR]) {
+#pragma unroll
+    for (int i = 0; i < TS_NPAR; i++) {
+        double col[TS_NPAR];
+        col[i] = 1.0 / L[ts_l(i, i)];
+        double s = col[i] * col[i];
+#pragma unroll
+        for (int k = i + 1; k < TS_NPAR; k++) {
+            double t = 0.0;
+#pragma unroll
+            for (int j = i; j < k; j++) t -= L[ts_l(k, j)] * col[j];
+            col[k] = t / L[ts_l(k, k)];
+            s += col[k] * col[k];
+        }
+        e[i] = sqrt(s);
+    }
+}
+
+// the axes of the form: FWHM = 2 sqrt(kk / l) of the eigenvalues l1 >= l2; false: not finite or not positive definite
+__device__ __forceinline__ bool ts_axes(double kk, double cyy, double cxy, double cxx, double& fmin_, double& fmaj, double& l1, double& l2) {
+    if (!tf_fin(cyy) || !tf_fin(cxy) || !tf_fin(cxx) || !(cyy > 0.0 && cxx > 0.0 && cyy * cxx - cxy * cxy > 0.0)) return false;
+    const double hd = 0.5 * (cyy - cxx), root = sqrt(hd * hd + cxy * cxy), mean = 0.5 * (cyy + cxx);
+    l1 = mean + root;
+    l2 = (cyy * cxx - cxy * cxy) / l1;                               // (not mean - root: no cancellation)
+    if (!(l2 > 0.0 && tf_fin(l1))) return false;
+    fmin_ = 2.0 * sqrt(kk / l1); fmaj = 2.0 * sqrt(kk / l2);
+    return true;
+}
+
+template <bool MINI>
+__global__ __launch_bounds__(TS_WAVES * 64) void k_trans_shapefit(ts_args a, bbx_spl spn, bbx_spl spr) {
+    __shared__ float s_dd[TS_WAVES][TF_WMAX * TF_WMAX], s_vv[TS_WAVES][TF_WMAX * TF_WMAX];       // 48.7 KB
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c = blockIdx.x * TS_WAVES + wv;
+    const bool live = c < a.ncand;                                   // (uniform over the wave, like everything that steers the flow below)
+    float* s_d = s_dd[wv];
+    float* s_v = s_vv[wv];
+    const int W = a.W, nw = W * W, hw = W / 2;
+    const int py = live ? a.ys[c] : -1, px = live ? a.xs[c] : -1;
+    bool nofit = py < 0 || py >= a.w.ny || px < 0 || px >= a.w.nx;
+    const int sub = tf_sub_index(a.w, py, px);
+    const tf_scal z = a.w.sc[sub];
+    int hit = 0;
+    const double cnt = tf_window<MINI>(a.w, spn, spr, z, py, px, nofit, W, lane, 64, s_d, s_v, hit);
+    __syncthreads();                                                 // the one barrier: the start below reads other lanes' pixels
+    if (!live) return;
+    unsigned fl = __builtin_amdgcn_ballot_w64(hit != 0) ? 2u : 0u;
+    const int n_used = (int)wave_sum_f64(cnt);
+    const double lo = (double)a.lo, hi = (double)a.hi, bound = (double)a.maxshift, beta = (double)a.beta;
+    double f0 = (double)a.fwhm0[sub];
+    if (n_used < TS_NMIN || !(f0 > 0.0) || !tf_fin(f0)) nofit = true;
+    f0 = fmin(fmax(f0, lo), hi);
+    // A starts at D of the peak pixel, or of the used pixel of largest |D| (the first of those in row-major order)
+    double A0 = 0.0;
+    if (!nofit) {
+        const int kp = hw * W + hw;
+        if (s_v[kp] > 0.f) A0 = (double)s_d[kp];
+        else {
+            float best = -1.f;
+            for (int k = 0; k < nw; k++)
+                if (s_v[k] > 0.f && fabsf(s_d[k]) > best) { best = fabsf(s_d[k]); A0 = (double)s_d[k]; }
+        }
+    }
+    for (int mi = 0; mi < 2; mi++) {
+        const bool moffat = mi == 1;
+        float res[TS_NPAR] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        unsigned f = (fl & 2u) | 4u;
+        if (!nofit && (a.models & (1 << mi))) {
+            const double kk = moffat ? exp2(1.0 / beta) - 1.0 : 2.0 * 0.69314718055994530942;
+            const double c0 = 4.0 * kk / (f0 * f0);
+            double p[TS_NPAR] = {A0, 0.0, 0.0, 0.0, c0, 0.0, c0}, t[TS_NPAR], dl[TS_NPAR], e[TS_NPAR];
+            double S[TS_NSUM], St[TS_NSUM], L[TS_NH];
+            ts_pass(moffat, beta, p, s_d, s_v, W, lane, S);
+            double lam = 1.0e-3;
+            bool accepted = false, conv = false, shape_last = false;
+            for (int it = 0; it < a.niter; it++) {
+                shape_last = false;
+                bool ok = false;
+                // a centre coordinate at its bound that the gradient pushes further out is held for this step
+                const bool hold2 = fabs(p[2]) >= bound && S[TS_NH + 2] * p[2] > 0.0, hold3 = fabs(p[3]) >= bound && S[TS_NH + 3] * p[3] > 0.0;
+                if (ts_chol(S, lam, L, hold2, hold3)) {
+                    double gs[TS_NPAR];
+#pragma unroll
+                    for (int i = 0; i < TS_NPAR; i++) gs[i] = S[TS_NH + i];
+                    if (hold2) gs[2] = 0.0;
+                    if (hold3) gs[3] = 0.0;
+                    ts_solve(L, gs, dl);
+                    bool finite = true;
+#pragma unroll
+                    for (int i = 0; i < TS_NPAR; i++) { t[i] = p[i] + dl[i]; finite = finite && tf_fin(t[i]); }
+                    double fa, fb, l1, l2;
+                    if (!finite || !ts_axes(kk, t[4], t[5], t[6], fa, fb, l1, l2) || !(fa >= lo && fb <= hi)) shape_last = true;
+                    else {
+                        t[2] = fmin(fmax(t[2], -bound), bound); t[3] = fmin(fmax(t[3], -bound), bound);
+                        ts_pass(moffat, beta, t, s_d, s_v, W, lane, St);
+                        ok = tf_fin(St[TS_NSUM - 1]) && St[TS_NSUM - 1] <= S[TS_NSUM - 1];
+                    }
+                }
+                if (ok) {
+                    // the step against the errors of the undamped H at the point it leaves
+                    conv = false;
+                    if (ts_chol(S, 0.0, L)) {
+                        ts_errors(L, e);
+                        conv = true;
+#pragma unroll
+                        for (int i = 0; i < TS_NPAR; i++) conv = conv && fabs(t[i] - p[i]) <= 0.01 * e[i];
+                    }
+                    accepted = true;
+#pragma unroll
+                    for (int i = 0; i < TS_NPAR; i++) p[i] = t[i];
+#pragma unroll
+                    for (int q = 0; q < TS_NSUM; q++) S[q] = St[q];
+                    lam = fmax(lam / 10.0, 1.0e-9);
+                } else lam = fmin(lam * 10.0, 1.0e9);
+            }
+            double fa, fb, l1, l2;
+            if (ts_chol(S, 0.0, L) && ts_axes(kk, p[4], p[5], p[6], fa, fb, l1, l2)) {
+                ts_errors(L, e);
+                const double r[TS_NPAR] = {p[2], p[3], e[2], e[3], sqrt(fa * fb), sqrt(l1 / l2), S[TS_NSUM - 1] / (double)(n_used - TS_NPAR)};
+                bool finite = true;
+#pragma unroll
+                for (int i = 0; i < TS_NPAR; i++) finite = finite && tf_fin(r[i]);
+                if (finite) {
+#pragma unroll
+                    for (int i = 0; i < TS_NPAR; i++) res[i] = (float)r[i];
+                    f = fl & 2u;
+                    if (fabs(p[2]) >= bound || fabs(p[3]) >= bound) f |= 1u;
+                    if (!accepted || !conv) f |= 8u;
+                    if (shape_last) f |= 16u;
+                }
+            }
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < TS_NPAR; i++) a.out[((size_t)mi * TS_NPAR + i) * a.ncand + c] = res[i];
+            a.flags[(size_t)mi * a.ncand + c] = (uint8_t)f;
+        }
+    }
+}
+
+extern "C" int bbx_trans_shapefit(bbx_ctx* ctx, int ny, int nx, const float* d_D, const float* d_N, const float* d_R, const float* d_sig_n,
+                                  const float* d_sig_r, const bbx_spline_image* mini_n, const bbx_spline_image* mini_r, const uint8_t* d_mask,
+                                  int nsub, int size, int nsx, const float* h_scal, const float* d_fwhm0, int ncand, const int32_t* d_ys,
+                                  const int32_t* d_xs, int W, int niter, float maxshift, int models, float beta, float fwhm_lo, float fwhm_hi,
+                                  float* d_out, uint8_t* d_flags, void* stream) {
+    if (!ctx || ny < 1 || nx < 1 || W < 5 || !(W & 1) || W > TF_WMAX || ncand < 0 || ncand > (1 << 28)) return BBX_ERR_ARG;
+    if (size < 1 || nsx < 1 || nsub < nsx || nsub % nsx || nsub > 65535 || niter < 1 || niter > 128) return BBX_ERR_ARG;
+    if (!(maxshift > 0.f) || !(maxshift <= 16.f) || models < 0 || models > 3 || !(beta > 1.f) || !(beta <= 100.f)) return BBX_ERR_ARG;
+    if (!(fwhm_lo > 0.f) || !(fwhm_lo < fwhm_hi) || !(fwhm_hi <= 1.0e6f)) return BBX_ERR_ARG;
+    const bool mini = mini_n != nullptr || mini_r != nullptr;
+    if (mini ? (!mini_n || !mini_r || d_sig_n || d_sig_r) : (!d_sig_n || !d_sig_r)) return BBX_ERR_ARG;               // one form, for both
+    bbx_spl spn = {}, spr = {};
+    if (mini) {
+        int rc = bbx_spl_make(mini_n, ny, nx, &spn); if (rc) return rc;
+        rc = bbx_spl_make(mini_r, ny, nx, &spr); if (rc) return rc;
+    }
+    if (!d_D || !d_N || !d_R || !h_scal || !d_fwhm0) return BBX_ERR_ARG;
+    if (ncand == 0 || models == 0) return BBX_OK;
+    if (!d_ys || !d_xs || !d_out || !d_flags) return BBX_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    tf_scal* sc = (tf_scal*)bbx_ws(ctx, WS_TRANSSHAPE, tf_up((size_t)nsub * sizeof(tf_scal)), &rc); if (rc) return rc;
+    BBX_HIP(hipMemcpyAsync(sc, h_scal, (size_t)nsub * sizeof(tf_scal), hipMemcpyHostToDevice, s));               // pageable source: staged before the call returns
+    const ts_args a = {{d_D, d_N, d_R, d_sig_n, d_sig_r, d_mask, sc, ny, nx, size, nsx, nsub / nsx}, d_fwhm0, d_ys, d_xs, d_out, d_flags,
+                       ncand, W, niter, models, maxshift, beta, fwhm_lo, fwhm_hi};
+    const int nblk = (ncand + TS_WAVES - 1) / TS_WAVES;
+    if (mini)
+        hipLaunchKernelGGL(k_trans_shapefit<true>, dim3(nblk), dim3(TS_WAVES * 64), 0, s, a, spn, spr);
+    else
+        hipLaunchKernelGGL(k_trans_shapefit<false>, dim3(nblk), dim3(TS_WAVES * 64), 0, s, a, spn, spr);
     BBX_LAUNCH_CHECK();
     return BBX_OK;
 }

@@ -90,6 +90,20 @@ trans_fit_maxshift = 2.0       # [pix] the position stays within this of the int
 trans_pd_grid = 256            # side of the grid P_D is formed on, >= 4 x the PSF stamp side, even, <= 512
 trans_chi2_max = None          # rows without a fit or with CHI2_PSF_D above this are dropped (T-NVET); None: no row is dropped
 
+# ---- transient vetting: an elliptical Gaussian and an elliptical Moffat fitted to D at every candidate (bbx_trans_shapefit, DESIGN.md
+# 4k; zogy's X/Y_GAUSS_D FWHM_GAUSS_D ELONG_GAUSS_D CHI2_GAUSS_D and the same of _MOFFAT_D, [EXT]: the rules are this project's own) ----
+# Off by default: `_trans.fits` keeps its columns, `_trans_hdr.fits` its keys.  Works with and without trans_psffit.
+trans_shapefit = False         # the sixteen catalogs.TRANSSHAPE_COLUMNS, T-SHAPE T-SHPSZ T-MBETA T-NGAUS T-NMOFF T-FWGMD T-ELGMD keys
+trans_shape_size = 11          # [pix] side of the (square, odd) window of the two fits, 5 .. 39
+trans_shape_niter = 32         # Levenberg-Marquardt iterations, always all of them
+trans_shape_maxshift = 2.0     # [pix] the centre stays within this of the integer peak in either axis
+trans_moffat_beta = 2.5        # the Moffat's beta, fixed (a free beta does not converge in this many iterations: DESIGN.md 4k)
+trans_shape_fwhm_lo = 0.5      # [pix] an axis FWHM below this refuses the step
+trans_shape_fwhm_hi = None     # [pix] ... and one above this; None: twice the window's side
+trans_fwhm_gauss_min = None    # rows without a Gauss fit or with FWHM_GAUSS_D below this are dropped (T-NVET); None: no bound
+trans_fwhm_gauss_max = None    # ... above this
+trans_elong_gauss_max = None   # ... or with ELONG_GAUSS_D above this
+
 # ---- flux ratio and dx, dy from matched stars (buildref.py:2782-3014 get_fratio; [EXT] zogy.get_fratio_dxdy) ----
 # Off by default: the subtraction then takes the caller's fratio, dx, dy (--fratio --zogy_dx --zogy_dy) as before.
 zogy_match = False             # measure fratio, dx, dy per sub-image from the stars matched between new frame and reference

@@ -1037,9 +1037,100 @@ def trans_fit_header(on, fit_size=None, rows=None, fold=None):
     return h
 
 
-def vet_transients(rows, chi2_max):
-    """the rows that pass --trans_chi2_max: those with a fit (no TRANS_NO_FIT) and chi2_psf_d <= chi2_max -> (kept rows, their indices)"""
-    keep = [i for i, r in enumerate(rows) if not r['flags_psf_d'] & TRANS_NO_FIT and r['chi2_psf_d'] <= chi2_max]
+TRANS_SHAPE_REFUSED = 16                                             # FLAGS_GAUSS_D / FLAGS_MOFFAT_D: bits 1 2 4 8 as above, and this (bbx_trans_shapefit)
+SHAPE_GAUSS, SHAPE_MOFFAT = 1, 2                                     # `models` of bbx_trans_shapefit
+SHAPE_OUT = ('y', 'x', 'yerr', 'xerr', 'fwhm', 'elong', 'chi2')      # the planes of its output
+
+
+def trans_shapefit(ctx, D, N, R, sig_n, sig_r, mask, fwhm0, ys, xs, scal, size, nsx, fit_size=None, niter=None, maxshift=None, models=3,
+                   beta=None, fwhm_lo=None, fwhm_hi=None, d_peaks=None):
+    """bbx_trans_shapefit: an elliptical Gaussian and an elliptical Moffat (beta fixed) fitted to D in the window of trans_psffit
+    (fit_size x fit_size pixels around every candidate's integer peak, the same used pixels and V_D) by Levenberg-Marquardt.  The
+    arguments are trans_psffit's, but for fwhm0 (device float32 [nsub]: the FWHM the fits start with in every sub-image) in the
+    place of the P_D stamps; fit_size, niter, maxshift, beta, fwhm_lo, fwhm_hi: settings.trans_shape_* / trans_moffat_beta (fwhm_hi
+    None: twice the window's side); models: SHAPE_GAUSS | SHAPE_MOFFAT
+    -> device (out float32 [2, 7, n]: per model (Gauss, Moffat) the planes SHAPE_OUT, y and x relative to the integer peak;
+    flags uint8 [2, n]: TRANS_AT_BOUND | TRANS_MASKED | TRANS_NO_FIT | TRANS_NOT_CONVERGED | TRANS_SHAPE_REFUSED).  No host wait"""
+    ny, nx = D.shape
+    for f in (D, N, R):
+        if f.dim() != 2 or f.dtype != torch.float32 or not f.is_contiguous() or tuple(f.shape) != (ny, nx):
+            raise ValueError('contiguous 2-D float32 frames of one shape expected')
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (ny, nx) or not mask.is_contiguous()):
+        raise ValueError('the mask must be a contiguous uint8 frame of the image shape')
+    mini = isinstance(sig_n, MiniImage)
+    if mini != isinstance(sig_r, MiniImage):
+        raise ValueError('the two sigma maps must be of one form: two frames or two MiniImage')
+    if not mini:
+        for f in (sig_n, sig_r):
+            if f.dtype != torch.float32 or tuple(f.shape) != (ny, nx) or not f.is_contiguous():
+                raise ValueError('sigma: contiguous float32 frames of the image shape or MiniImage expected')
+    scal = np.ascontiguousarray(scal, dtype=np.float32)
+    if scal.ndim != 2 or scal.shape[1] != 6:
+        raise ValueError('scal [nsub, 6] expected')
+    nsub = int(scal.shape[0])
+    if not torch.is_tensor(fwhm0) or fwhm0.dtype != torch.float32 or tuple(fwhm0.shape) != (nsub,) or not fwhm0.is_contiguous():
+        raise ValueError('fwhm0: a contiguous float32 device tensor [nsub] expected')
+    ys, xs = np.asarray(ys), np.asarray(xs)
+    n = int(ys.size)
+    if d_peaks is not None:
+        d_ys, d_xs = d_peaks
+        if d_ys.dtype != torch.int32 or d_xs.dtype != torch.int32 or d_ys.numel() != n or d_xs.numel() != n:
+            raise ValueError('d_peaks: the int32 device copies of ys, xs expected')
+    else:
+        d_ys, d_xs = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
+    dev = ctx.device
+    out = torch.zeros((2, len(SHAPE_OUT), n), dtype=torch.float32, device=dev)
+    flags = torch.full((2, n), TRANS_NO_FIT, dtype=torch.uint8, device=dev)        # (what a call with models == 0 leaves)
+    W = int(settings.trans_shape_size if fit_size is None else fit_size)
+    hi = settings.trans_shape_fwhm_hi if fwhm_hi is None else fwhm_hi
+    check(lib.bbx_trans_shapefit(ctx.h, ny, nx, _p(D), _p(N), _p(R), None if mini else _p(sig_n), None if mini else _p(sig_r),
+                                 sig_n.ref() if mini else None, sig_r.ref() if mini else None, _p(mask) if mask is not None else None, nsub,
+                                 int(size), int(nsx), scal.ctypes.data_as(C.POINTER(C.c_float)), _p(fwhm0), n, _p(d_ys), _p(d_xs), W,
+                                 int(settings.trans_shape_niter if niter is None else niter),
+                                 float(settings.trans_shape_maxshift if maxshift is None else maxshift), int(models),
+                                 float(settings.trans_moffat_beta if beta is None else beta),
+                                 float(settings.trans_shape_fwhm_lo if fwhm_lo is None else fwhm_lo), float(2 * W if hi is None else hi),
+                                 _p(out), _p(flags), ctx.stream()), 'bbx_trans_shapefit', ctx.h)
+    return out, flags
+
+
+_trans_shapefit = trans_shapefit                                     # (_optimal_subtraction's switch bears the name)
+
+
+def shape_start_fwhm(sub_pn, sub_pr):
+    """the FWHM the shape fits start with, per sub-image: 2.3548 x the larger window_sigma of the two PSF stamps; device float32
+    [nsub], no fetch"""
+    return (2.3548 * torch.maximum(window_sigma(sub_pn), window_sigma(sub_pr))).to(torch.float32).contiguous()
+
+
+def trans_shape_header(on, fit_size=None, beta=None, rows=None):
+    """the keys of `_trans_hdr.fits` for the Gauss and Moffat fits to D: T-SHAPE, and with it T-SHPSZ, T-MBETA, T-NGAUS, T-NMOFF (rows
+    with flags & 12 == 0), T-FWGMD, T-ELGMD (the medians over the converged Gauss rows; 'None' without any)"""
+    h = {'T-SHAPE': (bool(on), 'Gauss and Moffat fitted to the transient candidates?')}
+    if on:
+        bad = TRANS_NO_FIT | TRANS_NOT_CONVERGED
+        good = [r for r in rows if not r['flags_gauss_d'] & bad]
+        h['T-SHPSZ'] = (int(fit_size), '[pix] side of the window of the Gauss and Moffat fits')
+        h['T-MBETA'] = (float(beta), 'beta of the Moffat fit (fixed)')
+        h['T-NGAUS'] = (len(good), 'number of candidates with a converged Gauss fit')
+        h['T-NMOFF'] = (sum(1 for r in rows if not r['flags_moffat_d'] & bad), 'number of candidates with a converged Moffat fit')
+        h['T-FWGMD'] = (float(np.median([r['fwhm_gauss_d'] for r in good])) if good else 'None', '[pix] median FWHM_GAUSS_D of the converged fits')
+        h['T-ELGMD'] = (float(np.median([r['elong_gauss_d'] for r in good])) if good else 'None', 'median ELONG_GAUSS_D of the converged fits')
+    return h
+
+
+def vet_transients(rows, chi2_max=None, fwhm_gauss_min=None, fwhm_gauss_max=None, elong_gauss_max=None):
+    """the rows that pass the vetting -> (kept rows, their indices).  chi2_max (--trans_chi2_max): those with a fit of P_D (no
+    TRANS_NO_FIT) and chi2_psf_d <= chi2_max.  With any of the Gauss bounds (--trans_fwhm_gauss_min / _max, --trans_elong_gauss_max):
+    those with a Gauss fit (no TRANS_NO_FIT) inside every bound given"""
+    keep = list(range(len(rows)))
+    if chi2_max is not None:
+        keep = [i for i in keep if not rows[i]['flags_psf_d'] & TRANS_NO_FIT and rows[i]['chi2_psf_d'] <= chi2_max]
+    if fwhm_gauss_min is not None or fwhm_gauss_max is not None or elong_gauss_max is not None:
+        keep = [i for i in keep if not rows[i]['flags_gauss_d'] & TRANS_NO_FIT
+                and (fwhm_gauss_min is None or rows[i]['fwhm_gauss_d'] >= fwhm_gauss_min)
+                and (fwhm_gauss_max is None or rows[i]['fwhm_gauss_d'] <= fwhm_gauss_max)
+                and (elong_gauss_max is None or rows[i]['elong_gauss_d'] <= elong_gauss_max)]
     return [rows[i] for i in keep], keep
 
 
@@ -1339,7 +1430,9 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          thumbnail_pngs=False, ref_rows=None, ref_psf=None, match=False, ref_catalog=None, match_dist=None, match_nmin=None,
                          match_snr_min=None, shapes=False, shape_snr_min=None, psf_build=False, psf_size=None, psf_poldeg=None,
                          phot_centroid=False, objmask=False, objmask_nsigma=None, objmask_minarea=None, objmask_grow=None,
-                         objmask_max_frac=None, trans_psffit=False, trans_fit_size=None, trans_chi2_max=None):
+                         objmask_max_frac=None, trans_psffit=False, trans_fit_size=None, trans_chi2_max=None,
+                         trans_shapefit=False, trans_shape_size=None, trans_fwhm_gauss_min=None, trans_fwhm_gauss_max=None,
+                         trans_elong_gauss_max=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -1413,6 +1506,13 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       T-PDFOLD, T-CHI2MD (trans_fit_header).  trans_chi2_max: rows without a fit or with a chi2 above it are
                       dropped, with their thumbnails; T-NVET = the rows kept, T-NTRANS stays.  An exception in the stage:
                       today's table, T-PSFD False.  False: no kernel of bbx_transfit.hip is launched, no such keys
+      trans_shapefit: True (same conditions, with or without trans_psffit): an elliptical Gaussian and an elliptical Moffat are fitted
+                      to D at every candidate (bbx_trans_shapefit; trans_shape_size: settings), queued behind the fit of P_D or
+                      the peak search and read in the same copy back: every transient gains x_, xerr_, y_, yerr_, fwhm_, elong_,
+                      chi2_, flags_gauss_d and the same eight of _moffat_d; header_trans gets T-SHAPE, T-SHPSZ, T-MBETA, T-NGAUS,
+                      T-NMOFF, T-FWGMD, T-ELGMD (trans_shape_header).  trans_fwhm_gauss_min / _max, trans_elong_gauss_max: rows
+                      without a Gauss fit or outside a bound are dropped, with their thumbnails (T-NVET).  An exception in the
+                      stage: today's table, T-SHAPE False.  False: bbx_trans_shapefit is not launched, no such keys
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
             header (= header_new additions), header_trans)"""
     size = subimage_size or settings.subimage_size
@@ -1752,6 +1852,19 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             import logging
             logging.getLogger(__name__).warning('fit of P_D to the transient candidates failed: %s', e)
             d_tf = None
+    d_ts = None
+    shape_size = int(settings.trans_shape_size if trans_shape_size is None else trans_shape_size)
+    if trans_shapefit:
+        hdr_t['T-SHAPE'] = trans_shape_header(False)['T-SHAPE']      # until the fits have been read back
+    if trans_shapefit and tys.size and sub_pn is not None and sub_pr is not None and tuple(sub_pn.shape) == tuple(sub_pr.shape):
+        try:
+            sh_out, sh_fl = _trans_shapefit(ctx, res['D'], res['data_bkgsub'], res['ref_bkgsub'], bstd, rbstd, new_mask,
+                                            shape_start_fwhm(sub_pn, sub_pr), tys, txs, scal, size, nsx, fit_size=shape_size)
+            d_ts = torch.cat([sh_out.reshape(-1), sh_fl.to(torch.float32).reshape(-1)])
+        except Exception as e:                                       # the frame keeps today's table
+            import logging
+            logging.getLogger(__name__).warning('Gauss and Moffat fits to the transient candidates failed: %s', e)
+            d_ts = None
     if want_thumbs:
         # the cut-outs of the four frames, which are all still in HBM, and the mask flags under each peak in one pass; the
         # display planes from the cut-outs.  The reference's mask counts only where it shares the new frame's grid
@@ -1763,12 +1876,13 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                             frame_clipped_stats_enqueue(ctx, res['Fpsferr'], new_mask)])
     if d_fl is not None and not d_fl.numel():
         d_fl = None
-    back = [t for t in (d_fe, d_st, d_fl, d_tf) if t is not None]
+    back = [t for t in (d_fe, d_st, d_fl, d_tf, d_ts) if t is not None]
     got = (fetch(ctx, *back) if len(back) > 1 else [fetch(ctx, back[0])]) if back else []
     fe = got.pop(0) if d_fe is not None else None
     st = got.pop(0) if d_st is not None else None
     fl = got.pop(0) if d_fl is not None else None
     tf = got.pop(0) if d_tf is not None else None
+    ts = got.pop(0) if d_ts is not None else None
     if tys.size:
         res['transients'] = [dict(y=y, x=x, scorr=sc, fpsf=f, fpsferr=e)
                              for y, x, sc, f, e in zip(tys.tolist(), txs.tolist(), tsc.tolist(), fe[0].tolist(), fe[1].tolist())]
@@ -1785,12 +1899,26 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             if len(fold) and float(np.max(fold)) > PD_FOLD_WARN:
                 import logging
                 logging.getLogger(__name__).warning('P_D leaves %.3g of its |sum| outside its stamp (T-PDFOLD)', float(np.max(fold)))
-            if trans_chi2_max is not None:
-                res['transients'], keep = vet_transients(res['transients'], float(trans_chi2_max))
-                for k in ('thumbnails', 'thumbnail_png8'):
-                    if k in res:
-                        res[k] = res[k][torch.as_tensor(keep, dtype=torch.int64, device=res[k].device)]
-                hdr_t['T-NVET'] = (len(keep), 'number of transient candidates that passed the vetting')
+        if ts is not None:
+            n = int(tys.size)
+            planes, sfl = ts[:14 * n].reshape(2, 7, n), ts[14 * n:].reshape(2, n)
+            for m, name in enumerate(('gauss', 'moffat')):
+                for i, d in enumerate(res['transients']):
+                    d.update({'x_%s_d' % name: float(d['x'] + planes[m, 1, i]), 'xerr_%s_d' % name: float(planes[m, 3, i]),
+                              'y_%s_d' % name: float(d['y'] + planes[m, 0, i]), 'yerr_%s_d' % name: float(planes[m, 2, i]),
+                              'fwhm_%s_d' % name: float(planes[m, 4, i]), 'elong_%s_d' % name: float(planes[m, 5, i]),
+                              'chi2_%s_d' % name: float(planes[m, 6, i]), 'flags_%s_d' % name: int(sfl[m, i])})
+            hdr_t.update(trans_shape_header(True, shape_size, settings.trans_moffat_beta, res['transients']))
+        # the vetting: the chi2 bound needs the fit of P_D, the Gauss bounds the shape fits
+        bounds = dict(chi2_max=trans_chi2_max if tf is not None else None)
+        if ts is not None:
+            bounds.update(fwhm_gauss_min=trans_fwhm_gauss_min, fwhm_gauss_max=trans_fwhm_gauss_max, elong_gauss_max=trans_elong_gauss_max)
+        if any(v is not None for v in bounds.values()):
+            res['transients'], keep = vet_transients(res['transients'], **{k: None if v is None else float(v) for k, v in bounds.items()})
+            for k in ('thumbnails', 'thumbnail_png8'):
+                if k in res:
+                    res[k] = res[k][torch.as_tensor(keep, dtype=torch.int64, device=res[k].device)]
+            hdr_t['T-NVET'] = (len(keep), 'number of transient candidates that passed the vetting')
     else:
         res['transients'] = []
     hdr['Z-P'] = (True, 'successfully processed by ZOGY?')

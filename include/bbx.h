@@ -955,6 +955,39 @@ int bbx_trans_psffit(bbx_ctx *ctx, int ny, int nx, const float *d_D, const float
                      float maxshift, float *d_flux, float *d_err, float *d_dy, float *d_dx, float *d_chi2,
                      uint8_t *d_flags, void *stream);
 
+/* ---- transient vetting: an elliptical Gaussian and an elliptical Moffat fitted to D per candidate (bbx_transfit.hip, DESIGN.md
+ * 4k).  zogy fits both to D at every candidate (X/Y_GAUSS_D, FWHM_GAUSS_D, ELONG_GAUSS_D, CHI2_GAUSS_D and the same of _MOFFAT_D)
+ * ([EXT]: zogy is not in the reference tree; the rules below are THIS PROJECT'S OWN, parity is unpinned).
+ *
+ * bbx_trans_shapefit: per candidate c < ncand the window of bbx_trans_psffit, by the same device function: the same sub-image
+ * k, used pixels, V_D in float32, sigma forms, mask rule and flag 2; W odd, 5 <= W <= 39 (no stamp is involved).
+ *  - model m = B + A g(q), q = cyy dy^2 + 2 cxy dy dx + cxx dx^2, dy = y - y0, dx = x - x0 relative to the integer peak;
+ *    g = exp(-q / 2) (Gauss) or (1 + q)^-beta (Moffat, beta > 1 given by the caller); seven parameters (A, B, y0, x0, cyy, cxy, cxx);
+ *  - start: A = D at the peak pixel, or at the used pixel of largest |D| (the first in row-major order) if the peak is not used;
+ *    B = y0 = x0 = 0; cyy = cxx = 4 kk / f0^2, cxy = 0 with f0 = d_fwhm0[k] (DEVICE array [nsub]) clamped to [fwhm_lo, fwhm_hi]
+ *    and kk = 2 ln 2 (Gauss), 2^(1 / beta) - 1 (Moffat);
+ *  - Levenberg-Marquardt, niter times (1 .. 128, never fewer on the data's account), all in float64 on the float32 D and V_D of
+ *    the window: H = sum J J^T / V, g = sum J r / V, chi2 = sum r^2 / V (analytic J; 28 + 7 + 1 sums in a fixed order, no atomics);
+ *    (H + lambda diag H) delta = g by Cholesky, a pivot that is not positive and finite refuses the step; trial = p + delta, y0 and
+ *    x0 clamped to +-maxshift; refused for its shape (flag 16 if it is the last) if p + delta is not finite, the form is not
+ *    positive definite or an axis FWHM = 2 sqrt(kk / l) (l: eigenvalue of the form) lies outside [fwhm_lo, fwhm_hi]; else accepted
+ *    if chi2(trial) is finite and <= chi2.  Accepted: lambda = max(lambda / 10, 1e-9); refused: min(10 lambda, 1e9); lambda_0 = 1e-3;
+ *  - d_out[model][7][ncand] float32, model 0 Gauss, 1 Moffat: y0, x0, their errors (sqrt of the diagonal of the undamped H^-1 at the
+ *    final parameters), FWHM (geometric mean of the two axes), ELONG = sqrt(l1 / l2), chi2 / (n_used - 7).
+ * d_flags[model][ncand] u8 = 1 (|y0| or |x0| at maxshift) | 2 (a masked pixel was left out) | 4 (no fit: the peak off the frame,
+ * n_used < 8, d_fwhm0[k] not positive and finite, the final H not invertible, a result not finite, or the model not asked for in
+ * `models` (1 Gauss | 2 Moffat); all seven outputs 0) | 8 (no step was ever accepted, or a parameter of the last accepted step moved
+ * by more than 0.01 of its own error, errors from the undamped H at the point the step left) | 16 (the last trial was refused for
+ * its shape).  A negative candidate fits a negative A.  One wave per candidate, four candidates per workgroup, the windows in LDS
+ * (48.7 KB); sums per lane over pixels lane, lane + 64, ..., then the wave: same input, same bits.  ncand == 0 or models == 0:
+ * nothing is launched.  h_scal: HOST array [nsub][6] as above, staged in a workspace slot of its own.                       */
+int bbx_trans_shapefit(bbx_ctx *ctx, int ny, int nx, const float *d_D, const float *d_N, const float *d_R,
+                       const float *d_sig_n, const float *d_sig_r, const bbx_spline_image *mini_n,
+                       const bbx_spline_image *mini_r, const uint8_t *d_mask, int nsub, int size, int nsx, const float *scal,
+                       const float *d_fwhm0, int ncand, const int32_t *d_ys, const int32_t *d_xs, int W, int niter,
+                       float maxshift, int models, float beta, float fwhm_lo, float fwhm_hi, float *d_out, uint8_t *d_flags,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
