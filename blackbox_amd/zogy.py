@@ -1288,14 +1288,15 @@ def variance(ctx, data_bkgsub, bkg_std):
     return v
 
 
-def remap_mini(mini, grid, shape_in, box, step):
+def remap_mini(mini, grid, shape_in, box, step, shape_out=None):
     """a mini (per-box) image of the reference frame sampled on the new frame's box centres:
     bilinear interpolation of [mini] at the reference-frame positions that the projection
     lattice [grid] (coadd.projection_grid: [gny][gnx][2] = x, y input position of the output
     pixels (j*step, i*step)) assigns to the centres of the new frame's boxes.  Host, float64:
-    176 x 176 values."""
+    176 x 176 values.  shape_out: the new frame's shape: the result has the new frame's boxes (None: as many as the reference's
+    mini image has, which is the same thing only for two frames of one shape)."""
     mini = np.asarray(mini, np.float64)
-    nby, nbx = mini.shape
+    nby, nbx = mini.shape if shape_out is None else (shape_out[0] // box, shape_out[1] // box)
     cy = (np.arange(nby) + 0.5) * box - 0.5
     cx = (np.arange(nbx) + 0.5) * box - 0.5
     gy, gx = cy / step, cx / step
@@ -1619,7 +1620,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             from . import coadd
             ones = torch.ones_like(rwork)
             rwork, _ = coadd.resample(ctx, rwork, ones, ref_grid, (ny, nx), 1.0, ref_grid_step)
-            sdr = remap_mini(sdr, np.asarray(ref_grid), (rny, rnx), box, ref_grid_step)
+            sdr = remap_mini(sdr, np.asarray(ref_grid), (rny, rnx), box, ref_grid_step, shape_out=(ny, nx))
         elif (rny, rnx) != (ny, nx):
             raise ValueError('reference frame of another shape needs ref_grid')
         # co-added reference: no channel structure in its noise -> interpolation across the frame
