@@ -92,6 +92,19 @@ def _start_sampler(path):
     return th
 
 
+def align_keywords(a, S, tel=None):
+    """the keywords --ref_align adds to the subtraction's: the switch, and the align_* settings with the command line over them
+    (only degrees 1 and 2)"""
+    kw = dict(ref_align=True)
+    for key, arg in (('align_poldeg', 'align_poldeg'), ('align_max_shift', 'align_max_shift'), ('align_bin', 'align_bin'),
+                     ('align_nbright', None), ('align_rounds', None)):
+        v = getattr(a, arg, None) if arg else None
+        kw[key] = S.get_par(getattr(S, key), tel) if v is None else v
+    if kw['align_poldeg'] not in (1, 2):
+        raise ValueError('--align_poldeg: degree 1 or 2, got {}'.format(kw['align_poldeg']))
+    return kw
+
+
 def str2bool(v):
     """blackbox.py:8115-8123"""
     if isinstance(v, bool):
@@ -406,6 +419,9 @@ class Reducer:
             if par(a.zogy_match, 'zogy_match'):
                 sub['match'] = True
                 sub['match_dist'] = par(a.match_dist, 'match_dist_pix')
+            # the reference registered on the new frame from the stars of both; the keywords are only passed when switched on
+            if par(a.ref_align, 'ref_align'):
+                sub.update(align_keywords(a, S, self.tel))
             # the PSF of D fitted to every transient candidate; the keywords are only passed when switched on
             if par(a.trans_psffit, 'trans_psffit'):
                 sub['trans_psffit'] = True
@@ -1187,6 +1203,15 @@ def build_parser():
                          'Z-DX, Z-DY and Z-DXSTD, Z-DYSTD, Z-FNRSTD, Z-FNRERR); --fratio --zogy_dx --zogy_dy are the fallback '
                          '(default: settings.zogy_match)')
     ap.add_argument('--match_dist', type=float, default=None, help='[pix] largest distance of a star match (settings.match_dist_pix)')
+    ap.add_argument('--ref_align', type=str2bool, default=None,
+                    help='register --ref (any shape) on the new frame from the stars of both instead of taking it to lie on the new '
+                         'frame\'s pixel grid: A-P A-PLDG A-NVOTE A-NRUN A-NFAR A-NPAIR A-RMSX A-RMSY A-DX A-DY A-ROT A-SCALE A-FLAGS A-NEDGE '
+                         'T-NOFFR in the header of _trans; a registration that fails leaves the new-only products (default: settings.ref_align)')
+    ap.add_argument('--align_poldeg', type=int, choices=(1, 2), default=None,
+                    help='--ref_align: degree of the transform\'s polynomial, 1 or 2 (settings.align_poldeg)')
+    ap.add_argument('--align_max_shift', type=float, default=None,
+                    help='[pix] --ref_align: largest offset new - ref the vote looks for (settings.align_max_shift)')
+    ap.add_argument('--align_bin', type=float, default=None, help='[pix] --ref_align: bin of the vote\'s histogram (settings.align_bin)')
     ap.add_argument('--subimage_size', type=int, default=None)
     ap.add_argument('--flat_norm_sec', type=section, default=None,
                     help='y0:y1,x0:x1: flat normalisation / statistics section (default set_bb.flat_norm_sec of the telescope)')

@@ -153,6 +153,14 @@ SIGNATURES = {
                               _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'bbx_trans_shapefit': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _pf, _vp, _i, _vp, _vp, _i, _i, _f, _i, _f, _f, _f,
                                 _vp, _vp, _vp]),
+    'bbx_align_vote_bytes': (C.c_size_t, [_i, C.c_double, C.c_double, _i]),
+    'bbx_align_vote': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, _i, _i, _i, _vp, C.c_size_t,
+                            _vp, _vp, _vp, _vp]),
+    'bbx_align_fit': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _f, C.c_double, _i, _vp, _vp,
+                           _vp, _vp]),
+    'bbx_align_apply': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'bbx_align_grid': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'bbx_remap_mask': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError if the export is missing

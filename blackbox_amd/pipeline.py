@@ -332,6 +332,7 @@ class FramePipeline:
         self.ref_rows = None                                         # zogy.RefRows of the run's reference (made with ref_bkg_std)
         self.ref_psf = None                                          # zogy.RefPsf of the run's reference PSF (made with them; BBX_REF_PSF=0: none)
         self.ref_catalog = None                                      # zogy.RefCatalog of the run's reference (star match; made with them)
+        self.ref_stars = None                                        # zogy.RefStars of the run's reference (ref_align: its stars on its own grid)
         self._ref_lock = threading.Lock()                            # one lane makes the two and hands them over
         self.zogy_gate = None
         self.fpack_in_gate = os.environ.get('BBX_FPACK_GATE', '0') == '1'
@@ -457,7 +458,7 @@ class FramePipeline:
                 lib.bbx_event_destroy(sl[k])
         self.slots = []
         self.lane_out = None
-        self.ref_rows = self.ref_psf = self.ref_bkg_std = self.ref_catalog = None
+        self.ref_rows = self.ref_psf = self.ref_bkg_std = self.ref_catalog = self.ref_stars = None
         self.arena.close()
         for c in self.own_ctx:
             c.close()
@@ -672,10 +673,19 @@ class FramePipeline:
         if self.subtract is not None:
             from . import zogy as G
             try:
+                align = bool(self.subtract.get('ref_align'))
+                more = dict(ref_stars=self.ref_stars) if align else {}
                 sub = G.optimal_subtraction(ctx, data, new_mask=mask, zogy_gate=self.zogy_gate, ref_bkg_std=self.ref_bkg_std,
-                                            ref_rows=self.ref_rows, ref_psf=self.ref_psf, ref_catalog=self.ref_catalog, **self.subtract)
+                                            ref_rows=self.ref_rows, ref_psf=self.ref_psf, ref_catalog=self.ref_catalog, **more, **self.subtract)
+                if align and self.ref_stars is None and sub.get('ref_stars') is not None:
+                    # the reference's star list on its own grid is the same for every frame of the run (the registered
+                    # reference is not: every frame has its own lattice, so nothing below is kept)
+                    with self._ref_lock:
+                        if self.ref_stars is None:
+                            check(lib.bbx_wait(ctx.h, ctx.sp), 'bbx_wait', ctx.h)
+                            self.ref_stars = sub['ref_stars']
                 if (self.ref_bkg_std is None and self.subtract.get('ref_is_bkgsub') and self.subtract.get('ref_bkg_std_mini') is not None
-                        and self.subtract.get('ref_grid') is None and 'bkg_std_ref' in sub):
+                        and self.subtract.get('ref_grid') is None and not align and 'bkg_std_ref' in sub):
                     with self._ref_lock:
                         if self.ref_bkg_std is None:
                             # the reference's sigma image is the same for every frame of the run: made once, on whichever lane

@@ -113,6 +113,16 @@ match_snr_min = 20.0           # flux / fluxerr a star needs on both sides to en
 centroid_radius = 6            # [pix] the windowed centroid reads (2 * radius + 1)^2 pixels around the integer peak
 centroid_niter = 8             # iterations of the windowed centroid
 
+# ---- registration of the reference on the new frame from the two star lists (bbx_align.hip; [EXT] SWarp and two
+# astrometric solutions in zogy: the method is this project's own) ----
+# Off by default: --ref is taken to lie on the new frame's pixel grid (or the caller gives ref_grid), as before.
+ref_align = False              # register --ref (any shape) on the new frame from the stars of both; the A-* keys, T-NOFFR
+align_poldeg = 1               # degree of the transform's polynomial, 1 or 2
+align_max_shift = 256.0        # [pix] largest offset new - ref the vote looks for, in either axis
+align_bin = 4.0                # [pix] bin of the vote's histogram of pair differences
+align_nbright = 2048           # sources of each list that vote (at most 2048)
+align_rounds = 3               # rounds of (reference list through T^-1, match, fit) behind the vote
+
 # ---- source shapes of `_cat.fits` and the frame's seeing statistics (header keys S-NOBJ S-FWHM S-FWSTD S-SEEING S-SEESTD
 # S-ELONG S-ELOSTD, blackbox.py:3051-3057; [EXT] SExtractor in zogy: adaptive second moments here) ----
 # Off by default: `_cat.fits` keeps its seven columns and the header gets none of the keys.

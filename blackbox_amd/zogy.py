@@ -588,6 +588,263 @@ def match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, dis
     return d_tab, (d_match >= 0).sum().reshape(1)
 
 
+# ---- registration of the reference on the new frame from the two star lists (bbx_align.hip) ---------
+# [EXT] zogy registers with SWarp and two astrometric solutions; the method and its rules are this project's own, stated in
+# float64 numpy by tests/test_align_host.py.  A list is (ys int32, xs int32, off float32 [n, 2], flux float32, err float32) on
+# the device; T maps new-frame to reference pixels, coef float64 [12].
+ALIGN_PAIR_CAP, ALIGN_NMIN, ALIGN_FAR, ALIGN_CLIP = 8192, 15, 8, 3.0
+ALIGN_VOTE_FAILED, ALIGN_FEW_PAIRS, ALIGN_NOT_PD, ALIGN_DET = 1, 2, 4, 8          # the flag word
+
+
+def _expect_list(lst, name, n_cols=5):
+    """a star list crosses the C ABI as bare pointers: every column is checked against the list's length here"""
+    from .reduce import _expect
+    n = int(lst[0].numel())
+    for t, dt, shape, col in zip(lst[:n_cols], (torch.int32, torch.int32, torch.float32, torch.float32, torch.float32),
+                                 ((n,), (n,), (n, 2), (n,), (n,)), ('ys', 'xs', 'off', 'flux', 'err')):
+        _expect(t, dt, shape, '{} {}'.format(name, col))
+    return n
+
+
+def align_vote(ctx, a, b, nbright=None, max_shift=None, bin=None, nmin=ALIGN_NMIN, far=ALIGN_FAR, cap=ALIGN_PAIR_CAP):
+    """bbx_align_vote of the lists a, b = (ys, xs, off, flux[, ...]) -> device (info int32 [8], coarse float64 [2] = (dy, dx),
+    pairs int32 [cap, 2]; (-1, -1) past info[4] pairs).  No host wait"""
+    nbright = settings.align_nbright if nbright is None else nbright
+    max_shift = settings.align_max_shift if max_shift is None else max_shift
+    bin = settings.align_bin if bin is None else bin
+    n_a, n_b = _expect_list(a, 'list a', 4), _expect_list(b, 'list b', 4)
+    nbytes = int(lib.bbx_align_vote_bytes(int(nbright), float(max_shift), float(bin), int(cap)))
+    if nbytes == 0:
+        raise ValueError('align_vote: nbright {} (1 .. 2048), cap {} (1 .. 8192), max_shift {} or bin {} out of range'.format(nbright, cap, max_shift, bin))
+    dev = ctx.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    info = torch.empty(8, dtype=torch.int32, device=dev)
+    coarse = torch.empty(2, dtype=torch.float64, device=dev)
+    pairs = torch.empty((int(cap), 2), dtype=torch.int32, device=dev)
+    check(lib.bbx_align_vote(ctx.h, n_a, *[_p(t) for t in a[:4]], n_b, *[_p(t) for t in b[:4]], int(nbright), float(max_shift), float(bin),
+                             int(nmin), int(far), int(cap), _p(work), nbytes, _p(info), _p(coarse), _p(pairs), ctx.stream()),
+          'bbx_align_vote', ctx.h)
+    return info, coarse, pairs
+
+
+def align_fit(ctx, a, b, items, shape, poldeg, snr_min=None, clip=ALIGN_CLIP, nmin=ALIGN_NMIN):
+    """bbx_align_fit of the pairs items int32 [N, 2] (index into a, into b; -1: none) of the lists a, b (five columns each);
+    shape: the new frame's -> device (coef float64 [12], stats float64 [4] = n_used, rms_x, rms_y, flags; kept uint8 [N])"""
+    from .reduce import _expect
+    snr_min = settings.match_snr_min if snr_min is None else snr_min
+    if poldeg not in (1, 2):
+        raise ValueError('align_fit: degree 1 or 2, got {}'.format(poldeg))
+    n_a, n_b = _expect_list(a, 'list a'), _expect_list(b, 'list b')
+    N = int(items.shape[0])
+    _expect(items, torch.int32, (N, 2), 'items')
+    dev = ctx.device
+    coef = torch.empty(12, dtype=torch.float64, device=dev)
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    kept = torch.empty(N, dtype=torch.uint8, device=dev)
+    check(lib.bbx_align_fit(ctx.h, n_a, *[_p(t) for t in a[:5]], n_b, *[_p(t) for t in b[:5]], N, _p(items), int(shape[0]), int(shape[1]),
+                            int(poldeg), float(snr_min), float(clip), int(nmin), _p(coef), _p(stats), _p(kept), ctx.stream()),
+          'bbx_align_fit', ctx.h)
+    return coef, stats, kept
+
+
+def align_apply(ctx, b, coef, shape, poldeg):
+    """bbx_align_apply: the list b = (ys, xs, off) through the inverse of T (coef: device float64 [12]; shape: the new frame's)
+    -> device (ys int32, xs int32, off float32 [n, 2]), not sorted; a source T^-1 sends beyond 1e9 keeps its integers and gets
+    a NaN offset (it matches nothing)"""
+    from .reduce import _expect
+    if poldeg not in (1, 2):
+        raise ValueError('align_apply: degree 1 or 2, got {}'.format(poldeg))
+    n = _expect_list(b, 'list b', 3)
+    _expect(coef, torch.float64, (12,), 'coef')
+    dev = ctx.device
+    oys, oxs = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    ooff = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    check(lib.bbx_align_apply(ctx.h, n, _p(b[0]), _p(b[1]), _p(b[2]), _p(coef), int(shape[0]), int(shape[1]), int(poldeg), _p(oys), _p(oxs),
+                              _p(ooff), ctx.stream()), 'bbx_align_apply', ctx.h)
+    return oys, oxs, ooff
+
+
+def align_sort(ys, xs, off):
+    """(ys, xs, off) in (y, x) order of the integer peak, as bbx_match_mutual wants it, and the permutation that made it
+    (stable: equal peaks keep their list order).  Plumbing: a torch sort of the key y W + x and gathers"""
+    if not ys.numel():
+        return ys, xs, off, torch.empty(0, dtype=torch.int64, device=ys.device)
+    x64, y64 = xs.to(torch.int64), ys.to(torch.int64)
+    x0 = x64.min()
+    W = x64.max() - x0 + 1
+    perm = torch.sort(y64 * W + (x64 - x0), stable=True).indices
+    return ys[perm].contiguous(), xs[perm].contiguous(), off[perm].contiguous(), perm
+
+
+def align_grid_shape(shape, step):
+    """nodes of the lattice of a frame: one past the last pixel in both directions (coadd.projection_grid's count)"""
+    return -(-(int(shape[0]) + int(step)) // int(step)), -(-(int(shape[1]) + int(step)) // int(step))
+
+
+def align_grid(ctx, coef, shape, step=32):
+    """bbx_align_grid: T at the lattice nodes of the new frame -> device float64 [gny, gnx, 2] = (x, y), what coadd.resample
+    and remap_mask take as grid.  No host wait"""
+    from .reduce import _expect
+    _expect(coef, torch.float64, (12,), 'coef')
+    gny, gnx = align_grid_shape(shape, step)
+    grid = torch.empty((gny, gnx, 2), dtype=torch.float64, device=ctx.device)
+    check(lib.bbx_align_grid(ctx.h, _p(coef), int(shape[0]), int(shape[1]), int(step), gny, gnx, _p(grid), ctx.stream()), 'bbx_align_grid', ctx.h)
+    return grid
+
+
+def align_grid_host(coef, shape, step=32):
+    """the same lattice on the host, float64 numpy [gny, gnx, 2]: for remap_mini, which works there"""
+    c = np.asarray(coef, np.float64)
+    gny, gnx = align_grid_shape(shape, step)
+    hy, hx = 0.5 * shape[0], 0.5 * shape[1]
+    v, u = np.meshgrid((np.arange(gny) * float(step) - hy) / hy, (np.arange(gnx) * float(step) - hx) / hx, indexing='ij')
+    b = np.stack([np.ones_like(u), u, v, u * u, u * v, v * v], axis=-1)
+    return np.ascontiguousarray(np.stack([b @ c[:6], b @ c[6:12]], axis=-1))
+
+
+def remap_mask(ctx, mask, in_shape, grid, out_shape, step=32, edge=None):
+    """bbx_remap_mask: the mask (uint8 [in_shape] or None) of the reference on the new frame's grid through the lattice [grid]
+    (device float64 [gny, gnx, 2]) -> device (mask uint8 [out_shape] with the edge bit where the resampler has no footprint,
+    number of such pixels int64 [1]).  No host wait"""
+    from .reduce import _expect
+    edge = settings.mask_value['edge'] if edge is None else edge
+    in_ny, in_nx = int(in_shape[0]), int(in_shape[1])
+    out_ny, out_nx = int(out_shape[0]), int(out_shape[1])
+    if mask is not None:
+        _expect(mask, torch.uint8, (in_ny, in_nx), 'mask')
+    if not torch.is_tensor(grid) or grid.dim() != 3:
+        raise ValueError('remap_mask: the lattice as a device tensor [gny, gnx, 2] expected')
+    gny, gnx = int(grid.shape[0]), int(grid.shape[1])
+    _expect(grid, torch.float64, (gny, gnx, 2), 'grid')
+    out = torch.empty((out_ny, out_nx), dtype=torch.uint8, device=ctx.device)
+    nedge = torch.empty(1, dtype=torch.int64, device=ctx.device)
+    check(lib.bbx_remap_mask(ctx.h, in_ny, in_nx, _p(mask), out_ny, out_nx, _p(grid), gny, gnx, int(step), int(edge), _p(out), _p(nedge),
+                             ctx.stream()), 'bbx_remap_mask', ctx.h)
+    return out, nedge
+
+
+class RefStars:
+    """The reference's star list ON ITS OWN GRID, for the registration: the peaks of the background-subtracted reference above
+    cat_nsigma x the median of its sigma mini image, those on masked pixels dropped, with windowed centroids and PSF-weighted
+    fluxes, in (y, x) order on the device.  The PSF plane of a source is the one of its clamped tile (tile_index) among
+    sub_psfs [nsy * nsx, S, S]: only the S/N cut and the brightness ranking rest on it.  sigma: the reference's sigma frame
+    on its own grid.  Made once per run (host waits) and used while the reference tensor stays the same"""
+    builds = 0
+
+    def __init__(self, ctx, ref, sigma, ref_mask, sub_psfs, nsy, nsx, size, cat_nsigma=5.0, sigma_median=None, max_sources=200000,
+                 made_of=None):
+        from .reduce import _expect
+        rny, rnx = ref.shape
+        _expect(ref, torch.float32, (rny, rnx), 'reference')
+        _expect(sigma, torch.float32, (rny, rnx), 'reference sigma')
+        if ref_mask is not None:
+            _expect(ref_mask, torch.uint8, (rny, rnx), 'reference mask')
+        nsy, nsx = int(nsy), int(nsx)
+        _expect(sub_psfs, torch.float32, (nsy * nsx, sub_psfs.shape[1], sub_psfs.shape[1]), 'PSF stamps')
+        # made_of: the tensor the list is kept for, where [ref] is a background-subtracted copy of it made for this call
+        self.ref, self.shape = (ref if made_of is None else made_of), (rny, rnx)
+        thr = float(cat_nsigma) * float(sigma_median)
+        if np.isfinite(thr) and thr > 0:
+            ys, xs, pk = find_peaks_arrays(ctx, ref, thr, max_out=max_sources)
+        else:
+            ys = xs = np.zeros(0, np.int32); pk = np.zeros(0, np.float32)
+        keep = pk > 0
+        if ref_mask is not None and ys.size:
+            d_ys, d_xs = push(ctx, ys.astype(np.int64), xs.astype(np.int64))
+            keep &= fetch(ctx, ref_mask[d_ys, d_xs]) == 0
+        ys, xs = ys[keep], xs[keep]
+        self.n = int(ys.size)
+        dev = ctx.device
+        if self.n:
+            stamps = source_psfs(ctx, None, sub_psfs, ys, xs, nsx, size)
+            self.flux, self.err = psf_optflux(ctx, ref, sigma, stamps, ys, xs, v_is_sigma=True)
+            self.ys, self.xs = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
+            self.off = win_centroid(ctx, ref, self.ys, self.xs, window_sigma(sub_psfs), size, nsy, nsx)
+        else:
+            self.ys = self.xs = torch.empty(0, dtype=torch.int32, device=dev)
+            self.flux = self.err = torch.empty(0, dtype=torch.float32, device=dev)
+            self.off = torch.empty((0, 2), dtype=torch.float32, device=dev)
+        RefStars.builds += 1
+
+    def lists(self):
+        return self.ys, self.xs, self.off, self.flux, self.err
+
+    def matches(self, ref):
+        return ref is self.ref or (ref.data_ptr() == self.ref.data_ptr() and tuple(ref.shape) == self.shape)
+
+
+def align_header(fit=None, shape=None, poldeg=None, n_edge=None):
+    """the A-* keys of _trans_hdr.fits from the host copy of a registration: fit = dict(coef [12], n_used, rms_x, rms_y, flags,
+    info [8]); shape: the new frame's.  A-DX, A-DY: new - ref at the frame centre; A-ROT [deg] and A-SCALE from the linear part
+    in pixels.  No fit, or a flag word that is not 0: A-P False and the string 'None', set_qc's default, for the rest"""
+    keys = (('A-PLDG', 'degree of the registration polynomial'), ('A-NVOTE', 'votes of the winning offset block'),
+            ('A-NRUN', 'votes of the runner-up block'), ('A-NFAR', 'votes of the largest far block'),
+            ('A-NPAIR', 'star pairs in the last fit'), ('A-RMSX', '[pix] rms of the fit in x'), ('A-RMSY', '[pix] rms of the fit in y'),
+            ('A-DX', '[pix] x offset new - ref at the frame centre'), ('A-DY', '[pix] y offset new - ref at the frame centre'),
+            ('A-ROT', '[deg] rotation of ref against new'), ('A-SCALE', 'pixel scale new / ref'),
+            ('A-FLAGS', 'flags: 1 vote 2 pairs 4 singular 8 det'), ('A-NEDGE', 'pixels without reference coverage'))
+    ok = fit is not None and int(fit['flags']) == 0
+    hdr = {'A-P': (bool(ok), 'reference registered from its stars?')}
+    if not ok:
+        for k, c in keys:
+            hdr[k] = ('None', c)
+        if fit is not None:
+            hdr['A-FLAGS'] = (int(fit['flags']), keys[11][1])
+        return hdr
+    c = np.asarray(fit['coef'], np.float64)
+    hy, hx = 0.5 * shape[0], 0.5 * shape[1]
+    # the linear part in pixels: d(x_ref) / d(x_new) ... ; T(centre) = (c[0], c[6])
+    a11, a12, a21, a22 = c[1] / hx, c[2] / hy, c[7] / hx, c[8] / hy
+    info = np.asarray(fit['info'])
+    vals = (int(poldeg), int(info[0]), int(info[1]), int(info[7]), int(fit['n_used']), float(fit['rms_x']), float(fit['rms_y']),
+            float(hx - c[0]), float(hy - c[6]), float(np.degrees(np.arctan2(a21 - a12, a11 + a22))),
+            float(np.sqrt(abs(a11 * a22 - a12 * a21))), 0, int(n_edge) if n_edge is not None else 'None')
+    for (k, cm), v in zip(keys, vals):
+        hdr[k] = (v, cm)
+    return hdr
+
+
+def align_reference(ctx, new_lists, ref_stars, shape_new, shape_ref, ref_mask=None, poldeg=None, max_shift=None, bin=None, dist=None,
+                    snr_min=None, step=32, rounds=None, nbright=None):
+    """The registration of the reference on the new frame: new_lists = the new frame's (ys, xs, off, flux, err), sorted by
+    (y, x); ref_stars: a RefStars (or its five columns).  Queued on ctx's stream: the vote, the affine fit of its pairs, [rounds]
+    times (the reference's list through the inverse of T, sort, bbx_match_mutual, fit of degree poldeg), the lattice, the
+    reference's mask on the new frame's grid; then ONE host wait for coef, stats and info.
+    -> dict(grid, mask, coef, header, flags, n_edge, fit); flags != 0: grid and mask are None"""
+    poldeg = settings.align_poldeg if poldeg is None else int(poldeg)
+    rounds = settings.align_rounds if rounds is None else int(rounds)
+    dist = settings.match_dist_pix if dist is None else dist
+    if poldeg not in (1, 2):
+        raise ValueError('align_reference: degree 1 or 2, got {}'.format(poldeg))
+    a = tuple(new_lists)
+    b = tuple(ref_stars.lists()) if hasattr(ref_stars, 'lists') else tuple(ref_stars)
+    n_a = _expect_list(a, 'new list')
+    _expect_list(b, 'reference list')
+    info, coarse, pairs = align_vote(ctx, a, b, nbright, max_shift, bin)
+    coef, stats, _ = align_fit(ctx, a, b, pairs, shape_new, 1, snr_min)
+    ar = torch.arange(n_a, dtype=torch.int32, device=ctx.device)
+    for _ in range(rounds):
+        sy, sx, so, perm = align_sort(*align_apply(ctx, b[:3], coef, shape_new, poldeg))
+        m = match_mutual(ctx, a[:3], (sy, sx, so), dist)
+        if perm.numel():
+            ib = torch.where(m >= 0, perm[m.clamp(min=0).to(torch.int64)].to(torch.int32), torch.full_like(m, -1))
+        else:
+            ib = torch.full_like(m, -1)
+        items = torch.stack([torch.where(m >= 0, ar, torch.full_like(ar, -1)), ib], dim=1).contiguous()
+        coef, stats, _ = align_fit(ctx, a, b, items, shape_new, poldeg, snr_min)
+    grid = align_grid(ctx, coef, shape_new, step)
+    mask, nedge = remap_mask(ctx, ref_mask, shape_ref, grid, shape_new, step)
+    h_coef, h_stats, h_info, h_coarse, h_nedge = fetch(ctx, coef, stats, info, coarse, nedge)
+    flags = int(h_stats[3]) | int(h_info[5])
+    if not np.isfinite(h_coef).all():
+        flags |= int(h_stats[3]) or ALIGN_FEW_PAIRS
+    fit = dict(coef=h_coef, n_used=int(h_stats[0]), rms_x=float(h_stats[1]), rms_y=float(h_stats[2]), flags=flags, info=h_info, coarse=h_coarse)
+    ok = flags == 0
+    n_edge = int(h_nedge[0]) if ok else None
+    return dict(grid=grid if ok else None, mask=mask if ok else None, coef=h_coef, flags=flags, n_edge=n_edge, fit=fit,
+                header=align_header(fit, shape_new, poldeg, n_edge))
+
+
 # ---- source shapes of the catalogue and the frame's seeing / elongation statistics ---------
 # header keys S-NOBJ S-FWHM S-FWSTD S-SEEING S-SEESTD S-ELONG S-ELOSTD (blackbox.py:3051-3057; ranges set_qc.py:256-266).
 # [EXT] zogy takes them from SExtractor; here: adaptive second moments (include/bbx.h, DESIGN.md 4e), parity unpinned.
@@ -1169,7 +1426,7 @@ def psf_optflux_centroid(ctx, D, sigma, psf, sub_psfs, ys, xs, d_off, mask, nsx,
             raise ValueError('basis has %d planes, polynomial degree %d needs %d' % (cube.shape[0], psf['poldeg'], terms.shape[1]))
     else:
         cube = sub_psfs.contiguous()
-        idx = ((d_ys // int(size)) * int(nsx) + d_xs // int(size)).to(torch.int32)
+        idx = tile_index(d_ys, d_xs, size, int(cube.shape[0]) // int(nsx), nsx).to(torch.int32)
     if cube.dim() != 3 or cube.dtype != torch.float32 or cube.shape[1] != cube.shape[2]:
         raise ValueError('float32 PSF planes [n, S, S] expected')
     if not isinstance(sigma, MiniImage) and (sigma.dtype != torch.float32 or tuple(sigma.shape) != (ny, nx) or not sigma.is_contiguous()):
@@ -1333,13 +1590,26 @@ def subimage_psfs(ctx, psf, nsy, nsx, size):
     return psf.contiguous()
 
 
+def tile_index(ys, xs, size, nsy, nsx):
+    """index of the sub-image tile (size x size pixels, nsy x nsx tiles) of the integer peaks (ys, xs): numpy arrays or
+    tensors.  Clamped as the kernels clamp it (bbx_match.hip, k_win_centroid): min(max(y // size, 0), nsy - 1), likewise x -- a
+    peak of a frame that is no multiple of the tile (a reference on its own grid) takes the last tile, not one past the end
+    of the stamps.  For a frame of nsy size x nsx size pixels nothing changes"""
+    size, nsy, nsx = int(size), int(nsy), int(nsx)
+    if nsy < 1 or nsx < 1 or size < 1:
+        raise ValueError('tile_index: size, nsy, nsx must be positive, got {} {} {}'.format(size, nsy, nsx))
+    if torch.is_tensor(ys):
+        return torch.clamp(ys // size, 0, nsy - 1) * nsx + torch.clamp(xs // size, 0, nsx - 1)
+    return np.clip(np.asarray(ys) // size, 0, nsy - 1) * nsx + np.clip(np.asarray(xs) // size, 0, nsx - 1)
+
+
 def source_psfs(ctx, psf, sub_psfs, ys, xs, nsx, size):
     """unit-sum PSF stamp of every source: the PSFEx model at the source position, or the stamp
     of the sub-image the source falls in"""
     if isinstance(psf, dict):
         return psf_model_stamps(ctx, psf['basis'], np.asarray(xs) + 1.0, np.asarray(ys) + 1.0, psf['polzero'],
                                 psf['polscal'], psf['poldeg'])
-    k = push(ctx, ((np.asarray(ys) // size) * nsx + (np.asarray(xs) // size)).astype(np.int64))
+    k = push(ctx, tile_index(np.asarray(ys), np.asarray(xs), size, int(sub_psfs.shape[0]) // int(nsx), nsx).astype(np.int64))
     return sub_psfs.index_select(0, k).contiguous()
 
 
@@ -1433,7 +1703,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          phot_centroid=False, objmask=False, objmask_nsigma=None, objmask_minarea=None, objmask_grow=None,
                          objmask_max_frac=None, trans_psffit=False, trans_fit_size=None, trans_chi2_max=None,
                          trans_shapefit=False, trans_shape_size=None, trans_fwhm_gauss_min=None, trans_fwhm_gauss_max=None,
-                         trans_elong_gauss_max=None):
+                         trans_elong_gauss_max=None, ref_align=False, align_poldeg=None, align_max_shift=None, align_bin=None,
+                         align_nbright=None, align_rounds=None, ref_stars=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -1514,6 +1785,18 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       T-NMOFF, T-FWGMD, T-ELGMD (trans_shape_header).  trans_fwhm_gauss_min / _max, trans_elong_gauss_max: rows
                       without a Gauss fit or outside a bound are dropped, with their thumbnails (T-NVET).  An exception in the
                       stage: today's table, T-SHAPE False.  False: bbx_trans_shapefit is not launched, no such keys
+      ref_align     : True (with a reference of any shape and both PSFs; a caller's ref_grid with it is a ValueError): the reference
+                      is registered on the new frame from the stars of both (align_reference): the new frame's
+                      photometry and centroids first, then the reference's list on its own grid (RefStars: ref_stars where the
+                      caller keeps one of this very reference, else made here and returned as res['ref_stars']), the transform, its
+                      lattice -- which takes the place of ref_grid -- and the reference's mask on the new frame's grid, which
+                      takes the place of ref_mask (res['ref_mask_remapped']).  One more host wait.  Transient candidates whose peak
+                      has no reference under it (the mask's edge bit) are dropped with their thumbnails: T-NOFFR; T-NTRANS stays.
+                      res['align'] = align_reference's dict; header_trans gets A-P, A-PLDG, A-NVOTE, A-NRUN, A-NFAR, A-NPAIR, A-RMSX,
+                      A-RMSY, A-DX, A-DY, A-ROT, A-SCALE, A-FLAGS, A-NEDGE.  A registration that fails (flag word not 0, or an exception
+                      in the stage): the frame goes on as one without a reference, A-P False -- it is never subtracted unregistered.
+                      align_poldeg, align_max_shift, align_bin, align_nbright, align_rounds: settings.  False: no kernel of
+                      bbx_align.hip is launched, no such keys
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
             header (= header_new additions), header_trans)"""
     size = subimage_size or settings.subimage_size
@@ -1530,12 +1813,16 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     do_match = bool(match) and have_ref and have_psf and psf_ref is not None
     do_shapes = bool(shapes) and bool(cat_extract) and have_psf
     phot_centroid = bool(phot_centroid)
+    do_align = bool(ref_align) and have_ref
+    if do_align and ref_grid is not None:
+        raise ValueError('ref_align=True makes the lattice itself: a ref_grid beside it is refused')
+    ref_mask_remapped = ref_grid_host = None                        # set by a registration that succeeded
 
     # ---- new frame: mesh, subtraction, sigma image, variance
     mini, mini_std = get_back(ctx, new, new_mask, bkg_boxsize=box)
     work = torch.empty_like(new)
-    want_phot = cat_extract or do_match
-    want_cat = (want_phot or (build_here and have_ref)) and have_psf
+    want_phot = cat_extract or do_match or do_align
+    want_cat =(want_phot or (build_here and have_ref)) and have_psf
     second_pass = False
     if objmask:
         # the first pass's frame (no candidate list: it is not the frame the catalogue is searched on), the object mask made of
@@ -1597,10 +1884,13 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
 
     sub_pn = subimage_psfs(ctx, psf_new, nsy, nsx, size) if psf_new is not None else None
 
-    def prepare_reference():
-        """the reference frame on the new frame's grid: background-subtracted image + sigma image (before the star match
-        where that is asked for, else where the subtraction needs it)"""
-        nonlocal bstd
+    own = []
+
+    def reference_own_grid():
+        """the reference as it comes, on its own grid: background-subtracted image + sigma mini image (made once per call: the
+        registration measures its stars on it before prepare_reference brings it to the new frame)"""
+        if own:
+            return own[0]
         rny, rnx = ref.shape
         if ref_is_bkgsub:
             rwork = ref
@@ -1616,11 +1906,22 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             res['bkg_mini_ref'], sdr_meas = fetch(ctx, rmini, rstd_mini)
             sdr = sdr_meas if ref_bkg_std_mini is None else np.asarray(ref_bkg_std_mini, np.float32)
         res['bkg_std_mini_ref'] = sdr
+        own.append((rwork, sdr))
+        return own[0]
+
+    def prepare_reference():
+        """the reference frame on the new frame's grid: background-subtracted image + sigma image (before the star match
+        where that is asked for, else where the subtraction needs it)"""
+        nonlocal bstd
+        rny, rnx = ref.shape
+        rwork, sdr = reference_own_grid()
         if ref_grid is not None:
             from . import coadd
             ones = torch.ones_like(rwork)
             rwork, _ = coadd.resample(ctx, rwork, ones, ref_grid, (ny, nx), 1.0, ref_grid_step)
-            sdr = remap_mini(sdr, np.asarray(ref_grid), (rny, rnx), box, ref_grid_step, shape_out=(ny, nx))
+            # (a registration's lattice lives on the device: the mini image is remapped with its host twin)
+            sdr = remap_mini(sdr, ref_grid_host if ref_grid_host is not None else np.asarray(ref_grid), (rny, rnx), box, ref_grid_step,
+                             shape_out=(ny, nx))
         elif (rny, rnx) != (ny, nx):
             raise ValueError('reference frame of another shape needs ref_grid')
         # co-added reference: no channel structure in its noise -> interpolation across the frame
@@ -1644,6 +1945,56 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         hdr_t['S-BKGSTDR'] = (float(np.median(sdr)), '[e-] sigma (STD) background reference image')
         return rwork, rbstd, sdr, sub_pr, frame_path
 
+    def register_reference(new_list):
+        """ref_align: the reference's star list on its own grid (the caller's RefStars of this very reference, else made
+        here), the registration against the new frame's list (ys, xs, off, flux, err on the device; None: the frame has none)
+        and, where it succeeds, the lattice in place of ref_grid and the remapped mask in place of ref_mask.  Where it fails the
+        frame goes on as one without a reference"""
+        nonlocal ref_grid, ref_grid_host, ref_mask_remapped, have_ref, do_match
+        import logging
+        al, why = None, None
+        try:
+            if new_list is None:
+                raise ValueError('the new frame has no source list (no PSF, or nothing above the threshold)')
+            if psf_ref is None:
+                raise ValueError('no PSF of the reference')
+            rs = ref_stars if ref_stars is not None and ref_stars.matches(ref) else None
+            if rs is None:
+                rwork_own, sdr_own = reference_own_grid()
+                rny, rnx = ref.shape
+                if isinstance(psf_ref, dict) or psf_ref.dim() == 2:
+                    r_nsy, r_nsx = max(1, rny // size), max(1, rnx // size)
+                else:                                                # stamps of the new frame's tiling: the clamped tile's plane
+                    r_nsy, r_nsx = nsy, nsx
+                stamps = subimage_psfs(ctx, psf_ref, r_nsy, r_nsx, size).contiguous()
+                sig_med = float(np.median(sdr_own))
+                try:
+                    sig = mini2back(ctx, sdr_own, (rny, rnx), bkg_boxsize=box, interp_Xchan=True)
+                except (ValueError, _lib_BBXError):                  # a reference that is no multiple of the box: one level
+                    sig = torch.full((rny, rnx), sig_med, dtype=torch.float32, device=ctx.device)
+                rs = RefStars(ctx, rwork_own, sig, ref_mask, stamps, r_nsy, r_nsx, size, cat_nsigma, sigma_median=sig_med,
+                              max_sources=max_sources, made_of=ref)
+            res['ref_stars'] = rs
+            al = align_reference(ctx, new_list, rs, (ny, nx), tuple(ref.shape), ref_mask, poldeg=align_poldeg, max_shift=align_max_shift,
+                                 bin=align_bin, dist=match_dist, snr_min=match_snr_min, step=ref_grid_step, rounds=align_rounds,
+                                 nbright=align_nbright)
+            if al['flags'] != 0:
+                why = 'flag word %d (vote %s)' % (al['flags'], np.asarray(al['fit']['info']).tolist())
+        except Exception as e:                                       # the frame goes on without its reference
+            al, why = None, str(e)
+        res['align'] = al
+        if why is None:
+            ref_grid, ref_grid_host, ref_mask_remapped = al['grid'], align_grid_host(al['coef'], (ny, nx), ref_grid_step), al['mask']
+            res['ref_mask_remapped'] = al['mask']
+            hdr_t.update(al['header'])
+            return True
+        logging.getLogger(__name__).warning('registration of the reference failed (%s): processing the new image only', why)
+        hdr_t.update(al['header'] if al is not None else align_header(None))
+        hdr_t['T-NOFFR'] = ('None', 'candidates dropped: no reference there')
+        hdr.update({k: v for k, v in hdr_t.items() if k.startswith('A-')})         # (no _trans products will carry them: the frame's own header does)
+        have_ref = do_match = False
+        return False
+
     ref_side = None
     # ---- full-source catalogue (a17): peaks of the background-subtracted frame above
     # cat_nsigma x S-BKGSTD, PSF-weighted optimal flux at each (zogy.get_psfoptflux)
@@ -1653,13 +2004,13 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         thr = float(cat_nsigma) * hdr['S-BKGSTD'][0]
         if np.isfinite(thr) and thr > 0:
             pending = find_peaks_enqueue(ctx, work, thr, max_out=max_sources)
-            if do_match and not build_here:
+            if do_match and not build_here and not do_align:         # (a reference to be registered is prepared behind the photometry)
                 ref_side = prepare_reference()                       # (behind the search: its zoom would drop the candidate list)
             scal_n = host_side_meanwhile()
             ys, xs, pk = find_peaks_collect(ctx, pending)
         else:                                                        # no usable noise level: nothing is significant
             lib.bbx_zoom_candidates(ctx.h, None, 0.0)
-            if do_match and not build_here:
+            if do_match and not build_here and not do_align:
                 ref_side = prepare_reference()
             scal_n = host_side_meanwhile()
             ys = xs = np.zeros(0, np.int32); pk = np.zeros(0, np.float32)
@@ -1673,7 +2024,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             psf_new = res['psf']['model']
             if psf_new is not None:
                 sub_pn = subimage_psfs(ctx, psf_new, nsy, nsx, size)
-                if do_match:
+                if do_match and not do_align:
                     ref_side = prepare_reference()
             else:                                                    # no model: the frame of today without --psf_new
                 want_phot = do_match = do_shapes = have_ref = False
@@ -1684,8 +2035,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             d_ys, d_xs = push(ctx, ys.astype(np.int64), xs.astype(np.int64))
             d_mk = new_mask[d_ys, d_xs]
             peaks_off = None
-            if phot_centroid or do_shapes:
-                # the windowed centroids once: for the photometry (phot_centroid), the shapes and the star match
+            if phot_centroid or do_shapes or do_align:
+                # the windowed centroids once: for the photometry (phot_centroid), the shapes, the registration and the star match
                 d_y32, d_x32 = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
                 sigw = window_sigma(sub_pn)
             if phot_centroid:
@@ -1694,6 +2045,15 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             else:
                 stamps = source_psfs(ctx, psf_new, sub_pn, ys, xs, nsx, size)
                 f, e = psf_optflux(ctx, work, bstd, stamps, ys, xs, v_is_sigma=True)        # (bstd: frame or MiniImage)
+            if do_align:
+                # the registration: the new frame's list as the star match sees it (a peak on a masked pixel: no offset, no flux),
+                # then the reference on this frame's grid -- before anything below asks for it
+                if peaks_off is None:
+                    peaks_off = (d_y32, d_x32, win_centroid(ctx, work, d_y32, d_x32, sigw, size, nsy, nsx))
+                bad = d_mk != 0
+                a_off = torch.where(bad[:, None], torch.full_like(peaks_off[2], float('nan')), peaks_off[2]).contiguous()
+                if register_reference((d_y32, d_x32, a_off, torch.where(bad, torch.zeros_like(f), f).contiguous(), e)):
+                    ref_side = prepare_reference()
             back = [d_mk, f, e]
             if do_shapes:
                 # the moments and their statistics are queued behind the photometry and come back with it
@@ -1705,7 +2065,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                 # the star match rides on the same copy back: centroids, match against the reference's catalogue (the run's,
                 # or made here) and the table of clipped statistics are queued behind the photometry
                 rc = ref_catalog if ref_catalog is not None and ref_catalog.matches(ref_side[0], ref_side[1], size, border, phot_centroid) else \
-                    RefCatalog(ctx, ref_side[0], ref_side[1], ref_mask if ref_grid is None else None, psf_ref, size, border,
+                    RefCatalog(ctx, ref_side[0], ref_side[1], ref_mask if ref_grid is None else ref_mask_remapped, psf_ref, size, border,
                                cat_nsigma=cat_nsigma, sigma_median=hdr_t['S-BKGSTDR'][0], sub_psfs=ref_side[3], max_sources=max_sources,
                                phot_centroid=phot_centroid)
                 back += match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, match_dist, match_snr_min,
@@ -1727,6 +2087,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             if do_shapes:
                 shp, sfl, stab = got[-3][ok], got[-2][ok], got[-1]
         else:
+            if do_align:
+                register_reference(None)
             f = e = np.zeros(0, np.float32)
             shp, sfl, stab = np.zeros((0, 8), np.float32), np.zeros(0, np.uint8), empty_shape_table(nsub)
             poff, pfl = np.zeros((0, 2), np.float32), np.zeros(0, np.uint8)
@@ -1750,6 +2112,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             hdr.update(shape_header(stab, len(ys), settings.shape_nmin, settings.pixscale))
     if 'S-BKG' not in hdr:
         scal_n = host_side_meanwhile()
+    if do_align and have_ref and 'align' not in res:
+        register_reference(None)                                     # (no photometry ran: no PSF of the new frame)
     if not have_ref:
         hdr['Z-P'] = (False, 'successfully processed by ZOGY?')
         res['header'], res['header_new'], res['header_trans'], res['transients'] = _HeaderView(hdr, hdr_t), hdr, hdr_t, []
@@ -1839,6 +2203,11 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     if tys.size:
         d_ys, d_xs = push(ctx, tys.astype(np.int64), txs.astype(np.int64))
         d_fe = torch.stack([res['Fpsf'][d_ys, d_xs], res['Fpsferr'][d_ys, d_xs]])
+    d_edge = None
+    if tys.size and ref_mask_remapped is not None:
+        # the registered reference's mask under every candidate: where it carries the edge bit the frame has no reference, D
+        # is the new frame there and every star a candidate
+        d_edge = (ref_mask_remapped[d_ys, d_xs] & settings.mask_value['edge']).to(torch.float32)
     d_tf = None
     fit_size = int(settings.trans_fit_size if trans_fit_size is None else trans_fit_size)
     if trans_psffit:
@@ -1870,20 +2239,21 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         # the cut-outs of the four frames, which are all still in HBM, and the mask flags under each peak in one pass; the
         # display planes from the cut-outs.  The reference's mask counts only where it shares the new frame's grid
         d_fl = thumbnail_stamps(ctx, res, (res['data_bkgsub'], res['ref_bkgsub'], res['D'], res['Scorr']), tys, txs, tsize, new_mask,
-                                ref_mask if ref_grid is None else None, floats=thumbnails, pngs=thumbnail_pngs)
+                                ref_mask if ref_grid is None else ref_mask_remapped, floats=thumbnails, pngs=thumbnail_pngs)
     if frame_stats:
         # statistics over the unmasked pixels (new frame's mask), clipped like zogy's header values
         d_st = torch.stack([frame_clipped_stats_enqueue(ctx, res['Scorr'], new_mask),
                             frame_clipped_stats_enqueue(ctx, res['Fpsferr'], new_mask)])
     if d_fl is not None and not d_fl.numel():
         d_fl = None
-    back = [t for t in (d_fe, d_st, d_fl, d_tf, d_ts) if t is not None]
+    back = [t for t in (d_fe, d_st, d_fl, d_tf, d_ts, d_edge) if t is not None]
     got = (fetch(ctx, *back) if len(back) > 1 else [fetch(ctx, back[0])]) if back else []
     fe = got.pop(0) if d_fe is not None else None
     st = got.pop(0) if d_st is not None else None
     fl = got.pop(0) if d_fl is not None else None
     tf = got.pop(0) if d_tf is not None else None
     ts = got.pop(0) if d_ts is not None else None
+    edge_at = got.pop(0) if d_edge is not None else None
     if tys.size:
         res['transients'] = [dict(y=y, x=x, scorr=sc, fpsf=f, fpsferr=e)
                              for y, x, sc, f, e in zip(tys.tolist(), txs.tolist(), tsc.tolist(), fe[0].tolist(), fe[1].tolist())]
@@ -1910,6 +2280,15 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                               'fwhm_%s_d' % name: float(planes[m, 4, i]), 'elong_%s_d' % name: float(planes[m, 5, i]),
                               'chi2_%s_d' % name: float(planes[m, 6, i]), 'flags_%s_d' % name: int(sfl[m, i])})
             hdr_t.update(trans_shape_header(True, shape_size, settings.trans_moffat_beta, res['transients']))
+        if edge_at is not None:
+            # candidates without a reference under their peak leave, with their thumbnails; T-NTRANS stays the count before
+            keep = [i for i, v in enumerate(edge_at.tolist()) if not v]
+            if len(keep) < len(res['transients']):
+                res['transients'] = [res['transients'][i] for i in keep]
+                for k in ('thumbnails', 'thumbnail_png8'):
+                    if k in res:
+                        res[k] = res[k][torch.as_tensor(keep, dtype=torch.int64, device=res[k].device)]
+            hdr_t['T-NOFFR'] = (int(tys.size) - len(keep), 'candidates dropped: no reference there')
         # the vetting: the chi2 bound needs the fit of P_D, the Gauss bounds the shape fits
         bounds = dict(chi2_max=trans_chi2_max if tf is not None else None)
         if ts is not None:
@@ -1922,6 +2301,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             hdr_t['T-NVET'] = (len(keep), 'number of transient candidates that passed the vetting')
     else:
         res['transients'] = []
+    if ref_mask_remapped is not None and 'T-NOFFR' not in hdr_t:
+        hdr_t['T-NOFFR'] = (0, 'candidates dropped: no reference there')
     hdr['Z-P'] = (True, 'successfully processed by ZOGY?')
     for h in (hdr, hdr_t):
         h['Z-SIZE'] = (size, '[pix] size of (square) ZOGY subimages')

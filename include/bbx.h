@@ -988,6 +988,68 @@ int bbx_trans_shapefit(bbx_ctx *ctx, int ny, int nx, const float *d_D, const flo
                        float maxshift, int models, float beta, float fwhm_lo, float fwhm_hi, float *d_out, uint8_t *d_flags,
                        void *stream);
 
+/* ---- registration of the reference on the new frame from the two star lists (bbx_align.hip).  zogy registers
+ * with SWarp and two astrometric solutions ([EXT]); the method here and every rule below are THIS PROJECT'S OWN, stated in float64
+ * numpy by tests/test_align_host.py (vote_ref, fit_ref, apply_ref, grid_of, remap_mask_ref).  A list is integer peaks + float32
+ * offsets [n][2] = (dy, dx) + fluxes [+ errors]; A is the new frame's, B the reference's ON ITS OWN GRID.  T maps new-frame to
+ * reference pixels: per axis a polynomial in u = (x - nx / 2) / (nx / 2), v likewise, terms 1, u, v, u^2, uv, v^2;
+ * coef[12] = the six of x, then the six of y (degree 1: the last three of each are 0).  All entries are deterministic: integer
+ * atomics only, every float64 sum in a fixed order.  Every array crosses with its extent.                                  */
+#define BBX_ALIGN_NBRIGHT_MAX 2048   /* bbx_align_vote: sources of a list that vote (one 16 KB LDS sort) */
+#define BBX_ALIGN_CAP_MAX     8192   /* bbx_align_vote: pairs of the winning block that are written (one 32 KB LDS sort) */
+
+/* The vote for the coarse offset.  Of each list the nbright (<= BBX_ALIGN_NBRIGHT_MAX) brightest eligible sources (flux > 0 and
+ * finite, both offsets finite; ties to the lower index), in that order: their ranks.  Every pair's d = p_A - p_B, float32 as
+ * bbx_match_mutual forms it ((float)(integer difference) + (offset difference)), with |dy|, |dx| <= (float)max_shift counts into
+ * bin floor((d + max_shift) / bin) (float32) of an nb x nb histogram, nb = floor(2 max_shift / bin) + 1 (< 1024).  3 x 3 block
+ * sums; winner: the largest, the lowest (y, x) cell on ties; runner-up: the largest outside the winner's 5 x 5; far: the largest
+ * outside +- far cells.  The winning block's pairs in row-major order of (rank in A, rank in B), the first cap (<=
+ * BBX_ALIGN_CAP_MAX) of them: d_pairs[cap][2] = (index into A, index into B), (-1, -1) past those written; d_coarse[2] = medians of
+ * their dy, dx (even count: the midpoint of the two float32 values in float64; none: NaN).  d_info[8] = {winner's sum, runner-up's
+ * sum, winner's cell y, x, pairs written, failed, pairs found, far sum}; failed = 1 when the winner has fewer than nmin votes, is
+ * not above the runner-up, or is not above the far sum f by more than 3 sqrt(f).  d_work: scratch of work_bytes >=
+ * bbx_align_vote_bytes(nbright, max_shift, bin, cap) bytes (0: arguments out of range), 256-byte aligned.                       */
+size_t bbx_align_vote_bytes(int nbright, double max_shift, double bin, int cap);
+int bbx_align_vote(bbx_ctx *ctx, int n_a, const int32_t *d_a_ys, const int32_t *d_a_xs, const float *d_a_off,
+                   const float *d_a_flux, int n_b, const int32_t *d_b_ys, const int32_t *d_b_xs, const float *d_b_off,
+                   const float *d_b_flux, int nbright, double max_shift, double bin, int nmin, int far, int cap,
+                   void *d_work, size_t work_bytes, int32_t *d_info, double *d_coarse, int32_t *d_pairs, void *stream);
+
+/* The clipped least-squares fit of T (poldeg 1 or 2) to the pairs d_items[n_items][2] = (index into A, index into B); an index
+ * that is negative or not below its list's length: no pair.  A pair qualifies with both fluxes > 0, flux / err >= snr_min
+ * (float32) on both sides and finite offsets.  Normal equations in float64 on the basis above at the new frame's position
+ * (integer + (double)offset), Cholesky (a pivot not above 1e-12 of its diagonal element: not positive definite); first all
+ * qualifying pairs, then three passes that drop the pairs with r^2 > clip^2 (sx + sy) / n of those kept so far and fit again.
+ * d_coef[12] (NaN before the first solve), d_stats[4] = {n_used, rms_x, rms_y, flags}, d_kept[n_items] u8: the pairs of the last
+ * solve attempted.  flags: 2 fewer than max(nmin, number of terms) pairs at a solve (or an empty list), 4 not positive definite,
+ * 8 determinant of the linear part in pixels outside [0.5, 2].  One workgroup; sums: per thread over items t, t + 512, ..., the
+ * wave by DPP, the waves in order.                                                                                        */
+int bbx_align_fit(bbx_ctx *ctx, int n_a, const int32_t *d_a_ys, const int32_t *d_a_xs, const float *d_a_off,
+                  const float *d_a_flux, const float *d_a_err, int n_b, const int32_t *d_b_ys, const int32_t *d_b_xs,
+                  const float *d_b_off, const float *d_b_flux, const float *d_b_err, int n_items, const int32_t *d_items,
+                  int ny, int nx, int poldeg, float snr_min, double clip, int nmin, double *d_coef, double *d_stats,
+                  uint8_t *d_kept, void *stream);
+
+/* A list of the reference through the inverse of T (d_coef[12] on the device; ny, nx: the NEW frame's shape): the closed-form
+ * inverse of the linear part, two Newton steps for poldeg 2, float64 operation by operation as apply_ref.  Where |x|, |y| < 1e9:
+ * integer = floor(. + 0.5), offset = (float)(. - integer); else the integers of the input and a (NaN, NaN) offset.  Not sorted. */
+int bbx_align_apply(bbx_ctx *ctx, int n, const int32_t *d_ys, const int32_t *d_xs, const float *d_off, const double *d_coef,
+                    int ny, int nx, int poldeg, int32_t *d_oys, int32_t *d_oxs, float *d_ooff, void *stream);
+
+/* The lattice of bbx_resample_lanczos3 from T: d_grid[gny][gnx][2] = (x, y) of T at the new frame's pixels (j step, i step).
+ * The lattice must hold the node after the last pixel in both directions: BBX_ERR_ARG otherwise.                            */
+int bbx_align_grid(bbx_ctx *ctx, const double *d_coef, int ny, int nx, int step, int gny, int gnx, double *d_grid,
+                   void *stream);
+
+/* The mask d_mask[in_ny][in_nx] (NULL: none) on the output grid: per output pixel the input position by the resampler's own
+ * lattice interpolation (float64, its operations), the OR of the mask over the up-to-four pixels a bilinear interpolation would
+ * touch (the pixel at + 1 only where the position has a fractional part on that axis: the identity lattice gives the mask back),
+ * and edge_bit where the 6 x 6 LANCZOS3 footprint leaves the input (where bbx_resample_lanczos3 writes weight 0) or the position
+ * is not finite (nothing is read then).  d_out[out_ny][out_nx] u8, 4-byte aligned; d_nedge[1]: pixels that got the edge bit.
+ * The lattice must hold the node after the last output pixel in both directions: BBX_ERR_ARG otherwise.                     */
+int bbx_remap_mask(bbx_ctx *ctx, int in_ny, int in_nx, const uint8_t *d_mask, int out_ny, int out_nx, const double *d_grid,
+                   int gny, int gnx, int step, int edge_bit, uint8_t *d_out, int64_t *d_nedge, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
