@@ -107,6 +107,7 @@ SIGNATURES = {
     'bbx_median_stack': (_i, [_vp, C.c_int64, _i, C.POINTER(_vp), _pf, _vp, _i, _vp, _vp]),
     'bbx_canny_edge_map': (_i, [_vp, _i, _i, _vp, _pd, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp]),
     'bbx_sat_trails': (_i, [_vp, _i, _i, _vp, _vp, _pd, _i, _pd, _i, _vp, _vp, _vp]),
+    'bbx_sat_trails_state': (_i, [_vp, _i, _i, _i, _pd, C.POINTER(C.c_int32), _i, _vp]),
     'bbx_bkg_boxstats': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     'bbx_mini_fill_filter': (_i, [_vp, _i, _i, _vp, _vp]),
     'bbx_spline_prefilter': (_i, [_vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),

@@ -45,7 +45,6 @@ struct sat_state {
 #define SAT_SUBW 200
 struct sat_rect { int r0, r1, c0, c1; };
 
-
 // 2 x 2 sums (blackbox.py:4171-4172)
 __global__ __launch_bounds__(256) void k_bin2(const float* __restrict__ d, int nyb, int nxb, float* __restrict__ b) {
     const int X = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y;
@@ -79,14 +78,13 @@ __global__ __launch_bounds__(256) void k_bin_minmax(const float* __restrict__ b,
     }
 }
 
+// every field: what a frame does not reach (the segment, the start of the walk, the rotations of a rejected line) reads as
+// zero afterwards, not as the frame before
 __global__ void k_sat_init(sat_state* st) {
     if (threadIdx.x == 0) {
-        st->best = 0;
-        st->accept = 0; st->found = 0; st->k = 0; st->lo_off = 0; st->hi_off = 0; st->votes = 0;
-        st->rho = 0; st->c = 0; st->s = 0; st->chord = 0; st->tmin = ~0ull; st->tmax = 0ull; st->t0 = 0; st->t1 = 0;
-        st->fit_n = 0; st->fit_t = st->fit_d = st->fit_tt = st->fit_td = 0; st->icpt = 0; st->slope = 0;
-        st->bmax_key = 0u; st->bmin_key = ~0u; st->seg_ok = 0; st->nwin = 0; st->row_min = 0x7fffffff; st->row_max = -1;
-        st->band_r0 = 0; st->band_rows = 0; st->rot_rows = st->rot_cols = 0;
+        *st = sat_state{};
+        st->tmin = ~0ull; st->tmax = 0ull;
+        st->bmax_key = 0u; st->bmin_key = ~0u; st->row_min = 0x7fffffff; st->row_max = -1;
     }
 }
 
@@ -140,7 +138,7 @@ __device__ __forceinline__ double dkey_inv(unsigned long long k) {
 __global__ void k_trail_decide(sat_state* st, const double* __restrict__ cs, int nrho, int nyb, int nxb, int min_votes) {
     if (threadIdx.x != 0) return;
     const unsigned long long b = st->best;
-    if (!b) return;
+    if (!b) { st->rho = (double)(-(nrho / 2)); return; }          // no edge pixel: the first cell of an all-zero accumulator (k = 0)
     const unsigned votes = (unsigned)(b >> 32);
     const unsigned long long flat = 0xffffffffull - (b & 0xffffffffull);
     const int k = (int)(flat / nrho), r = (int)(flat % nrho);
@@ -557,30 +555,42 @@ extern "C" int bbx_count_objects(bbx_ctx* ctx, int ny, int nx, const uint8_t* d_
 int bbx_canny_edges(bbx_ctx* ctx, const float* d_bin, int ny, int nx, const double* h_gauss, int radius, double low_frac, double high_frac,
                     int min_size, uint32_t* d_out, int32_t* d_out_cnt, uint32_t out_cap, hipStream_t s);
 
+// where the pieces of a frame's detection sit in the WS_CAND workspace: binned frame | edge list | cos/sin | partials | state |
+// the strips of the walk | the band of the rotated frame (its width is at most the frame's diagonal + 2)
+struct sat_layout {
+    int nyb, nxb, nrho, band_cols;
+    size_t nb, cap, o_bin, o_list, o_cs, o_part, o_st, o_rect, o_band, total;
+};
+static sat_layout sat_layout_of(int ny, int nx, int ntheta) {
+    sat_layout L;
+    L.nyb = ny / 2; L.nxb = nx / 2;
+    L.nb = (size_t)L.nyb * L.nxb;
+    // skimage.transform.hough_line: offset = ceil(hypot(ny, nx)), 2 offset cells of one pixel
+    L.nrho = 2 * (int)ceil(sqrt((double)L.nyb * L.nyb + (double)L.nxb * L.nxb));
+    L.cap = L.nb / 8 + 4096;
+    L.o_bin = 0; L.o_list = L.o_bin + ((L.nb * 4 + 255) & ~(size_t)255);
+    L.o_cs = L.o_list + ((L.cap * 4 + 255) & ~(size_t)255); L.o_part = L.o_cs + (((size_t)ntheta * 16 + 255) & ~(size_t)255);
+    L.o_st = L.o_part + SAT_BLOCKS * 3 * 8;
+    L.band_cols = L.nrho / 2 + 8;
+    L.o_rect = (L.o_st + sizeof(sat_state) + 255) & ~(size_t)255; L.o_band = (L.o_rect + SAT_MAXWIN * sizeof(sat_rect) + 255) & ~(size_t)255;
+    L.total = L.o_band + (size_t)2 * SAT_BANDH * L.band_cols * sizeof(double) + 256;
+    return L;
+}
+
 extern "C" int bbx_sat_trails(bbx_ctx* ctx, int ny, int nx, const float* d_data, uint8_t* d_mask, const double* h_cos_sin,
                               int ntheta, const double* h_gauss, int gauss_radius, int32_t* d_nsats, float* d_info, void* stream) {
     if (!ctx || !d_data || !d_mask || !h_cos_sin || !h_gauss || !d_nsats || !d_info || ny < 8 || nx < 8 || (ny & 1) || (nx & 1) ||
         ntheta < 4 || ntheta > 4096 || ((uintptr_t)d_data) % 8)
         return BBX_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const int nyb = ny / 2, nxb = nx / 2;
-    const size_t nb = (size_t)nyb * nxb;
-    // skimage.transform.hough_line: offset = ceil(hypot(ny, nx)), 2 offset cells of one pixel
-    const int nrho = 2 * (int)ceil(sqrt((double)nyb * nyb + (double)nxb * nxb));
+    const sat_layout L = sat_layout_of(ny, nx, ntheta);
+    const int nyb = L.nyb, nxb = L.nxb, nrho = L.nrho, band_cols = L.band_cols;
+    const size_t nb = L.nb, cap = L.cap;
     int rc;
-    const size_t cap = nb / 8 + 4096;
-    // workspace: binned frame | edge list | cos/sin | partials | state
-    const size_t o_bin = 0, o_list = o_bin + ((nb * 4 + 255) & ~(size_t)255);
-    const size_t o_cs = o_list + ((cap * 4 + 255) & ~(size_t)255), o_part = o_cs + (((size_t)ntheta * 16 + 255) & ~(size_t)255);
-    const size_t o_st = o_part + SAT_BLOCKS * 3 * 8;
-    // make_mask: the strips of the walk and the band of the rotated frame (its width is at most the frame's diagonal + 2)
-    const int band_cols = nrho / 2 + 8;
-    const size_t o_rect = (o_st + sizeof(sat_state) + 255) & ~(size_t)255, o_band = (o_rect + SAT_MAXWIN * sizeof(sat_rect) + 255) & ~(size_t)255;
-    const size_t total = o_band + (size_t)2 * SAT_BANDH * band_cols * sizeof(double) + 256;
-    char* ws = (char*)bbx_ws(ctx, WS_CAND, total, &rc); if (rc) return rc;
-    float* bin = (float*)(ws + o_bin); uint32_t* list = (uint32_t*)(ws + o_list);
-    double* cs = (double*)(ws + o_cs); sat_state* st = (sat_state*)(ws + o_st);
-    sat_rect* rects = (sat_rect*)(ws + o_rect); double* band = (double*)(ws + o_band);
+    char* ws = (char*)bbx_ws(ctx, WS_CAND, L.total, &rc); if (rc) return rc;
+    float* bin = (float*)(ws + L.o_bin); uint32_t* list = (uint32_t*)(ws + L.o_list);
+    double* cs = (double*)(ws + L.o_cs); sat_state* st = (sat_state*)(ws + L.o_st);
+    sat_rect* rects = (sat_rect*)(ws + L.o_rect); double* band = (double*)(ws + L.o_band);
     int32_t* cnt = &ctx->d_counters[CNT_CAND];
     BBX_HIP(hipMemcpyAsync(cs, h_cos_sin, (size_t)ntheta * 16, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_sat_init, dim3(1), dim3(128), 0, s, st);
@@ -618,6 +628,42 @@ extern "C" int bbx_sat_trails(bbx_ctx* ctx, int ny, int nx, const float* d_data,
     hipLaunchKernelGGL(k_sat_info, dim3(1), dim3(64), 0, s, st, d_info);
     BBX_LAUNCH_CHECK();
     return bbx_count_objects(ctx, ny, nx, d_mask, BBX_MASK_SATELLITE, d_nsats, stream);
+}
+
+static double dkey_inv_host(unsigned long long k) {                          // dkey_inv on the host
+    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double v; memcpy(&v, &u, sizeof(v));
+    return v;
+}
+
+// The decisions of the last bbx_sat_trails call on this context (tests): they still sit in the WS_CAND workspace.  Waits for
+// the stream, copies, launches nothing.
+extern "C" int bbx_sat_trails_state(bbx_ctx* ctx, int ny, int nx, int ntheta, double* h_state, int32_t* h_rects, int max_rects, void* stream) {
+    if (!ctx || !h_state || max_rects < 0 || (max_rects > 0 && !h_rects) || ny < 8 || nx < 8 || (ny & 1) || (nx & 1) || ntheta < 4 || ntheta > 4096)
+        return BBX_ERR_ARG;
+    const sat_layout L = sat_layout_of(ny, nx, ntheta);
+    if (!ctx->d_ws[WS_CAND] || ctx->ws_bytes[WS_CAND] < L.total) return BBX_ERR_ARG;         // no such call came before
+    hipStream_t s = (hipStream_t)stream;
+    const char* ws = (const char*)ctx->d_ws[WS_CAND];
+    sat_state st;
+    BBX_HIP(hipMemcpyAsync(&st, ws + L.o_st, sizeof(sat_state), hipMemcpyDeviceToHost, s));
+    BBX_HIP(hipStreamSynchronize(s));
+    const double nan = __builtin_nan("");
+    const bool sup = st.tmax != 0ull;                                                         // a supporting edge pixel was seen
+    const double v[BBX_SAT_NSTATE] = {(double)st.accept, (double)st.seg_ok, (double)st.found, (double)st.k, (double)st.votes, st.rho, st.t0, st.t1,
+                                      sup ? dkey_inv_host(st.tmin) : nan, sup ? dkey_inv_host(st.tmax) : nan, st.icpt, st.slope,
+                                      (double)st.seg[0], (double)st.seg[1], (double)st.seg[2], (double)st.seg[3],
+                                      (double)st.rot_rows, (double)st.rot_cols, st.sx, st.sy, (double)st.band_r0, (double)st.band_rows,
+                                      (double)st.nwin, (double)st.row_min, (double)st.row_max};
+    for (int i = 0; i < BBX_SAT_NSTATE; i++) h_state[i] = v[i];
+    int n = st.nwin < 0 ? 0 : (st.nwin > SAT_MAXWIN ? SAT_MAXWIN : st.nwin);
+    if (n > max_rects) n = max_rects;
+    if (n > 0) {
+        static_assert(sizeof(sat_rect) == 4 * sizeof(int32_t), "h_rects holds r0, r1, c0, c1 per strip");
+        BBX_HIP(hipMemcpyAsync(h_rects, ws + L.o_rect, (size_t)n * sizeof(sat_rect), hipMemcpyDeviceToHost, s));
+        BBX_HIP(hipStreamSynchronize(s));
+    }
+    return BBX_OK;
 }
 
 // bbx_build_flags (bbx_ctx.hip): the satellite stage's timing knock-outs (this file, bbx_canny.hip) compiled in?

@@ -474,10 +474,29 @@ int bbx_median_stack(bbx_ctx *ctx, int64_t npix, int nframes, const float *const
  *  h_gauss [gauss_radius + 1] : scipy.ndimage's Gaussian weights for sigma = 3, centre first
  *                               (radius int(4 sigma + 0.5) = 12), float64, from the host like the angles.
  *  d_nsats [1] i32 : 8-connected objects of bit 16 (NSATS).
- *  d_info [8] f32  : level, sigma, votes, theta index, rho, strip lo, strip hi, found.     */
+ *  d_info [8] f32  : largest binned pixel, smallest binned pixel, votes of the best cell, its theta index,
+ *                    its rho, strips painted, 1 = a segment went to make_mask, 1 = a trail was masked.  */
 int bbx_sat_trails(bbx_ctx *ctx, int ny, int nx, const float *d_data, uint8_t *d_mask,
                    const double *h_cos_sin, int ntheta, const double *h_gauss, int gauss_radius,
                    int32_t *d_nsats, float *d_info, void *stream);
+
+/* bbx_sat_trails_state: the decisions of the last bbx_sat_trails call on this context, for tests.  ny, nx and
+ * ntheta are those of that call; nothing else may have run on the context in between (the values sit in a
+ * shared workspace).  Waits for the stream and copies; launches nothing.
+ *  h_state [BBX_SAT_NSTATE] f64 (host), integers as exact doubles:
+ *    0 accept (the line passed the vote, refinement, support and segment tests), 1 seg_ok (a segment went to
+ *    make_mask), 2 found (a trail was masked), 3 k (theta index), 4 votes, 5 rho,
+ *    6 t0, 7 t1 (where the cell's line enters / leaves the binned frame, position along the line),
+ *    8 tmin, 9 tmax (extent of the supporting edge pixels along the line; NaN: none seen),
+ *    10 icpt, 11 slope (refined line), 12..15 segment x0, y0, x1, y1 (binned pixels),
+ *    16 rot_rows, 17 rot_cols (rotated frame), 18 sx, 19 sy (the segment's first point there),
+ *    20 band_r0, 21 band_rows (rows of the rotated frame that were interpolated),
+ *    22 nwin (strips painted), 23 row_min, 24 row_max (their row range).
+ *  h_rects [4 * max_rects] i32 (host): the first min(nwin, max_rects) strips as r0, r1, c0, c1 (rotated
+ *    frame, half-open), in the order of the walk.                                                        */
+#define BBX_SAT_NSTATE 25
+int bbx_sat_trails_state(bbx_ctx *ctx, int ny, int nx, int ntheta, double *h_state, int32_t *h_rects,
+                         int max_rects, void *stream);
 
 /* bbx_canny_edge_map: the front end of bbx_sat_trails on its own (parity tests against scikit-image):
  * np.percentile(img, (4.5, 93)) + skimage.exposure.rescale_intensity + skimage.feature.canny(sigma from

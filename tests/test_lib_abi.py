@@ -44,6 +44,8 @@ def test_bad_arguments_are_rejected_without_gpu():
     assert L.bbx_stream_wait_event(None, None) == -1
     assert L.bbx_copy_async(None, None, 16, 0, None) == -1
     assert L.bbx_funpack_tiles(None, 10, 10, 2, None, None, 1, None, None, None, 0, None, None) == -1
+    state = (ctypes.c_double * 25)()
+    assert L.bbx_sat_trails_state(None, 600, 900, 352, state, None, 0, None) == -1
 
 
 def test_product_never_imports_oracle():
