@@ -282,6 +282,18 @@ def f32x16(values):
     return arr
 
 
+def ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def expect(t, dtype, shape, name):
+    """device pointers cross the C ABI without their extents: a wrong shape or dtype would be
+    a device fault, so it is refused here"""
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError('{}: expected contiguous {} device tensor of shape {}, got {} {}'.format(
+            name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+
+
 def check(code, what, ctx=None):
     if code != 0:
         detail = ''

@@ -26,13 +26,10 @@ import os
 
 from . import _lib, overscan, settings
 from ._lib import lib, check, Geom, BBX_RAW_U16, BBX_RAW_F32
+from ._lib import ptr as _ptr, expect as _expect
 
 get_par = settings.get_par
 _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None) or (lambda idx: torch.cuda.current_stream(idx).cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 class Context:
@@ -73,14 +70,6 @@ class Context:
             self.close()
         except Exception:
             pass
-
-
-def _expect(t, dtype, shape, name):
-    """device pointers cross the C ABI without their extents: a wrong shape or dtype would be
-    a device fault, so it is refused here"""
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not t.is_cuda:
-        raise ValueError('{}: expected contiguous {} device tensor of shape {}, got {} {}'.format(
-            name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
 
 
 def raw_type_of(raw):
