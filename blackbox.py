@@ -105,6 +105,17 @@ def align_keywords(a, S, tel=None):
     return kw
 
 
+def float_list(v):
+    """'0.66,1.5,5' -> (0.66, 1.5, 5.0)"""
+    try:
+        out = tuple(float(t) for t in str(v).split(',') if t.strip())
+    except ValueError:
+        raise argparse.ArgumentTypeError('a comma list of numbers expected, got %r' % (v,))
+    if not out:
+        raise argparse.ArgumentTypeError('a comma list of numbers expected, got %r' % (v,))
+    return out
+
+
 def str2bool(v):
     """blackbox.py:8115-8123"""
     if isinstance(v, bool):
@@ -403,6 +414,13 @@ class Reducer:
         if sub['cat_extract'] and par(a.cat_shapes, 'cat_shapes'):
             # source shapes of the catalogue and the frame's seeing / elongation keys; the keyword is only passed when switched on
             sub['shapes'] = True
+        if sub['cat_extract'] and par(a.cat_apphot, 'cat_apphot'):
+            # aperture fluxes with a local sky annulus in the catalogue and the AP-* keys; the keywords are only passed when switched on
+            sub['aper_phot'] = True
+            if a.apphot_radii is not None:
+                sub['apphot_radii'] = a.apphot_radii
+            if a.apphot_local_sky is not None:
+                sub['apphot_local_sky'] = a.apphot_local_sky
         if par(a.objmask, 'objmask'):
             # object mask + second background pass, whenever the subtraction stage runs; the keywords are only passed when switched on
             sub['objmask'] = True
@@ -1135,6 +1153,14 @@ def build_parser():
     ap.add_argument('--cat_shapes', type=str2bool, default=None,
                     help='with --cat_extract: FWHM, ELONGATION, A, B, THETA, X2, Y2, XY, FLAGS_MASK and sub-pixel X_POS / Y_POS in '
                          '_cat.fits, S-NOBJ S-FWHM S-FWSTD S-SEEING S-SEESTD S-ELONG S-ELOSTD in the header (default: settings.cat_shapes)')
+    ap.add_argument('--cat_apphot', type=str2bool, default=None,
+                    help='with --cat_extract: aperture fluxes E_FLUX_APER_R<r>xFWHM / E_FLUXERR_APER_R<r>xFWHM, BKG_APER, BKGSTD_APER, NSKY_APER, '
+                         'FWHM_APER, FLAGS_APER in _cat.fits, AP-P AP-FWHM AP-NAPER AP-R* AP-SKYIN AP-SKYOU AP-LSKY AP-NSTAR AP-OPT* in the '
+                         'header (default: settings.cat_apphot)')
+    ap.add_argument('--apphot_radii', type=float_list, default=None,
+                    help='[FWHM] aperture radii of --cat_apphot, a comma list of at most 8 (default: settings.apphot_radii)')
+    ap.add_argument('--apphot_local_sky', type=str2bool, default=None,
+                    help='subtract the sky annulus\' clipped median from the aperture fluxes (default: settings.apphot_local_sky)')
     ap.add_argument('--trans_psffit', type=str2bool, default=None,
                     help='fit the PSF of D to D at every transient candidate: X_PSF_D Y_PSF_D E_FLUX_PSF_D E_FLUXERR_PSF_D CHI2_PSF_D '
                          'FLAGS_PSF_D in `_trans.fits`, T-PSFD T-FITSZ T-NFIT T-PDFOLD T-CHI2MD in its header (default: '

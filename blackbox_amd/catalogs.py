@@ -19,6 +19,10 @@ THETA, X2, Y2, XY and FLAGS_MASK (SHAPE_COLUMNS) after the seven columns above; 
 
 Photometry with the PSF on the centroid (settings.phot_centroid, off by default): a 'new' table that carries it is written with
 FLAGS_OPT (PHOT_COLUMNS: 1 no centroid, 2 masked pixels left out, 4 no PSF sum) after those.
+
+Aperture photometry (settings.cat_apphot, off by default): a 'new' table that carries it is written with the columns of
+aper_columns(table) after those: E_FLUX_APER_R<r>xFWHM / E_FLUXERR_APER_R<r>xFWHM per radius (qc.py:489-502), BKG_APER, BKGSTD_APER,
+NSKY_APER, FWHM_APER, FLAGS_APER; the dummy catalogue keeps the seven.
 """
 import os
 import shutil
@@ -51,8 +55,24 @@ TRANSFIT_COLUMNS = (('X_PSF_D', np.float32, 'pix'), ('Y_PSF_D', np.float32, 'pix
 # appended after TRANSFIT_COLUMNS to the 'trans' columns of a table that carries them
 TRANSSHAPE_COLUMNS = tuple((n + '_' + m + '_D', np.uint8 if n == 'FLAGS' else np.float32, '' if n in ('ELONG', 'CHI2', 'FLAGS') else 'pix')
                            for m in ('GAUSS', 'MOFFAT') for n in ('X', 'XERR', 'Y', 'YERR', 'FWHM', 'ELONG', 'CHI2', 'FLAGS'))
+# aperture photometry (settings.cat_apphot; zogy.optimal_subtraction(aper_phot=True)): the fixed columns behind the flux / error pair
+# of every radius, whose names carry the radius (aper_columns)
+APER_COLUMNS = (('BKG_APER', np.float32, 'e-'), ('BKGSTD_APER', np.float32, 'e-'), ('NSKY_APER', np.int32, ''), ('FWHM_APER', np.float32, 'pix'),
+                ('FLAGS_APER', np.uint8, ''))
 THUMBNAILS = ('RED', 'REF', 'D', 'SCORR')                     # plane order of zogy.thumbnail_stamps; blackbox.py:2701
 THUMBNAIL_COLUMNS = tuple('THUMBNAIL_' + c for c in THUMBNAILS)
+
+
+def aper_columns(table):
+    """the aperture columns a table carries, in the order they are written: every E_FLUX_APER_R<r>xFWHM with its E_FLUXERR_ twin in
+    the table's own order, then APER_COLUMNS -> ((name, dtype, unit), ...); () for a table without them"""
+    if table is None or APER_COLUMNS[-1][0] not in table:
+        return ()
+    out = []
+    for name in table:
+        if name.startswith('E_FLUX_APER_R'):
+            out += [(name, np.float32, 'e-'), (name.replace('E_FLUX_', 'E_FLUXERR_', 1), np.float32, 'e-')]
+    return tuple(out) + APER_COLUMNS
 
 
 def format_cat(table, cat_output, cat_type='new', header2add=None):
@@ -76,6 +96,10 @@ def format_cat(table, cat_output, cat_type='new', header2add=None):
             units[name] = unit
     if cat_type != 'trans' and table is not None and PHOT_COLUMNS[0][0] in table:
         for name, dt, unit in PHOT_COLUMNS:
+            cols[name] = np.asarray(table[name]).astype(dt)
+            units[name] = unit
+    if cat_type != 'trans':
+        for name, dt, unit in aper_columns(table):
             cols[name] = np.asarray(table[name]).astype(dt)
             units[name] = unit
     if cat_type == 'trans' and table is not None and TRANSFIT_COLUMNS[0][0] in table:

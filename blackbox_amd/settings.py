@@ -137,6 +137,15 @@ pixscale = 0.564               # [arcsec/pix] S-SEEING = S-FWHM x pixscale (find
 # Off by default: the fluxes keep their bits, `_cat.fits` its columns.
 phot_centroid = False          # E_FLUX_OPT / E_FLUXERR_OPT / SNR_OPT with the shifted PSF, masked pixels left out, FLAGS_OPT, sub-pixel X_POS / Y_POS, PHOT-CEN
 
+# ---- aperture photometry of `_cat.fits` with a local sky annulus (bbx_aper_phot; the E_FLUX_APER_R<r>xFWHM columns of
+# qc.py:489-502 with set_zogy.apphot_radii; [EXT] zogy.get_apflux / SExtractor: the rules of include/bbx.h here, this project's own) ----
+# Off by default: `_cat.fits` keeps its columns and the header gets none of the AP-* keys.
+cat_apphot = False             # E_FLUX_APER_R*xFWHM, E_FLUXERR_APER_R*xFWHM, BKG_APER, BKGSTD_APER, NSKY_APER, FWHM_APER, FLAGS_APER; the AP-* keys
+apphot_radii = (0.66, 1.5, 5.0)    # [FWHM] aperture radii (set_zogy.apphot_radii), at most 8
+apphot_sky_inout = (5.0, 7.0)  # [FWHM] inner and outer radius of the sky annulus
+apphot_local_sky = True        # subtract the annulus' clipped median from the aperture fluxes
+apphot_sky_nmin = 20           # fewer annulus pixels than this after clipping: no local sky (FLAGS_APER 8), nothing subtracted
+
 # ---- PSF model from the frame's own stars (`_psf.fits`, header keys PSF-*: blackbox.py:3085-3110, set_qc.py:293-296;
 # [EXT] PSFEx in zogy: the rules of include/bbx.h here; this project's own unless a PSFEx parameter is named) ----
 # Off by default: a frame without --psf_new is processed without a PSF as before.

@@ -40,6 +40,8 @@ from .starmatch import (MATCH_COLS, _MATCH_HDR, _MC, RefCatalog, empty_match_tab
                         match_scalars, match_stats)
 from .psfbuild import (BBX_ERR_NOTCONV, PSF_REASONS, _PSF_HDR, build_psf, psf_chi2, psf_chi2_median, psf_fit, psf_header,         # noqa: F401
                        psf_ncoef, psf_select, psf_stamps)
+from .aperphot import (APER_FEW_SKY, APER_MASKED, APER_NO_CENTROID, APER_OFF_FRAME, APER_SKY_CUT, APER_TOO_BIG, _radii as _aper_radii,         # noqa: F401
+                       aper_column_names, aper_columns, aper_fwhm, aper_header, aper_phot)
 from .align import (ALIGN_CLIP, ALIGN_DET, ALIGN_FAR, ALIGN_FEW_PAIRS, ALIGN_NMIN, ALIGN_NOT_PD, ALIGN_PAIR_CAP,         # noqa: F401
                     ALIGN_VOTE_FAILED, RefStars, _expect_list, align_apply, align_fit, align_grid, align_grid_host, align_grid_shape,
                     align_header, align_reference, align_sort, align_vote, remap_mask)
@@ -48,6 +50,7 @@ BBX_ERR_OVERFLOW, BBX_ERR_PSFWIN = -4, -6          # include/bbx.h
 BBX_OPT_ZOGY_KWIN_OFF = 4
 _trans_psffit = trans_psffit                                         # (_optimal_subtraction's switch bears the name)
 _trans_shapefit = trans_shapefit                                     # (_optimal_subtraction's switch bears the name)
+_aper_phot = aper_phot                                               # (_optimal_subtraction's switch bears the name)
 
 
 def optimal_subtraction(ctx, *args, **kw):
@@ -72,7 +75,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          objmask_max_frac=None, trans_psffit=False, trans_fit_size=None, trans_chi2_max=None,
                          trans_shapefit=False, trans_shape_size=None, trans_fwhm_gauss_min=None, trans_fwhm_gauss_max=None,
                          trans_elong_gauss_max=None, ref_align=False, align_poldeg=None, align_max_shift=None, align_bin=None,
-                         align_nbright=None, align_rounds=None, ref_stars=None):
+                         align_nbright=None, align_rounds=None, ref_stars=None, aper_phot=False, apphot_radii=None, apphot_sky_inout=None,
+                         apphot_local_sky=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -165,6 +169,17 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       in the stage): the frame goes on as one without a reference, A-P False -- it is never subtracted unregistered.
                       align_poldeg, align_max_shift, align_bin, align_nbright, align_rounds: settings.  False: no kernel of
                       bbx_align.hip is launched, no such keys
+      aper_phot     : True (with cat_extract and psf_new): every catalogue source gets its aperture fluxes and errors in circles of
+                      apphot_radii x FWHM with the exact circle-pixel overlap as weight, its local sky from the annulus
+                      apphot_sky_inout x FWHM (subtracted unless apphot_local_sky is False) and a flag byte (bbx_aper_phot, DESIGN.md
+                      4m), about the windowed centroids that phot_centroid, shapes or the registration made, else taken here; queued
+                      behind the photometry and read in the same copy back, with the frame's FWHM (aper_fwhm: one number per
+                      frame): res['catalog'] gains E_FLUX_APER_R<r>xFWHM, E_FLUXERR_APER_R<r>xFWHM per radius, BKG_APER, BKGSTD_APER,
+                      NSKY_APER, FWHM_APER, FLAGS_APER (APER_NO_CENTROID | APER_MASKED | APER_OFF_FRAME | APER_FEW_SKY | APER_SKY_CUT |
+                      APER_TOO_BIG), res['aper'] = dict(fwhm, radii, n_good), header_new gets AP-P, AP-FWHM, AP-NAPER, AP-R1..n,
+                      AP-SKYIN, AP-SKYOU, AP-LSKY, AP-NSTAR, AP-OPT1..n (aper_header).  An exception in the stage: today's catalogue,
+                      AP-P False.  False: no kernel of bbx_aper.hip is launched, no such keys or columns.  apphot_radii,
+                      apphot_sky_inout, apphot_local_sky: settings
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
             header (= header_new additions), header_trans)"""
     size = subimage_size or settings.subimage_size
@@ -181,6 +196,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     do_match = bool(match) and have_ref and have_psf and psf_ref is not None
     do_shapes = bool(shapes) and bool(cat_extract) and have_psf
     phot_centroid = bool(phot_centroid)
+    do_aper = bool(aper_phot) and bool(cat_extract) and have_psf
     do_align = bool(ref_align) and have_ref
     if do_align and ref_grid is not None:
         raise ValueError('ref_align=True makes the lattice itself: a ref_grid beside it is refused')
@@ -393,7 +409,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                 if do_match and not do_align:
                     ref_side = prepare_reference()
             else:                                                    # no model: the frame of today without --psf_new
-                want_phot = do_match = do_shapes = have_ref = False
+                want_phot = do_match = do_shapes = do_aper = have_ref = False
     if want_phot and sub_pn is not None:
         if ys.size:
             # peaks on masked pixels are dropped; their mask values come back with the fluxes (one host wait: the photometry
@@ -401,8 +417,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             d_ys, d_xs = push(ctx, ys.astype(np.int64), xs.astype(np.int64))
             d_mk = new_mask[d_ys, d_xs]
             peaks_off = None
-            if phot_centroid or do_shapes or do_align:
-                # the windowed centroids once: for the photometry (phot_centroid), the shapes, the registration and the star match
+            if phot_centroid or do_shapes or do_align or do_aper:
+                # the windowed centroids once: for the photometry (phot_centroid), the shapes, the apertures, the registration and the star match
                 d_y32, d_x32 = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
                 sigw = window_sigma(sub_pn)
             if phot_centroid:
@@ -436,11 +452,26 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                                phot_centroid=phot_centroid)
                 back += match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, match_dist, match_snr_min,
                                       peaks_off=peaks_off)
+            d_aper = None
+            if do_aper:
+                # the apertures and the annulus are queued behind the photometry and come back with it, the frame's FWHM too
+                try:
+                    if peaks_off is None:
+                        peaks_off = (d_y32, d_x32, win_centroid(ctx, work, d_y32, d_x32, sigw, size, nsy, nsx))
+                    d_afw = aper_fwhm(sub_pn)
+                    d_aper = _aper_phot(ctx, work, bstd, new_mask, d_y32, d_x32, peaks_off[2], d_afw.expand(nsub).contiguous(), size, nsy, nsx,
+                                        radii=apphot_radii, sky_inout=apphot_sky_inout, sub_sky=apphot_local_sky)
+                except Exception as ex:                              # the frame keeps today's catalogue
+                    logging.getLogger(__name__).warning('aperture photometry of the catalogue failed: %s', ex)
+                    d_aper = None
             if do_shapes:
                 back += [d_shp, d_sfl, d_stab]
             if phot_centroid:
                 back += [peaks_off[2], d_pfl]
+            if d_aper is not None:
+                back += list(d_aper) + [d_afw]
             got = fetch(ctx, *back)
+            aper = [got.pop() for _ in range(5)][::-1] if d_aper is not None else None      # (the last five: flux, err, sky, flags, FWHM)
             mk, f, e = got[:3]
             if do_match:
                 mtab, npairs = got[3:5]
@@ -452,12 +483,22 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                 pfl, poff = got.pop()[ok], got.pop()[ok]              # (the last two: the flags, then the offsets)
             if do_shapes:
                 shp, sfl, stab = got[-3][ok], got[-2][ok], got[-1]
+            if aper is not None:
+                aper = [a[ok] for a in aper[:4]] + [float(aper[4][0])]
         else:
             if do_align:
                 register_reference(None)
             f = e = np.zeros(0, np.float32)
             shp, sfl, stab = np.zeros((0, 8), np.float32), np.zeros(0, np.uint8), empty_shape_table(nsub)
             poff, pfl = np.zeros((0, 2), np.float32), np.zeros(0, np.uint8)
+            aper = None
+            if do_aper:
+                try:
+                    na = len(_aper_radii(apphot_radii))
+                    aper = [np.zeros((0, na), np.float32), np.zeros((0, na), np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.uint8),
+                            float(fetch(ctx, aper_fwhm(sub_pn))[0])]
+                except Exception as ex:
+                    logging.getLogger(__name__).warning('aperture photometry of the catalogue failed: %s', ex)
         if cat_extract:
             peaks = ys
             res['catalog'] = dict(Y_POS=ys.astype(np.float32) + 1, X_POS=xs.astype(np.float32) + 1,
@@ -476,6 +517,14 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             res['catalog'].update(shape_columns(ys, xs, shp, sfl))
             res['shapes'] = dict(table=stab, n_good=int(stab[nsub, _SC['n_fwhm']]))
             hdr.update(shape_header(stab, len(ys), settings.shape_nmin, settings.pixscale))
+        if do_aper and aper is not None:
+            cat = res['catalog']
+            acols = aper_columns(*aper, radii=apphot_radii)
+            hdr.update(aper_header(True, aper[4], apphot_radii, apphot_sky_inout, apphot_local_sky, acols, cat['E_FLUX_OPT'], cat['SNR_OPT']))
+            cat.update(acols)
+            res['aper'] = dict(fwhm=aper[4], radii=_aper_radii(apphot_radii), n_good=hdr['AP-NSTAR'][0])
+        elif do_aper:
+            hdr.update(aper_header(False))
     if 'S-BKG' not in hdr:
         scal_n = host_side_meanwhile()
     if do_align and have_ref and 'align' not in res:

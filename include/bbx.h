@@ -925,6 +925,47 @@ int bbx_psf_optflux_shift(bbx_ctx *ctx, int ny, int nx, const float *d_D, const 
                           const int32_t *d_ys, const int32_t *d_xs, const float *d_off, float *d_flux, float *d_err,
                           uint8_t *d_flags, void *stream);
 
+/* ---- aperture photometry with a local sky annulus (bbx_aper.hip): the model-independent fluxes of the catalogue,
+ * E_FLUX_APER_R<r>xFWHM / E_FLUXERR_APER_R<r>xFWHM of qc.py:489-502 (set_zogy.apphot_radii).  zogy's get_apflux and SExtractor are
+ * [EXT], not in the reference tree: only the column names and the radii follow the reference, the rules below are THIS PROJECT'S
+ * OWN and parity with zogy's numbers is unpinned.  Any image and any positions: per source s < nsrc at the integer peak (d_ys, d_xs)
+ * of d_D[ny][nx], all geometry in float64 and no product contracted into an fma:
+ *  1 centre = peak + d_off[s] = (dy, dx) (bbx_win_centroid: relative to the peak; d_off NULL: zeros).  An offset that is not finite,
+ *    or beyond 1e6 pixels in either axis, is no centroid: the peak alone, flag 1.
+ *  2 f = d_fwhm[tile of the integer peak], tile = min(max(y / size, 0), nsy - 1) * nsx + the same of x (zogy.tile_index's clamp);
+ *    r_k = (double) radii[k] * (double) f for the naper <= BBX_APER_NMAX apertures (radii: a HOST array, in FWHM),
+ *    r_in, r_out = (double) sky_in * f, (double) sky_out * f.
+ *  3 too big, flag 32: f not positive and finite, or the largest r_k or r_out beyond BBX_APER_RMAX pixels.  Every float of the row is
+ *    NaN, n = 0, nothing else is measured.  (The bound sizes the kernel: a window of at most 97 x 97 pixels, at most
+ *    pi (48 + 0.71)^2 = 7454 pixel centres in the annulus, which fit the 8192 floats of one 32 KB LDS buffer.)
+ *  4 a pixel iy, ix lies at dy = (double)(iy - yp) - (double) off_y, dx likewise; d^2 = dy dy + dx dx.  It is USED when it is on the
+ *    frame, d_mask == 0 there (d_mask may be NULL), D is finite and sigma is finite; sigma from the frame d_sigma[ny][nx] or read off
+ *    the mini image sigma_mini (bbx_psf_optflux_shift's: exactly one of the two), V = max(D, 0) + sigma^2 in float32.
+ *  5 the weight of a pixel in aperture k is the exact area of the disc of radius r_k inside the unit pixel: 1 when the farthest corner
+ *    is inside, (|dx| + 1/2)^2 + (|dy| + 1/2)^2 <= r^2; 0 when the nearest point is not, max(|dx| - 1/2, 0)^2 + max(|dy| - 1/2, 0)^2
+ *    >= r^2; otherwise the clipped chord height integrated over the pixel's x-range [max(|dx| - 1/2, -r), min(|dx| + 1/2, r)], split at
+ *    +-sqrt(r^2 - y0^2), +-sqrt(r^2 - y1^2) (y0, y1 = |dy| -+ 1/2; the four clamped into the range and sorted), with
+ *    G(x) = (x sqrt(r^2 - x^2) + r^2 asin(x / r)) / 2; on each piece the top is the flat edge y1 (y1 <= h at the midpoint, h = sqrt(r^2
+ *    - m^2)) or the arc, the bottom the flat edge y0 (y0 >= -h) or the arc; the sum clamped to [0, 1].  No sub-pixel sampling.
+ *  6 S_k = sum w D, A_k = sum w, V_k = sum w V over the used pixels, in float64.  Flag 2: a pixel that the largest aperture touches
+ *    (weight > 0: its nearest point inside) is on the frame and not used; flag 4: such a pixel lies off the frame.
+ *  7 the sky sample: the used pixels with r_in^2 <= d^2 < r_out^2, whole pixels by their centres; flag 16 when such a pixel is not used
+ *    or off the frame.  Sorted and clipped by bbx_match_stats's rule (3 sigma about the exact median -- an even count: the float64
+ *    midpoint --, population std, at most 5 rounds, stop when nothing is clipped) -> sky, sd, n.  n < sky_nmin (>= 1): flag 8, the
+ *    sky outputs are (NaN, NaN, n) and nothing is subtracted.
+ *  8 F_k = S_k - sky A_k when sub_sky is set and flag 8 is not, else S_k; E_k = sqrt(V_k + [sky subtracted] A_k^2 (pi / 2) sd^2 / n);
+ *    A_k == 0: both NaN.  d_flux[s][k], d_err[s][k], d_sky[s] = (sky, sd, n) as float32, rounded once; d_flags[s] u8.
+ * Deterministic: the sample's order of arrival in LDS does not reach the result (it is sorted), every sum is taken in a fixed order
+ * (per thread over its pixels, then the crossed pixels its wave noted, the wave, the four waves in order): same input -> same bits.
+ * nsrc == 0: nothing is launched, the outputs may be NULL.  One workgroup of 256 per source.                                  */
+#define BBX_APER_RMAX 48        /* [pix] largest aperture or annulus radius */
+#define BBX_APER_NMAX 8         /* apertures of one call */
+int bbx_aper_phot(bbx_ctx *ctx, int ny, int nx, const float *d_D, const float *d_sigma,
+                  const bbx_spline_image *sigma_mini, const uint8_t *d_mask, int nsrc, const int32_t *d_ys,
+                  const int32_t *d_xs, const float *d_off, const float *d_fwhm, int size, int nsy, int nsx, int naper,
+                  const float *radii, float sky_in, float sky_out, int sub_sky, int sky_nmin, float *d_flux, float *d_err,
+                  float *d_sky, uint8_t *d_flags, void *stream);
+
 /* ---- transient vetting: the PSF of D per sub-image and its fit to D per candidate (bbx_transfit.hip).  zogy fits
  * the PSF of the difference image to D at every candidate with free position (E_FLUX_PSF_D, X_PSF_D, Y_PSF_D, CHI2_PSF_D) ([EXT]:
  * zogy is not in the reference tree; the rules below are THIS PROJECT'S OWN, parity is unpinned).
