@@ -57,20 +57,6 @@ static inline bool al_bins(double max_shift, double bin, int* nb) {
     return true;
 }
 
-// ascending bitonic sort of n = 2^k keys in LDS by the whole workgroup (ready for every thread on return)
-template <typename T> __device__ __forceinline__ void al_lds_sort(T* s, int n) {
-    for (int k = 2; k <= n; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < n / 2; t += AL_BLOCK) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i + j;
-                const bool asc = (i & k) == 0;
-                const T a = s[i], b = s[p];
-                if ((a > b) == asc) { s[i] = b; s[p] = a; }
-            }
-            __syncthreads();
-        }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // vote
 // ---------------------------------------------------------------------------------------------------------------------
@@ -133,7 +119,7 @@ __global__ __launch_bounds__(AL_BLOCK) void k_vote_select(al_list A, al_list B, 
             if (pos < AL_NBRIGHT) s_key[pos] = key;                  // (the keys are unique: exactly k of them are <= thr)
         }
     __syncthreads();
-    al_lds_sort(s_key, AL_NBRIGHT);
+    lds_sort<AL_BLOCK>(s_key, AL_NBRIGHT);
     for (int r = tid; r < k; r += AL_BLOCK) {
         const int i = (int)(s_key[r] & 0xffffffffu);
         if (i < L.n) {
@@ -260,7 +246,7 @@ __device__ __forceinline__ double vote_median(const float* v, int m, uint32_t* s
     __syncthreads();
     for (int i = threadIdx.x; i < n2; i += AL_BLOCK) s[i] = i < m ? f2key(v[i]) : 0xffffffffu;
     __syncthreads();
-    al_lds_sort(s, n2);
+    lds_sort<AL_BLOCK>(s, n2);
     if (m == 0) return __builtin_nan("");
     return 0.5 * ((double)key2f(s[(m - 1) / 2]) + (double)key2f(s[m / 2]));
 }
@@ -395,11 +381,11 @@ __device__ __forceinline__ void fit_body(const fit_args& a, double* red) {
                     bx[r] += Bv[r] * X; by[r] += Bv[r] * Y;
                 }
             }
-            cnt = psb_block_sum<FIT_WAVES>(cnt, red);
+            cnt = wg_sum_seq<FIT_WAVES>(cnt, red);
 #pragma unroll
-            for (int k = 0; k < NC * (NC + 1) / 2; k++) M[k] = psb_block_sum<FIT_WAVES>(M[k], red);
+            for (int k = 0; k < NC * (NC + 1) / 2; k++) M[k] = wg_sum_seq<FIT_WAVES>(M[k], red);
 #pragma unroll
-            for (int k = 0; k < NC; k++) { bx[k] = psb_block_sum<FIT_WAVES>(bx[k], red); by[k] = psb_block_sum<FIT_WAVES>(by[k], red); }
+            for (int k = 0; k < NC; k++) { bx[k] = wg_sum_seq<FIT_WAVES>(bx[k], red); by[k] = wg_sum_seq<FIT_WAVES>(by[k], red); }
             n_used = cnt;
             if (cnt < (double)max(a.nmin, NC)) { flags |= 2; break; }                  // (every thread holds the same sums)
             // Cholesky, lower factor in place of the triangle; a pivot not above 1e-12 of its diagonal element: not positive definite
@@ -446,8 +432,8 @@ __device__ __forceinline__ void fit_body(const fit_args& a, double* red) {
                 for (int k = 0; k < NC; k++) { rx = rx - c[k] * Bv[k]; ry = ry - c[6 + k] * Bv[k]; }
                 sx += rx * rx; sy += ry * ry;
             }
-            sx = psb_block_sum<FIT_WAVES>(sx, red);
-            sy = psb_block_sum<FIT_WAVES>(sy, red);
+            sx = wg_sum_seq<FIT_WAVES>(sx, red);
+            sy = wg_sum_seq<FIT_WAVES>(sy, red);
             for (int k = 0; k < 12; k++) coef[k] = c[k];
             rms_x = sqrt(sx / cnt); rms_y = sqrt(sy / cnt);
             if (pass == 3) break;                                    // (the set the last solve used is the one reported)

@@ -4,7 +4,8 @@
 //
 //   k_aper_phot : one workgroup of 256 per source, all geometry in float64 (the Makefile's -ffp-contract=off keeps d^2 unfused)
 //     1 sky     the annulus' used pixels -> LDS (appended per wave: one LDS atomic a wave and round; the order of arrival does
-//               not reach the result, the sample is sorted next), bitonic sort, the clip of bbx_stats.h on the sorted sample
+//               not reach the result, the sample is sorted next), then stats_clip<256> of bbx_stats.h: the one sort and clip
+//               that bbx_match.hip and bbx_shapes.hip run with 1024 threads
 //     2 classes the window of the largest aperture once more: a pixel inside aperture k adds itself with weight 1; one the
 //               circle crosses is noted in the wave's own list of that aperture (in the sample's LDS, which is free by now)
 //     3 arcs    the lists, 64 entries at a time: only here sqrt and asin in float64 are paid, by full waves
@@ -71,68 +72,6 @@ __device__ __noinline__ double apr_partial(double ax, double ay, double r, doubl
         area = area + (on ? top - bot : 0.0);
     }
     return fmin(fmax(area, 0.0), 1.0);                               // (rounding may leave the sum a few 1e-17 outside)
-}
-
-// ---- the clip of bbx_stats.h's stats_clip for a workgroup of 256 --------------------------------------------------------
-// sums of two doubles over the workgroup, the same values in every thread; red[2][2][APR_WAVES] is used alternately
-__device__ __forceinline__ void apr_block_sum(double& a, double& b, double* red, int& ph) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    a = wave_sum_f64(a); b = wave_sum_f64(b);
-    if (lane == 0) { red[(ph * 2 + 0) * APR_WAVES + wave] = a; red[(ph * 2 + 1) * APR_WAVES + wave] = b; }
-    __syncthreads();
-    const double* ra = red + (ph * 2 + 0) * APR_WAVES;
-    const double* rb = red + (ph * 2 + 1) * APR_WAVES;
-    a = (ra[0] + ra[1]) + (ra[2] + ra[3]);
-    b = (rb[0] + rb[1]) + (rb[2] + rb[3]);
-    ph ^= 1;
-}
-
-// vals[0..m) -> sorted (bitonic network over the next power of two, padded with +inf), then 3 sigma about the exact median,
-// spread = population std, at most 5 rounds, stop when nothing is clipped -> n, median, std in every thread
-__device__ __forceinline__ void apr_clip(float* vals, int m, double* red, double out[3]) {
-    const int tid = threadIdx.x;
-    int P = 2;
-    while (P < m) P <<= 1;
-    for (int i = m + tid; i < P; i += APR_BLOCK) vals[i] = __builtin_inff();
-    __syncthreads();
-    for (int kk = 2; kk <= P; kk <<= 1)
-        for (int j = kk >> 1; j >= 1; j >>= 1) {
-            for (int t = tid; t < P / 2; t += APR_BLOCK) {
-                const int i = 2 * j * (t / j) + (t % j);
-                stats_cswap(vals, i, i + j, (i & kk) == 0);
-            }
-            __syncthreads();
-        }
-    int lo = 0, hi = m, ph = 0;
-    double med = 0.0, std = 0.0;
-    for (int round = 0; round <= 5; round++) {                       // rounds 0..4 clip; the last pass only takes the statistics
-        const int n = hi - lo;
-        if (n == 0) break;
-        med = (n & 1) ? (double)vals[lo + n / 2] : ((double)vals[lo + n / 2 - 1] + (double)vals[lo + n / 2]) / 2.0;
-        double s = 0.0, z = 0.0;
-        for (int i = lo + tid; i < hi; i += APR_BLOCK) s += (double)vals[i];
-        apr_block_sum(s, z, red, ph);
-        const double mean = s / (double)n;
-        double ss = 0.0;
-        for (int i = lo + tid; i < hi; i += APR_BLOCK) { const double d = mean - (double)vals[i]; ss += d * d; }
-        apr_block_sum(ss, z, red, ph);
-        std = sqrt(ss / (double)n);
-        if (round == 5) break;
-        const double L = med - 3.0 * std, H = med + 3.0 * std;
-        double nl = 0.0, nh = 0.0;
-        for (int i = lo + tid; i < hi; i += APR_BLOCK) {
-            const double v = (double)vals[i];
-            if (!(v >= L)) nl += 1.0;
-            else if (!(v <= H)) nh += 1.0;
-        }
-        apr_block_sum(nl, nh, red, ph);
-        if (nl == 0.0 && nh == 0.0) break;
-        lo += (int)nl; hi -= (int)nh;
-    }
-    const int n = hi - lo;
-    const double nan = __builtin_nan("");
-    out[0] = (double)n; out[1] = n ? med : nan; out[2] = n ? std : nan;
-    __syncthreads();                                                 // vals is used again by the caller
 }
 
 // ---- the kernel -------------------------------------------------------------------------------------------------------------
@@ -223,8 +162,10 @@ __global__ __launch_bounds__(APR_BLOCK) void k_aper_phot(apr_args a, bbx_spl sp)
     }
     __syncthreads();
     const int msky = min(s_cnt, APR_CAP);
-    double st[3];
-    apr_clip(s_vals, msky, s_red, st);                               // (ends behind a barrier: s_vals is free)
+    double st[4];                                                    // n, median, mean (not used), std
+    float vlo, vhi;
+    int ph = 0;
+    stats_clip<APR_BLOCK>(s_vals, msky, s_red, ph, st, vlo, vhi);    // (ends behind a barrier: s_vals is free)
     const bool few = st[0] < (double)a.sky_nmin;
     if (few) fl |= 8u;
     const bool subtract = a.sub_sky && !few;
@@ -312,7 +253,7 @@ __global__ __launch_bounds__(APR_BLOCK) void k_aper_phot(apr_args a, bbx_spl sp)
         double F = Sk, E2 = Vk;
         if (subtract) {
             F = Sk - st[1] * Ak;
-            E2 = Vk + Ak * Ak * (3.141592653589793 / 2.0) * st[2] * st[2] / st[0];
+            E2 = Vk + Ak * Ak * (3.141592653589793 / 2.0) * st[3] * st[3] / st[0];
         }
         const bool none = Ak == 0.0;
         a.flux[s * a.naper + k] = none ? (float)nan : (float)F;
@@ -320,7 +261,7 @@ __global__ __launch_bounds__(APR_BLOCK) void k_aper_phot(apr_args a, bbx_spl sp)
     }
     if (tid == 0) {
         a.sky[3 * s] = few ? (float)nan : (float)st[1];
-        a.sky[3 * s + 1] = few ? (float)nan : (float)st[2];
+        a.sky[3 * s + 1] = few ? (float)nan : (float)st[3];
         a.sky[3 * s + 2] = (float)st[0];
         a.flags[s] = (uint8_t)s_fl;
     }

@@ -343,21 +343,82 @@ template <int NR, bool ROLLED = false> __device__ __forceinline__ void wave_sort
     }
 }
 
-// ---- shared by bbx_psfbuild.hip, bbx_psfphot.hip and bbx_transfit.hip ----
-// sum of one double per thread over a workgroup of NW waves, the same value in every thread: wave sums by DPP, the wave totals
-// through LDS, added in wave order.  red[NW]; the caller's next use of red is behind a barrier of its own
-template <int NW>
-__device__ __forceinline__ double psb_block_sum(double v, double* red) {
-    v = wave_sum_f64(v);
-    __syncthreads();                                                 // (red may still be read from the call before)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; w++) t += red[w];
-    return t;
+// ---- workgroup primitives: one LDS sort and the two orders in which the project adds wave totals ----
+// compare-exchange of elements i < p of the LDS sort, by element type: min / max with both stores for float (the values are
+// not NaN; -0.0 and +0.0 are placed as fminf / fmaxf place them), compare and conditional swap for the integer keys
+__device__ __forceinline__ void lds_cswap(float* s, int i, int p, bool asc) {
+    const float a = s[i], b = s[p];
+    const float lo = fminf(a, b), hi = fmaxf(a, b);
+    s[i] = asc ? lo : hi;
+    s[p] = asc ? hi : lo;
+}
+template <typename T> __device__ __forceinline__ void lds_cswap(T* s, int i, int p, bool asc) {
+    const T a = s[i], b = s[p];
+    if ((a > b) == asc) { s[i] = b; s[p] = a; }
+}
+// ascending bitonic sort of n = 2^k elements in LDS by the whole workgroup of BLOCK threads (ready for every thread on return)
+template <int BLOCK, typename T> __device__ __forceinline__ void lds_sort(T* s, int n) {
+    for (int k = 2; k <= n; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < n / 2; t += BLOCK) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                lds_cswap(s, i, i + j, (i & k) == 0);
+            }
+            __syncthreads();
+        }
 }
 
+// Sums of doubles over a workgroup of NW waves, the same values in every thread: wave sums by DPP, the wave totals through LDS.
+// The order in which the wave totals are added is part of the pinned bits; there are two, and a call site keeps its own.
+// wg_sum_tree: the balanced pairwise tree, (r0 + r1) + (r2 + r3) for four waves.  The two halves of red[N][2][NW] are used
+// alternately (ph), so one barrier per call is enough; the half is the inner index, so that calls with different N on one
+// buffer (k_thumb_png8: red[Nmax][2][NW]) never write where the call before may still read
+template <int NW> __device__ __forceinline__ double wg_tree(const double* r) {
+    if constexpr (NW == 1) return r[0];
+    else return wg_tree<NW / 2>(r) + wg_tree<NW / 2>(r + NW / 2);
+}
+template <int NW, int N>
+__device__ __forceinline__ void wg_sum_tree(double (&v)[N], double* red, int& ph) {
+    static_assert(NW > 0 && (NW & (NW - 1)) == 0, "wg_sum_tree: a power of two of waves");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] = wave_sum_f64(v[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; k++) red[(k * 2 + ph) * NW + wave] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] = wg_tree<NW>(red + (k * 2 + ph) * NW);
+    ph ^= 1;
+}
+// wg_sum_seq: wave order, ((r0 + r1) + r2) + ...  red[NW][N]; the caller's next use of red is behind a barrier of its own
+template <int NW, int N>
+__device__ __forceinline__ void wg_sum_seq(double (&v)[N], double* red) {
+#pragma unroll
+    for (int q = 0; q < N; q++) v[q] = wave_sum_f64(v[q]);
+    __syncthreads();                                                 // (red may still be read from the call before)
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < N; q++) red[(threadIdx.x >> 6) * N + q] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < N; q++) {
+        double t = red[q];
+#pragma unroll
+        for (int w = 1; w < NW; w++) t += red[w * N + q];
+        v[q] = t;
+    }
+}
+template <int NW>
+__device__ __forceinline__ double wg_sum_seq(double v, double* red) {
+    double a[1] = {v};
+    wg_sum_seq<NW, 1>(a, red);
+    return a[0];
+}
+
+// ---- shared by bbx_psfbuild.hip, bbx_psfphot.hip and bbx_transfit.hip ----
 // oracle/coadd.py lanczos3_taps: k(t) = sinc(t) sinc(t / 3) at t = frac - (-2 .. 3), 0 for |t| >= 3, divided by their sum in
 // float64, then float32
 __device__ __forceinline__ void psb_taps(float frac, float w[6]) {
@@ -414,10 +475,10 @@ __device__ __forceinline__ void psb_shift_stamp(float* a, float* b, int S, float
     psb_shift_pass<false, BLOCK>(b, a, S, dy);
     __syncthreads();
 }
-// sum of the stamp's pixels in float64: per thread over pixels tid, tid + BLOCK, ..., then psb_block_sum
+// sum of the stamp's pixels in float64: per thread over pixels tid, tid + BLOCK, ..., then wg_sum_seq
 template <int BLOCK>
 __device__ __forceinline__ double psb_stamp_sum(const float* a, int npx, double* red) {
     double part = 0.0;
     for (int k = threadIdx.x; k < npx; k += BLOCK) part += (double)a[k];
-    return psb_block_sum<BLOCK / 64>(part, red);
+    return wg_sum_seq<BLOCK / 64>(part, red);
 }

@@ -215,24 +215,24 @@ __global__ __launch_bounds__(STATS_BLOCK) void k_match_stats(stats_in in, int si
     // ---- flux ratio, and the weighted mean over its clipped sample
     match_walk<Q_FR>(in, sg, base, s_vals, 0.f, 0.f, z0, z1);
     __syncthreads();
-    stats_clip(s_vals, m, s_red, ph, st, vlo, vhi);
-    double sw = 0.0, swf = 0.0;
-    if (st[0] > 0.0) match_walk<Q_WEIGHT>(in, sg, base, s_vals, vlo, vhi, sw, swf);
-    stats_block_sum(sw, swf, s_red, ph);
+    stats_clip<STATS_BLOCK>(s_vals, m, s_red, ph, st, vlo, vhi);
+    double sw[2] = {0.0, 0.0};                                       // sum of w, sum of w f
+    if (st[0] > 0.0) match_walk<Q_WEIGHT>(in, sg, base, s_vals, vlo, vhi, sw[0], sw[1]);
+    wg_sum_tree<STATS_WAVES>(sw, s_red, ph);
     if (tid == 0) {
         o[0] = (double)n; o[1] = st[0]; o[2] = st[1]; o[3] = st[2]; o[4] = st[3];
-        o[5] = st[0] > 0.0 ? swf / sw : nan;
-        o[6] = st[0] > 0.0 ? 1.0 / sqrt(sw) : nan;
+        o[5] = st[0] > 0.0 ? sw[1] / sw[0] : nan;
+        o[6] = st[0] > 0.0 ? 1.0 / sqrt(sw[0]) : nan;
         o[15] = (double)sg.stride;
     }
     // ---- dx, dy
     match_walk<Q_DX>(in, sg, base, s_vals, 0.f, 0.f, z0, z1);
     __syncthreads();
-    stats_clip(s_vals, m, s_red, ph, st, vlo, vhi);
+    stats_clip<STATS_BLOCK>(s_vals, m, s_red, ph, st, vlo, vhi);
     if (tid == 0) { o[7] = st[0]; o[8] = st[1]; o[9] = st[2]; o[10] = st[3]; }
     match_walk<Q_DY>(in, sg, base, s_vals, 0.f, 0.f, z0, z1);
     __syncthreads();
-    stats_clip(s_vals, m, s_red, ph, st, vlo, vhi);
+    stats_clip<STATS_BLOCK>(s_vals, m, s_red, ph, st, vlo, vhi);
     if (tid == 0) { o[11] = st[0]; o[12] = st[1]; o[13] = st[2]; o[14] = st[3]; }
 }
 

@@ -103,7 +103,7 @@ extern "C" int bbx_psf_select(bbx_ctx* ctx, int n, const int32_t* d_ys, const in
 // ---------------------------------------------------------------------------------------------------------------------
 // vignettes
 // ---------------------------------------------------------------------------------------------------------------------
-// (psb_block_sum, psb_taps: bbx_common.h -- bbx_psfphot.hip shifts its stamps with the same taps)
+// (wg_sum_seq, psb_taps: bbx_common.h -- bbx_psfphot.hip shifts its stamps with the same taps)
 __global__ __launch_bounds__(PSB_BLOCK) void k_psf_stamps(int ny, int nx, const float* __restrict__ img, const uint8_t* __restrict__ mask,
                                                           int nsrc, const int32_t* __restrict__ ys, const int32_t* __restrict__ xs,
                                                           const float* __restrict__ shapes, const float* __restrict__ sig,
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(PSB_BLOCK) void k_psf_stamps(int ny, int nx, const 
             s_st[k] = t;
             if ((r - h) * (r - h) + (c - h) * (c - h) <= h * h) part += (double)t;
         }
-        norm = psb_block_sum<PSB_BLOCK / 64>(part, s_red);
+        norm = wg_sum_seq<PSB_BLOCK / 64>(part, s_red);
         if (!(norm > 0.0) || !(norm < 1.0e300)) bad = 1;             // (uniform: every thread holds the same norm)
         if (!bad) {
             const double s2 = (double)sg * (double)sg, n2 = norm * norm;
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(PSB_BLOCK) void k_psf_chi2(int npix, int ncoef, con
         const double d = (double)I[(size_t)s * npix + p] - (double)m;
         part += (double)w[(size_t)s * npix + p] * (d * d);
     }
-    const double tot = psb_block_sum<PSB_BLOCK / 64>(part, s_red);
+    const double tot = wg_sum_seq<PSB_BLOCK / 64>(part, s_red);
     if (tid == 0) chi2[s] = (float)(tot / (double)npix);
 }
 

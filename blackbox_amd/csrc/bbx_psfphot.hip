@@ -9,7 +9,7 @@
 //     3 norm    sum of the S x S pixels in float64 (psb_stamp_sum)
 //     4 sums    num = sum P D / V, den = sum P^2 / V in float64, V = max(D, 0) + sigma^2 in float32 (k_variance's)
 //   Block sums: per-thread partial sums over pixels tid, tid + 256, ..., the waves' totals through LDS in wave order
-//   (psb_block_sum): no atomics, the same input gives the same bits.
+//   (wg_sum_seq): no atomics, the same input gives the same bits.
 #include "bbx_spline.h"
 
 #define PPH_BLOCK  256
@@ -112,8 +112,8 @@ __global__ __launch_bounds__(PPH_BLOCK) void k_psf_optflux_shift(pph_args a, bbx
         }
     }
     if (__syncthreads_or(hit)) fl |= 2u;
-    num = psb_block_sum<PPH_BLOCK / 64>(num, s_red);
-    den = psb_block_sum<PPH_BLOCK / 64>(den, s_red);
+    num = wg_sum_seq<PPH_BLOCK / 64>(num, s_red);
+    den = wg_sum_seq<PPH_BLOCK / 64>(den, s_red);
     if (tid == 0) {
         a.flux[s] = den > 0.0 ? (float)(num / den) : 0.f;
         a.err[s] = den > 0.0 ? (float)(1.0 / sqrt(den)) : 0.f;

@@ -157,12 +157,12 @@ __global__ __launch_bounds__(STATS_BLOCK) void k_shape_stats(shape_in in, int si
     shape_item<SQ_FWHM> fw = {in, s_vals};
     stats_walk<false>(sg, base, fw);
     __syncthreads();
-    stats_clip(s_vals, m, s_red, ph, st, vlo, vhi);
+    stats_clip<STATS_BLOCK>(s_vals, m, s_red, ph, st, vlo, vhi);
     if (tid == 0) { o[0] = (double)n; o[1] = (double)sg.stride; o[2] = st[0]; o[3] = st[1]; o[4] = st[3]; }
     shape_item<SQ_ELONG> el = {in, s_vals};
     stats_walk<false>(sg, base, el);
     __syncthreads();
-    stats_clip(s_vals, m, s_red, ph, st, vlo, vhi);
+    stats_clip<STATS_BLOCK>(s_vals, m, s_red, ph, st, vlo, vhi);
     if (tid == 0) { o[5] = st[0]; o[6] = st[1]; o[7] = st[3]; }
 }
 

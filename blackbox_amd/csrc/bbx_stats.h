@@ -1,6 +1,7 @@
-// bbx_stats.h -- device code shared by bbx_match.hip, bbx_shapes.hip and bbx_psfbuild.hip: clipped statistics of a
+// bbx_stats.h -- device code shared by bbx_match.hip, bbx_shapes.hip, bbx_psfbuild.hip and bbx_aper.hip: clipped statistics of a
 // (y, x)-sorted source list per sub-image tile and of the frame (one workgroup of STATS_BLOCK threads per segment: count,
 // strided selection in list order, LDS sort, sigma clipping on the sorted sample, float64 sums in a fixed order).
+// bbx_aper.hip takes the clip alone (stats_clip<256> on its annulus sample).
 #pragma once
 #include "bbx_common.h"
 
@@ -34,24 +35,6 @@ __device__ __forceinline__ stats_seg stats_segment(int seg, int size, int nsy, i
     }
     sg.stride = 1;
     return sg;
-}
-
-// sums of two doubles over the workgroup, the same values in every thread: wave sums by DPP, the wave totals through LDS and
-// added as a fixed tree.  red[2][2][STATS_WAVES] is used alternately, so one barrier per call is enough
-__device__ __forceinline__ void stats_block_sum(double& a, double& b, double* red, int& ph) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    a = wave_sum_f64(a); b = wave_sum_f64(b);
-    if (lane == 0) { red[(ph * 2 + 0) * STATS_WAVES + wave] = a; red[(ph * 2 + 1) * STATS_WAVES + wave] = b; }
-    __syncthreads();
-    double t[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const double* r = red + (ph * 2 + k) * STATS_WAVES;
-        t[k] = (((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))) +
-               (((r[8] + r[9]) + (r[10] + r[11])) + ((r[12] + r[13]) + (r[14] + r[15])));
-    }
-    a = t[0]; b = t[1];
-    ph ^= 1;
 }
 
 // One walk over the segment's part of the list in list order: every wave takes a contiguous share, 64 sources at a time.
@@ -96,55 +79,43 @@ __device__ __forceinline__ int stats_count(stats_seg& sg, Item& it, int* cnt, in
     return n;
 }
 
-__device__ __forceinline__ void stats_cswap(float* v, int i, int j, bool up) {
-    const float a = v[i], b = v[j];
-    const float lo = fminf(a, b), hi = fmaxf(a, b);                  // (the values are not NaN)
-    v[i] = up ? lo : hi;
-    v[j] = up ? hi : lo;
-}
-
-// vals[0..m) -> sorted (bitonic network over the next power of two, padded with +inf), then box_stats: 3 sigma about the exact
+// vals[0..m) -> sorted (lds_sort over the next power of two, padded with +inf), then box_stats: 3 sigma about the exact
 // median, spread = population std, at most 5 rounds, stop when nothing is clipped.  On the sorted sample a clipped set is a
-// range [lo, hi).  -> n, median, mean, std (every thread), and the range's end values
+// range [lo, hi).  -> n, median, mean, std (every thread), and the range's end values.  By a workgroup of BLOCK threads;
+// red[2][2][BLOCK / 64] and ph: wg_sum_tree's
+template <int BLOCK>
 __device__ __forceinline__ void stats_clip(float* vals, int m, double* red, int& ph, double out[4], float& vlo, float& vhi) {
     const int tid = threadIdx.x;
     int P = 2;
     while (P < m) P <<= 1;
-    for (int i = m + tid; i < P; i += STATS_BLOCK) vals[i] = __builtin_inff();
+    for (int i = m + tid; i < P; i += BLOCK) vals[i] = __builtin_inff();
     __syncthreads();
-    for (int kk = 2; kk <= P; kk <<= 1)
-        for (int j = kk >> 1; j >= 1; j >>= 1) {
-            for (int t = tid; t < P / 2; t += STATS_BLOCK) {
-                const int i = 2 * j * (t / j) + (t % j);
-                stats_cswap(vals, i, i + j, (i & kk) == 0);
-            }
-            __syncthreads();
-        }
+    lds_sort<BLOCK>(vals, P);
     int lo = 0, hi = m;
     double med = 0.0, mean = 0.0, std = 0.0;
     for (int round = 0; round <= 5; round++) {                       // rounds 0..4 clip; the last pass only takes the statistics
         const int n = hi - lo;
         if (n == 0) break;
         med = (n & 1) ? (double)vals[lo + n / 2] : ((double)vals[lo + n / 2 - 1] + (double)vals[lo + n / 2]) / 2.0;
-        double s = 0.0, z = 0.0;
-        for (int i = lo + tid; i < hi; i += STATS_BLOCK) s += (double)vals[i];
-        stats_block_sum(s, z, red, ph);
-        mean = s / (double)n;
-        double ss = 0.0;
-        for (int i = lo + tid; i < hi; i += STATS_BLOCK) { const double d = mean - (double)vals[i]; ss += d * d; }
-        stats_block_sum(ss, z, red, ph);
-        std = sqrt(ss / (double)n);
+        double s[2] = {0.0, 0.0};
+        for (int i = lo + tid; i < hi; i += BLOCK) s[0] += (double)vals[i];
+        wg_sum_tree<BLOCK / 64>(s, red, ph);
+        mean = s[0] / (double)n;
+        double ss[2] = {0.0, 0.0};
+        for (int i = lo + tid; i < hi; i += BLOCK) { const double d = mean - (double)vals[i]; ss[0] += d * d; }
+        wg_sum_tree<BLOCK / 64>(ss, red, ph);
+        std = sqrt(ss[0] / (double)n);
         if (round == 5) break;
         const double L = med - 3.0 * std, H = med + 3.0 * std;
-        double nl = 0.0, nh = 0.0;
-        for (int i = lo + tid; i < hi; i += STATS_BLOCK) {
+        double nc[2] = {0.0, 0.0};                                   // clipped below, above
+        for (int i = lo + tid; i < hi; i += BLOCK) {
             const double v = (double)vals[i];
-            if (!(v >= L)) nl += 1.0;
-            else if (!(v <= H)) nh += 1.0;
+            if (!(v >= L)) nc[0] += 1.0;
+            else if (!(v <= H)) nc[1] += 1.0;
         }
-        stats_block_sum(nl, nh, red, ph);
-        if (nl == 0.0 && nh == 0.0) break;
-        lo += (int)nl; hi -= (int)nh;
+        wg_sum_tree<BLOCK / 64>(nc, red, ph);
+        if (nc[0] == 0.0 && nc[1] == 0.0) break;
+        lo += (int)nc[0]; hi -= (int)nc[1];
     }
     const int n = hi - lo;
     const double nan = __builtin_nan("");

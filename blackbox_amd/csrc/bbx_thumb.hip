@@ -73,26 +73,6 @@ extern "C" int bbx_thumbnails(bbx_ctx* ctx, int ny, int nx, const float* const* 
 // display planes: flipud, zscale limits (float64), scale_data (float32, three separately rounded operations)
 // ---------------------------------------------------------------------------------------------------------------------
 
-// sums of N doubles over the workgroup, the same value in every thread; wave sums by DPP, the four wave totals through LDS and
-// added in a fixed order.  red[2][3][4] is used alternately, so one barrier per call is enough.
-template <int N>
-__device__ __forceinline__ void thumb_block_sum(double (&v)[N], double* red, int& ph) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; k++) v[k] = wave_sum_f64(v[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; k++) red[(ph * 3 + k) * 4 + wave] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        const double* r = red + (ph * 3 + k) * 4;
-        v[k] = (r[0] + r[1]) + (r[2] + r[3]);
-    }
-    ph ^= 1;
-}
-
 __device__ __forceinline__ void thumb_cswap(float& a, float& b, bool up) {
     const float lo = fminf(a, b), hi = fmaxf(a, b);                  // (the samples are finite or +inf: no NaN here)
     a = up ? lo : hi;
@@ -104,7 +84,7 @@ __global__ __launch_bounds__(THUMB_BLOCK) void k_thumb_png8(int size, const floa
     extern __shared__ __attribute__((aligned(16))) float s_px[];                                 // [size * size]: the flipped stamp
     __shared__ __attribute__((aligned(16))) float s_samp[THUMB_SORT];
     __shared__ uint8_t s_bad[THUMB_SORT];
-    __shared__ double s_red[2 * 3 * 4];
+    __shared__ double s_red[2 * 3 * 4];                              // wg_sum_tree's, up to three sums at once
     __shared__ int s_cnt[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int npx = size * size;
@@ -201,13 +181,13 @@ __global__ __launch_bounds__(THUMB_BLOCK) void k_thumb_png8(int size, const floa
 #pragma unroll
             for (int j = 0; j < 4; j++)
                 if (ok[j] && !bad[j]) { a[0] += 1.0; a[1] += (double)(tid + j * THUMB_BLOCK); a[2] += y[j]; }
-            thumb_block_sum<3>(a, s_red, ph);
+            wg_sum_tree<THUMB_BLOCK / 64>(a, s_red, ph);
             const double nw = a[0], xm = a[1] / nw, ym = a[2] / nw;
             double b[2] = {0.0, 0.0};
 #pragma unroll
             for (int j = 0; j < 4; j++)
                 if (ok[j] && !bad[j]) { const double dx = (double)(tid + j * THUMB_BLOCK) - xm; b[0] += dx * dx; b[1] += dx * (y[j] - ym); }
-            thumb_block_sum<2>(b, s_red, ph);
+            wg_sum_tree<THUMB_BLOCK / 64>(b, s_red, ph);
             slope = b[1] / b[0];
             const double icpt = ym - slope * xm;
             double flat[4], c[1] = {0.0};
@@ -216,13 +196,13 @@ __global__ __launch_bounds__(THUMB_BLOCK) void k_thumb_png8(int size, const floa
                 flat[j] = y[j] - (slope * (double)(tid + j * THUMB_BLOCK) + icpt);
                 if (ok[j] && !bad[j]) c[0] += flat[j];
             }
-            thumb_block_sum<1>(c, s_red, ph);
+            wg_sum_tree<THUMB_BLOCK / 64>(c, s_red, ph);
             const double mf = c[0] / nw;
             double d[1] = {0.0};
 #pragma unroll
             for (int j = 0; j < 4; j++)
                 if (ok[j] && !bad[j]) { const double e = flat[j] - mf; d[0] += e * e; }
-            thumb_block_sum<1>(d, s_red, ph);
+            wg_sum_tree<THUMB_BLOCK / 64>(d, s_red, ph);
             const double thr = 2.5 * sqrt(d[0] / nw);                // krej * flat[~badpix].std()
 #pragma unroll
             for (int j = 0; j < 4; j++)
@@ -240,7 +220,7 @@ __global__ __launch_bounds__(THUMB_BLOCK) void k_thumb_png8(int size, const floa
                 }
                 bad[j] = bb;
             }
-            thumb_block_sum<1>(g, s_red, ph);                        // (its barrier also ends the reads of s_bad)
+            wg_sum_tree<THUMB_BLOCK / 64>(g, s_red, ph);             // (its barrier also ends the reads of s_bad)
             last = ngood;
             ngood = (int)g[0];
         }

@@ -25,21 +25,6 @@
 
 struct tf_scal { float sn, sr, fn, fr, dx, dy; };
 
-// NQ sums at once: wave sums by DPP, wave totals through LDS, added in wave order; the result in every thread
-template <int NQ>
-__device__ __forceinline__ void tf_block_sums(double (&v)[NQ], double (*red)[TF_NSUM]) {
-#pragma unroll
-    for (int q = 0; q < NQ; q++) v[q] = wave_sum_f64(v[q]);
-    __syncthreads();                                                 // (red may still be read from the call before)
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < NQ; q++) red[threadIdx.x >> 6][q] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NQ; q++) v[q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
-}
-
 __device__ __forceinline__ bool tf_pos(float v) { return finite_f32(v) && v > 0.f; }
 __device__ __forceinline__ bool tf_fin(double v) { return fabs(v) <= 1.0e300; }                                   // (false for NaN)
 
@@ -137,8 +122,8 @@ __global__ __launch_bounds__(TF_BLOCK) void k_pd_rows(const double2* __restrict_
             raw[((size_t)sub * S + sy) * S + sx] = p;
         }
     }
-    tot = psb_block_sum<TF_BLOCK / 64>(tot, s_red);
-    in = psb_block_sum<TF_BLOCK / 64>(in, s_red);
+    tot = wg_sum_seq<TF_BLOCK / 64>(tot, s_red);
+    in = wg_sum_seq<TF_BLOCK / 64>(in, s_red);
     if (tid == 0) {
         rowsum[((size_t)sub * M + y) * 2] = tot;
         rowsum[((size_t)sub * M + y) * 2 + 1] = in;
@@ -161,7 +146,7 @@ __global__ __launch_bounds__(TF_BLOCK) void k_pd_finish(const float* __restrict_
         v[4] += rowsum[((size_t)sub * M + y) * 2 + 1];
     }
 #pragma unroll
-    for (int q = 0; q < 5; q++) v[q] = psb_block_sum<TF_BLOCK / 64>(v[q], s_red);
+    for (int q = 0; q < 5; q++) v[q] = wg_sum_seq<TF_BLOCK / 64>(v[q], s_red);
     const tf_scal z = sc[sub];
     const bool live = tf_pos(z.sn) && tf_pos(z.sr) && tf_pos(z.fn) && tf_pos(z.fr) && v[1] > 0.0 && tf_fin(v[1]) && v[2] > 0.0 && tf_fin(v[2]) &&
                       v[0] > 0.0 && tf_fin(v[0]) && v[3] > 0.0 && tf_fin(v[3]);
@@ -252,7 +237,7 @@ __global__ __launch_bounds__(TF_BLOCK) void k_trans_psffit(tf_args a, bbx_spl sp
     __shared__ float s_a[TF_SMAX * TF_SMAX];                         // 9.6 KB each: the stamp, and the row pass's output
     __shared__ float s_b[TF_SMAX * TF_SMAX];
     __shared__ float s_d[TF_WMAX * TF_WMAX], s_v[TF_WMAX * TF_WMAX]; // 6.1 KB each: D and V_D of the window (V_D = 0: pixel not used)
-    __shared__ double s_red[TF_BLOCK / 64][TF_NSUM];
+    __shared__ double s_red[TF_BLOCK / 64 * TF_NSUM];
     __shared__ double s_red1[TF_BLOCK / 64];
     const int tid = threadIdx.x, c = blockIdx.x;
     const int S = a.S, npx = S * S, h = S / 2, W = a.W, nw = W * W, hw = W / 2;
@@ -267,7 +252,7 @@ __global__ __launch_bounds__(TF_BLOCK) void k_trans_psffit(tf_args a, bbx_spl sp
     double cnt[1];
     cnt[0] = tf_window<MINI>(a.w, spn, spr, z, py, px, nofit, W, tid, TF_BLOCK, s_d, s_v, hit);
     if (__syncthreads_or(hit)) fl |= 2u;
-    tf_block_sums<1>(cnt, s_red);
+    wg_sum_seq<TF_BLOCK / 64>(cnt, s_red);
     const int n_used = (int)cnt[0];
     if (n_used < 4) nofit = true;
 
@@ -302,7 +287,7 @@ __global__ __launch_bounds__(TF_BLOCK) void k_trans_psffit(tf_args a, bbx_spl sp
             q[3] += ux * ux / v; q[4] += ux * uy / v; q[5] += uy * uy / v;
             q[6] += p * d / v; q[7] += ux * d / v; q[8] += uy * d / v;
         }
-        tf_block_sums<TF_NSUM>(q, s_red);
+        wg_sum_seq<TF_BLOCK / 64>(q, s_red);
         const double m00 = q[0], m01 = q[1], m02 = q[2], m11 = q[3], m12 = q[4], m22 = q[5], r0 = q[6], r1 = q[7], r2 = q[8];
         const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
         const double det = (m00 * c00 + m01 * c01) + m02 * c02;
@@ -333,7 +318,7 @@ __global__ __launch_bounds__(TF_BLOCK) void k_trans_psffit(tf_args a, bbx_spl sp
                 const double v = (double)vf, p = (double)s_a[i] / norm;
                 q[0] += p * (double)s_d[k] / v; q[1] += p * p / v;
             }
-            tf_block_sums<2>(q, s_red);
+            wg_sum_seq<TF_BLOCK / 64>(q, s_red);
             if (!(q[1] > 0.0) || !tf_fin(q[1]) || !tf_fin(q[0])) nofit = true;
             else {
                 F = q[0] / q[1]; err = 1.0 / sqrt(q[1]);
@@ -345,7 +330,7 @@ __global__ __launch_bounds__(TF_BLOCK) void k_trans_psffit(tf_args a, bbx_spl sp
                     const double e = (double)s_d[k] - F * ((double)s_a[i] / norm);
                     r[0] += e * e / (double)vf;
                 }
-                tf_block_sums<1>(r, s_red);
+                wg_sum_seq<TF_BLOCK / 64>(r, s_red);
                 chi2 = r[0] / (double)(n_used - 3);
             }
         }
