@@ -8,7 +8,7 @@ FITS in -> `{tel}_{yyyymmdd}_{hhmmss}_red.fits` (float32, e-), `..._mask.fits` (
 `..._red_hdr.fits`, `..._red.log`; with --cat_extract / --trans_extract the products of
 zogy.optimal_subtraction that the hot path covers (set_blackbox.py:157-164): `_red_bkg_mini`,
 `_red_bkg_std_mini`, `_red_cat` (+ `_red_cat_hdr`), `_red_D`, `_red_Scorr`, `_red_Fpsf`,
-`_red_trans` (+ `_red_trans_hdr`), and with --objmask True `_red_objmask`.  The reference image, its mask and the PSFs are explicit
+`_red_trans` (+ `_red_trans_hdr`), with --objmask True `_red_objmask`, with --limmag True `_red_limmag`.  The reference image, its mask and the PSFs are explicit
 inputs (--ref, --ref_mask, --psf_new, --psf_ref), like the masters (--mflat, --mbias, --bpm):
 their selection / creation (reference building, PSFEx, astrometry) is orchestration.
 `--master_date D --red_dir R --master_dir M` makes the masters of the evening date D (or of a file
@@ -340,7 +340,8 @@ class Reducer:
                 log.exception('exception was raised while reading the non-linearity splines %s', args.nonlin)
         # inputs of the subtraction stage
         self.sub = None
-        if args.cat_extract or args.trans_extract:
+        from blackbox_amd import settings as _S
+        if args.cat_extract or args.trans_extract or (_S.get_par(_S.limmag, tel) if args.limmag is None else args.limmag):
             self.sub = self._load_subtraction_inputs(load)
         _mark('calibration_and_reference_files_in_hbm')
 
@@ -421,6 +422,15 @@ class Reducer:
                 sub['apphot_radii'] = a.apphot_radii
             if a.apphot_local_sky is not None:
                 sub['apphot_local_sky'] = a.apphot_local_sky
+        if par(a.limmag, 'limmag'):
+            # the limiting-flux image of the reduced frame and the LIM* keys; the keywords are only passed when switched on
+            sub['limmag'] = True
+            from blackbox_amd import limflux
+            limflux.check_parameters(a.limmag_nsigma, a.limmag_psf_frac)      # (a ValueError here, not a frame without its image later)
+            if a.limmag_nsigma is not None:
+                sub['limmag_nsigma'] = a.limmag_nsigma
+            if a.limmag_psf_frac is not None:
+                sub['limmag_psf_frac'] = a.limmag_psf_frac
         if par(a.objmask, 'objmask'):
             # object mask + second background pass, whenever the subtraction stage runs; the keywords are only passed when switched on
             sub['objmask'] = True
@@ -691,6 +701,7 @@ class Reducer:
             return
         hnew, htrans = res['header_new'], res['header_trans']
         header.update(hnew)
+        self.write_red_limmag(base, res, header, products)
         bkg_hdr = {'BKG-SIZE': hnew['BKG-SIZE']}
         products.small('image', base + '_bkg_mini.fits', np.asarray(res['bkg_mini_new']), bkg_hdr)
         products.small('image', base + '_bkg_std_mini.fits', np.asarray(res['bkg_std_mini_new']), bkg_hdr)
@@ -735,32 +746,60 @@ class Reducer:
         T-NSIGMA x Fpsferr -- in magnitudes when a zeropoint is known (--zeropoint, or PC-ZP of the header, with the
         extinction term PC-EXTCO x AIRMASSC when both are there: the photometric calibration itself is outside this
         path), else as a flux in e- (LIMUNIT says which)"""
-        R, torch = self.R, self.torch
         if res.get('Fpsferr') is None:
             return
         nsig = float(_hval(header, 'T-NSIGMA', 6.0))
-        lim = zp = None
+        lim = None
         if not products.stages(base + '_trans_limmag.fits'):
             # (else the output stage has queued the flux limit already: only its header is made here, no image)
             lim = res['Fpsferr'] * nsig
-            zp = self.args.zeropoint
-            if zp is None and 'PC-ZP' in header and not isinstance(R.hval(header, 'PC-ZP'), str):
-                zp = float(R.hval(header, 'PC-ZP'))
+        lim, h = self._limit_product(lim, header)
+        h['LIMNSIG'] = (nsig, '[sigma] significance of the limit')
+        products.image(base + '_trans_limmag.fits', lim.contiguous() if lim is not None else None, h)
+
+    def _zeropoint(self, header):
+        """-> (zp, ext): the zeropoint of the frame (--zeropoint, else a numeric PC-ZP of the header; None: none is known) and the
+        extinction term PC-EXTCO x AIRMASSC (0 unless both are there)"""
+        R = self.R
+        zp = self.args.zeropoint
+        if zp is None and 'PC-ZP' in header and not isinstance(R.hval(header, 'PC-ZP'), str):
+            zp = float(R.hval(header, 'PC-ZP'))
+        ext = 0.0
+        if zp is not None and 'PC-EXTCO' in header and 'AIRMASSC' in header:
+            try:
+                ext = float(R.hval(header, 'PC-EXTCO')) * float(R.hval(header, 'AIRMASSC'))
+            except (TypeError, ValueError):
+                ext = 0.0
+        return zp, ext
+
+    def _limit_product(self, lim, header):
+        """the one unit rule of `_trans_limmag` and `_red_limmag`: lim, a flux limit in e- (None: the output stage has queued it, as
+        a flux: _limmag_is_flux) -> (the image to write, a copy of the header with LIMUNIT): magnitudes when a zeropoint is known"""
+        from blackbox_amd.limflux import limit_magnitudes
         h = dict(header)
+        zp, ext = self._zeropoint(header) if lim is not None else (None, 0.0)
         if zp is not None:
-            exptime = float(exptime_of(header))
-            ext = 0.0
-            if 'PC-EXTCO' in header and 'AIRMASSC' in header:
-                try:
-                    ext = float(R.hval(header, 'PC-EXTCO')) * float(R.hval(header, 'AIRMASSC'))
-                except (TypeError, ValueError):
-                    ext = 0.0
-            lim = torch.where(lim > 0, zp - 2.5 * torch.log10(lim.clamp(min=1e-30) / exptime) - ext, torch.zeros_like(lim))
+            lim = limit_magnitudes(lim, zp, float(exptime_of(header)), ext)
             h['LIMUNIT'] = ('mag', 'unit of the limiting-magnitude image')
         else:
             h['LIMUNIT'] = ('e-', 'limit in flux: no zeropoint was given')
-        h['LIMNSIG'] = (nsig, '[sigma] significance of the limit')
-        products.image(base + '_trans_limmag.fits', lim.contiguous() if lim is not None else None, h)
+        return lim, h
+
+    def write_red_limmag(self, base, res, header, products):
+        """`_red_limmag.fits` (set_blackbox.py:157-159): the detection limit of the reduced frame per pixel (res['limflux'],
+        bbx_limflux_image) in the unit of `_trans_limmag`, and the frame keys LIMEFLUX, LIMMAG, LIMFNU in [header]"""
+        from blackbox_amd.limflux import limflux_header
+        info = res.get('limflux_info')
+        if info is None:
+            return
+        zp, ext = self._zeropoint(header)
+        header.update(limflux_header(res.get('limflux') is not None, info.get('stat'), info.get('win'), info.get('nsigma'), info.get('frac'),
+                                     exptime=float(exptime_of(header)), zp=zp, ext=ext))
+        if res.get('limflux') is None or not self.R.hval(header, 'LIMMAG-P'):
+            return
+        lim = None if products.stages(base + '_limmag.fits') else res['limflux']
+        lim, h = self._limit_product(lim, header)
+        products.image(base + '_limmag.fits', lim.contiguous() if lim is not None else None, h)
 
     # ---- many object frames: frames-in-flight pipeline ------------------------------------------
     def reduce_list(self, files):
@@ -894,6 +933,8 @@ class _ListRun:
         if r.args.fpack:
             # (output slots: the images of two frames per lane, one more image per frame with the object mask)
             nslots = 14 if r.sub is not None and r.sub.get('objmask') else 12
+            if r.sub is not None and r.sub.get('limmag'):
+                nslots += 2                                      # (and one with the limiting-flux image)
             self.stage = outstage.OutputStage(r.ctx.device, 2 * geom.ysize_chan, 8 * geom.xsize_chan, nwriters=nwriters, nslots=nslots)
             kw = dict(outstage=self.stage, out_base=self.out_base, on_written=self.on_written,
                       header_hook=self.header_hook, stage_limmag=r._limmag_is_flux)
@@ -1161,6 +1202,15 @@ def build_parser():
                     help='[FWHM] aperture radii of --cat_apphot, a comma list of at most 8 (default: settings.apphot_radii)')
     ap.add_argument('--apphot_local_sky', type=str2bool, default=None,
                     help='subtract the sky annulus\' clipped median from the aperture fluxes (default: settings.apphot_local_sky)')
+    ap.add_argument('--limmag', type=str2bool, default=None,
+                    help='the limiting-flux image of the reduced frame from its sky noise, mask and PSF (--psf_new or --psf_build): '
+                         '_red_limmag.fits (magnitudes with --zeropoint or PC-ZP, else e-), LIMMAG-P LIMNSIG LIMEFLUX LIMMAG LIMFNU LIMPFRAC '
+                         'LIMWIN LIMNPIX in the header (default: settings.limmag)')
+    ap.add_argument('--limmag_nsigma', type=float, default=None,
+                    help='[sigma] significance of --limmag\'s limit (default: settings.limmag_nsigma)')
+    ap.add_argument('--limmag_psf_frac', type=float, default=None,
+                    help='share of the sum of PSF^2 that --limmag\'s window may leave out, in [0, 1); 0: the whole stamp (default: '
+                         'settings.limmag_psf_frac)')
     ap.add_argument('--trans_psffit', type=str2bool, default=None,
                     help='fit the PSF of D to D at every transient candidate: X_PSF_D Y_PSF_D E_FLUX_PSF_D E_FLUXERR_PSF_D CHI2_PSF_D '
                          'FLAGS_PSF_D in `_trans.fits`, T-PSFD T-FITSZ T-NFIT T-PDFOLD T-CHI2MD in its header (default: '

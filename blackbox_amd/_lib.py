@@ -150,6 +150,7 @@ SIGNATURES = {
     'bbx_psf_chi2': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'bbx_psf_optflux_shift': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'bbx_aper_phot': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _pf, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'bbx_limflux_image': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _f, C.c_double, _vp, _vp, _vp]),
     'bbx_zogy_pd_stamps': (_i, [_vp, _i, _i, _i, _vp, _vp, _pf, _vp, _vp, _vp]),
     'bbx_trans_psffit': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _pf, _i, _vp, _vp, _i, _i, _f,
                               _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -139,6 +139,7 @@ enum {
     WS_CAND, WS_FLAGS, WS_STAGE2, WS_CRLIST, WS_HIST, WS_SEL, WS_MISC, WS_STRIP, WS_HVALS, WS_CRORIG, WS_CANNY, WS_ZCAND, WS_BCAND, WS_FPHINT, WS_BOXFAIL, WS_ZSPL,
     WS_TRANSFIT,
     WS_TRANSSHAPE,       // bbx_trans_shapefit's scalars: a slot of its own, so that the call may be queued beside bbx_trans_psffit's
+    WS_LIMFLUX,          // bbx_limflux_image: the windows T_t and the windowed, squared stamps of every tile
     WS_MAX
 };
 static_assert(WS_MAX <= BBX_WS_SLOTS, "bbx_ctx::d_ws holds BBX_WS_SLOTS slots");

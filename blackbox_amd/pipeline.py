@@ -755,6 +755,10 @@ class FramePipeline:
         sub = f.sub
         if sub is not None and sub.get('objmask') is not None:
             names['objmask'] = st.submit(ctx, g, sub['objmask'], base + '_objmask.fits')
+        if sub is not None and sub.get('limflux') is not None and sub['header_new']['LIMMAG-P'][0]:
+            # `_red_limmag` as a flux limit; with a zeropoint the caller makes the image in magnitudes, as for `_trans_limmag`
+            if self.stage_limmag(f.header) if callable(self.stage_limmag) else self.stage_limmag:
+                names['red_limmag'] = st.submit(ctx, g, sub['limflux'], base + '_limmag.fits')
         if sub is not None and sub.get('D') is not None:
             for ext in ('D', 'Scorr', 'Fpsf'):
                 names[ext] = st.submit(ctx, g, sub[ext], '{}_{}.fits'.format(base, ext))

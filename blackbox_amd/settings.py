@@ -146,6 +146,14 @@ apphot_sky_inout = (5.0, 7.0)  # [FWHM] inner and outer radius of the sky annulu
 apphot_local_sky = True        # subtract the annulus' clipped median from the aperture fluxes
 apphot_sky_nmin = 20           # fewer annulus pixels than this after clipping: no local sky (FLAGS_APER 8), nothing subtracted
 
+# ---- limiting-flux image of the reduced frame (`_red_limmag.fits`, set_blackbox.py:157-159; LIMEFLUX, LIMFNU, LIMMAG:
+# blackbox.py:3151-3153; bbx_limflux_image; [EXT] zogy.get_psfoptflux(get_limflux_array=True): the rules of
+# include/bbx.h here, this project's own) ----
+# Off by default: no kernel of bbx_limflux.hip is launched, no LIM* key is added, no file is written.
+limmag = False                 # _red_limmag.fits; LIMMAG-P LIMNSIG LIMEFLUX LIMMAG LIMFNU LIMPFRAC LIMWIN LIMNPIX
+limmag_nsigma = 5.0            # [sigma] significance of the limit (finding_chart.py:232)
+limmag_psf_frac = 1e-4         # share of sum PSF^2 the window may leave out (0: the whole stamp)
+
 # ---- PSF model from the frame's own stars (`_psf.fits`, header keys PSF-*: blackbox.py:3085-3110, set_qc.py:293-296;
 # [EXT] PSFEx in zogy: the rules of include/bbx.h here; this project's own unless a PSFEx parameter is named) ----
 # Off by default: a frame without --psf_new is processed without a PSF as before.

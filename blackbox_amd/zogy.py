@@ -42,6 +42,7 @@ from .psfbuild import (BBX_ERR_NOTCONV, PSF_REASONS, _PSF_HDR, build_psf, psf_ch
                        psf_ncoef, psf_select, psf_stamps)
 from .aperphot import (APER_FEW_SKY, APER_MASKED, APER_NO_CENTROID, APER_OFF_FRAME, APER_SKY_CUT, APER_TOO_BIG, _radii as _aper_radii,         # noqa: F401
                        aper_column_names, aper_columns, aper_fwhm, aper_header, aper_phot)
+from .limflux import check_parameters as _limflux_parameters, limflux_header, limflux_image, limit_magnitudes         # noqa: F401
 from .align import (ALIGN_CLIP, ALIGN_DET, ALIGN_FAR, ALIGN_FEW_PAIRS, ALIGN_NMIN, ALIGN_NOT_PD, ALIGN_PAIR_CAP,         # noqa: F401
                     ALIGN_VOTE_FAILED, RefStars, _expect_list, align_apply, align_fit, align_grid, align_grid_host, align_grid_shape,
                     align_header, align_reference, align_sort, align_vote, remap_mask)
@@ -51,6 +52,7 @@ BBX_OPT_ZOGY_KWIN_OFF = 4
 _trans_psffit = trans_psffit                                         # (_optimal_subtraction's switch bears the name)
 _trans_shapefit = trans_shapefit                                     # (_optimal_subtraction's switch bears the name)
 _aper_phot = aper_phot                                               # (_optimal_subtraction's switch bears the name)
+_limflux_image = limflux_image                                       # (the stage calls it by this name)
 
 
 def optimal_subtraction(ctx, *args, **kw):
@@ -76,7 +78,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          trans_shapefit=False, trans_shape_size=None, trans_fwhm_gauss_min=None, trans_fwhm_gauss_max=None,
                          trans_elong_gauss_max=None, ref_align=False, align_poldeg=None, align_max_shift=None, align_bin=None,
                          align_nbright=None, align_rounds=None, ref_stars=None, aper_phot=False, apphot_radii=None, apphot_sky_inout=None,
-                         apphot_local_sky=None):
+                         apphot_local_sky=None, limmag=False, limmag_nsigma=None, limmag_psf_frac=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -180,6 +182,16 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       AP-SKYIN, AP-SKYOU, AP-LSKY, AP-NSTAR, AP-OPT1..n (aper_header).  An exception in the stage: today's catalogue,
                       AP-P False.  False: no kernel of bbx_aper.hip is launched, no such keys or columns.  apphot_radii,
                       apphot_sky_inout, apphot_local_sky: settings
+      limmag        : True (with psf_new, or a model that psf_build made): the limiting flux of the frame at every pixel, limmag_nsigma x
+                      the error of the PSF-weighted optimal flux of a faint source centred there on sky noise alone (bbx_limflux_image,
+                      DESIGN.md 4n), from the second-pass sigma map, new_mask and the tiles' PSF stamps over the window that holds
+                      1 - limmag_psf_frac of sum PSF^2; queued behind the catalogue photometry, its clipped frame statistic (3 sigma,
+                      5 rounds, zeros skipped) and the tiles' windows ride the same copy back: res['limflux'] = the device image,
+                      res['limflux_info'] = dict(stat, win, nsigma, frac), header_new gets LIMMAG-P, LIMNSIG, LIMEFLUX, LIMMAG,
+                      LIMFNU, LIMPFRAC, LIMWIN, LIMNPIX (limflux_header; exposure time and zeropoint are the caller's: LIMEFLUX, LIMMAG
+                      and LIMFNU are 'None' here).  Without a PSF, or on an exception in the stage: the frame goes on, LIMMAG-P
+                      False, the other keys 'None', no res['limflux'].  False: no kernel of bbx_limflux.hip is launched, no such keys.
+                      A limmag_nsigma that is not positive or a limmag_psf_frac outside [0, 1): ValueError before anything is queued
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
             header (= header_new additions), header_trans)"""
     size = subimage_size or settings.subimage_size
@@ -198,6 +210,9 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     phot_centroid = bool(phot_centroid)
     do_aper = bool(aper_phot) and bool(cat_extract) and have_psf
     do_align = bool(ref_align) and have_ref
+    do_lim = bool(limmag)
+    if do_lim:
+        lim_nsigma, lim_frac = _limflux_parameters(limmag_nsigma, limmag_psf_frac)
     if do_align and ref_grid is not None:
         raise ValueError('ref_align=True makes the lattice itself: a ref_grid beside it is refused')
     ref_mask_remapped = ref_grid_host = None                        # set by a registration that succeeded
@@ -377,6 +392,24 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         have_ref = do_match = False
         return False
 
+    def limflux_enqueue():
+        """the limiting-flux image and its frame statistic, queued on the frame's stream -> [statistic [8] float64, windows [nsub]
+        int32] on the device; None (and a warning) where the stage fails"""
+        try:
+            lim, win = _limflux_image(ctx, bstd, new_mask, sub_pn.contiguous(), size, nsy, nsx, nsigma=lim_nsigma, frac=lim_frac)
+            d_lst = frame_clipped_stats_enqueue(ctx, lim, new_mask)
+            res['limflux'] = lim
+            return [d_lst, win]
+        except Exception as ex:                                      # the frame goes on without the image
+            logging.getLogger(__name__).warning('limiting-flux image of the reduced frame failed: %s', ex)
+            res.pop('limflux', None)
+            return None
+
+    def limflux_finish(got):
+        """got: the host copies of limflux_enqueue's pair, or None"""
+        res['limflux_info'] = dict(stat=got[0] if got else None, win=got[1] if got else None, nsigma=lim_nsigma, frac=lim_frac)
+        hdr.update(limflux_header(got is not None, *(got or (None, None)), nsigma=lim_nsigma, frac=lim_frac))
+
     ref_side = None
     # ---- full-source catalogue (a17): peaks of the background-subtracted frame above
     # cat_nsigma x S-BKGSTD, PSF-weighted optimal flux at each (zogy.get_psfoptflux)
@@ -470,7 +503,12 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                 back += [peaks_off[2], d_pfl]
             if d_aper is not None:
                 back += list(d_aper) + [d_afw]
+            d_lim = limflux_enqueue() if do_lim else None            # behind the photometry, in the same copy back
+            if d_lim is not None:
+                back += d_lim
             got = fetch(ctx, *back)
+            if do_lim:
+                limflux_finish([got.pop() for _ in range(2)][::-1] if d_lim is not None else None)     # (the last two: statistic, windows)
             aper = [got.pop() for _ in range(5)][::-1] if d_aper is not None else None      # (the last five: flux, err, sky, flags, FWHM)
             mk, f, e = got[:3]
             if do_match:
@@ -525,6 +563,10 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             res['aper'] = dict(fwhm=aper[4], radii=_aper_radii(apphot_radii), n_good=hdr['AP-NSTAR'][0])
         elif do_aper:
             hdr.update(aper_header(False))
+    if do_lim and 'limflux_info' not in res:
+        # no photometry was read back (no catalogue asked for, no PSF, or nothing above the threshold): a copy back of its own
+        d_lim = limflux_enqueue() if sub_pn is not None else None
+        limflux_finish(fetch(ctx, *d_lim) if d_lim is not None else None)
     if 'S-BKG' not in hdr:
         scal_n = host_side_meanwhile()
     if do_align and have_ref and 'align' not in res:

@@ -966,6 +966,38 @@ int bbx_aper_phot(bbx_ctx *ctx, int ny, int nx, const float *d_D, const float *d
                   const float *radii, float sky_in, float sky_out, int sub_sky, int sky_nmin, float *d_flux, float *d_err,
                   float *d_sky, uint8_t *d_flags, void *stream);
 
+/* ---- limiting-flux image of the reduced frame (bbx_limflux.hip): `_red_limmag.fits` and the keys LIMEFLUX, LIMFNU,
+ * LIMMAG of blackbox.py:3151-3153.  The quantity is what bbx_psf_optflux* return as err, taken at every pixel: the error of the
+ * PSF-weighted optimal flux of a faint source centred there, on sky noise alone, times nsigma.  zogy.get_psfoptflux(
+ * get_limflux_array=True) is [EXT], not in the reference tree: only the file name, the key names and the 5 sigma convention follow
+ * the reference, the rules below are THIS PROJECT'S OWN and parity with zogy's numbers is unpinned.
+ *  1 the tile of the output pixel (y, x): t = min(max(y / size, 0), nsy - 1) * nsx + the same of x (zogy.tile_index's clamp: a frame
+ *    that is no multiple of size gives the rest to the last tile).  d_planes[nsy * nsx][S][S]: unit-sum stamps, S odd, <= 49, the
+ *    centre at S / 2.
+ *  2 Q_t[j][i] = (P_t[j][i] / norm_t)^2 in float64, norm_t = the float64 sum of the plane; Q rounded to float32 once.  A norm_t
+ *    that is not positive and finite: every pixel of the tile is 0, d_win[t] = 0.
+ *  3 the window T_t: the smallest odd T <= S for which the float64 sum of Q over the central T x T pixels is at least (1 - frac)
+ *    times the float64 sum over all S x S (both sums ring by ring, outwards, each ring row-major; O(S^2) per tile); frac == 0:
+ *    T_t = S.  frac in [0, 1), anything else BBX_ERR_ARG.  d_win[t] = T_t (d_win may be NULL).  Q is NOT renormalised to the
+ *    window: on a uniform background the limit is high by at most frac / 2 (relative).  The window is made on the device by a small
+ *    kernel of the same call, no host wait.
+ *  4 W(iy, ix) = min(1.0f / (sigma * sigma), the largest finite float32) in float32 (a sigma below 5e-20, whose square underflows,
+ *    gives that largest number, not inf: every W is finite), sigma from the frame d_sigma[ny][nx] or read off the mini image sigma_mini at
+ *    the pixel (bbx_psf_optflux_shift's reader: within 3e-7 of the frame's value) -- exactly one of the two, else BBX_ERR_ARG.
+ *    W = 0 off the frame, where d_mask != 0 (d_mask may be NULL), and where sigma is not finite or not positive.  Sky noise only:
+ *    no max(D, 0) term, this is the limit for a faint source.
+ *  5 den(y, x) = sum over j, i in [-k, k], k = T_t / 2, h = S / 2, of Q_t[h + j][h + i] W(y + j, x + i): float32 fma chain, i
+ *    outermost, then j, both ascending.  No atomics: same input -> same bits.
+ *  6 d_lim[y][x] = nsigma / sqrt(den) as float32, 0 where den is not positive.  The pixel's own mask value plays no part beyond 4:
+ *    a masked pixel gets the limit of a source centred on it.
+ *  7 ny * nx == 0: nothing is launched.
+ * Two kernels: the windows (one workgroup per tile), then blocks of 64 x 32 output pixels laid out per tile, W of block + halo in
+ * LDS, Q read as a wave-uniform operand, eight outputs per lane.  2 T^2 ny nx FLOP.                                             */
+#define BBX_LIMFLUX_SMAX 49     /* largest stamp side */
+int bbx_limflux_image(bbx_ctx *ctx, int ny, int nx, const float *d_sigma, const bbx_spline_image *sigma_mini,
+                      const uint8_t *d_mask, int S, const float *d_planes, int size, int nsy, int nsx,
+                      float nsigma, double frac, float *d_lim, int32_t *d_win, void *stream);
+
 /* ---- transient vetting: the PSF of D per sub-image and its fit to D per candidate (bbx_transfit.hip).  zogy fits
  * the PSF of the difference image to D at every candidate with free position (E_FLUX_PSF_D, X_PSF_D, Y_PSF_D, CHI2_PSF_D) ([EXT]:
  * zogy is not in the reference tree; the rules below are THIS PROJECT'S OWN, parity is unpinned).
