@@ -458,6 +458,15 @@ class Reducer:
                 chi2_max = par(a.trans_chi2_max, 'trans_chi2_max')
                 if chi2_max is not None:
                     sub['trans_chi2_max'] = chi2_max
+            # fake stars planted in the frame that is subtracted and read back from Scorr / Fpsf; the keywords are only passed when switched on
+            nfake = par(a.fake_stars, 'nfakestars')
+            if nfake and int(nfake) > 0:
+                from blackbox_amd import fakestars
+                sub['fake_stars'] = int(nfake)
+                sub['fake_s2n'] = fakestars.fake_s2n_list(par(a.fake_s2n, 'fakestar_s2n'))       # (a ValueError here, not a frame without its stars later)
+                for k in ('fake_seed', 'fake_noise', 'fake_radius', 'fake_clear_nsigma'):
+                    if getattr(a, k) is not None:
+                        sub[k] = getattr(a, k)
             # a Gauss and a Moffat fitted to every transient candidate, with or without the fit of P_D; likewise
             if par(a.trans_shapefit, 'trans_shapefit'):
                 sub['trans_shapefit'] = True
@@ -731,7 +740,11 @@ class Reducer:
                 qc.run_qc_check(full_t, self.tel, cat_type='trans', cat_dummy=base + '_trans.fits', check_key_type='trans')
             else:
                 thumbs = self._thumbnail_products(res, base)
-                products.small('trans', res['transients'], base + '_trans.fits', dict(full_t), *([thumbs] if thumbs else []))
+                extra = dict(thumbs or {}, fake_star=True) if res.get('fakestars') is not None else thumbs      # (FAKE_STAR even in an empty table)
+                products.small('trans', res['transients'], base + '_trans.fits', dict(full_t), *([extra] if extra else []))
+                if res.get('fakestars') is not None:
+                    # the injected stars and what came back of them (fake_table), by the route of `_trans.fits`
+                    products.small('fakestars', res['fakestars']['table'], base + '_trans_fakestars.fits', dict(full_t))
             products.small('header', base + '_trans_hdr.fits', dict(full_t))
 
     def _limmag_is_flux(self, header):
@@ -1218,6 +1231,17 @@ def build_parser():
     ap.add_argument('--trans_fit_size', type=int, default=None, help='[pix] side of the window of that fit (default: settings.trans_fit_size)')
     ap.add_argument('--trans_chi2_max', type=float, default=None,
                     help='drop the candidates without a fit or with CHI2_PSF_D above this, T-NVET (default: settings.trans_chi2_max)')
+    ap.add_argument('--fake_stars', type=int, default=None,
+                    help='fake stars per sub-image, added to the background-subtracted new frame before the subtraction and read back from '
+                         'Scorr / Fpsf: _trans_fakestars.fits, FAKE_STAR in `_trans.fits`, T-NFAKE T-FAKESN T-FK* in its header; 0: none '
+                         '(default: settings.nfakestars)')
+    ap.add_argument('--fake_s2n', type=float_list, default=None,
+                    help='asked S/N of the fake stars, a comma list of at most 8 taken in turn (default: settings.fakestar_s2n)')
+    ap.add_argument('--fake_seed', type=int, default=None, help='seed of their positions and noise (default: settings.fakestar_seed)')
+    ap.add_argument('--fake_noise', type=str2bool, default=None, help='add their own Poisson noise (default: settings.fakestar_noise)')
+    ap.add_argument('--fake_radius', type=int, default=None, help='[pix] recovery window about the injected pixel, <= 4 (default: settings.fakestar_radius)')
+    ap.add_argument('--fake_clear_nsigma', type=float, default=None,
+                    help='[sigma] no star where |new| or |ref| exceeds this within 3 pixels (default: settings.fake_clear_nsigma)')
     ap.add_argument('--trans_shapefit', type=str2bool, default=None,
                     help='fit an elliptical Gaussian and an elliptical Moffat to D at every transient candidate: X/Y_GAUSS_D FWHM_GAUSS_D '
                          'ELONG_GAUSS_D CHI2_GAUSS_D FLAGS_GAUSS_D and the same of _MOFFAT_D in `_trans.fits`, T-SHAPE T-SHPSZ T-MBETA T-NGAUS '

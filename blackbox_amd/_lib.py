@@ -164,6 +164,9 @@ SIGNATURES = {
     'bbx_align_apply': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'bbx_align_grid': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'bbx_remap_mask': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'bbx_fake_inject': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _i, C.c_uint64,
+                            _vp, _vp, _vp, _vp, _vp]),
+    'bbx_fake_recover': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError if the export is missing

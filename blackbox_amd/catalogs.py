@@ -59,6 +59,14 @@ TRANSSHAPE_COLUMNS = tuple((n + '_' + m + '_D', np.uint8 if n == 'FLAGS' else np
 # of every radius, whose names carry the radius (aper_columns)
 APER_COLUMNS = (('BKG_APER', np.float32, 'e-'), ('BKGSTD_APER', np.float32, 'e-'), ('NSKY_APER', np.int32, ''), ('FWHM_APER', np.float32, 'pix'),
                 ('FLAGS_APER', np.uint8, ''))
+# fake stars (settings.nfakestars; zogy.optimal_subtraction(fake_stars=N)): the star a candidate row belongs to, 0 for a real candidate;
+# appended to the 'trans' columns of a table that carries it
+FAKE_COLUMNS = (('FAKE_STAR', np.int16, ''),)
+# the table of `_trans_fakestars.fits` (fakestars.fake_table)
+FAKESTAR_TABLE = (('NUMBER', np.int32, ''), ('X_IN', np.float32, 'pix'), ('Y_IN', np.float32, 'pix'), ('SNR_IN', np.float32, ''),
+                  ('SNR_SKY_IN', np.float32, ''), ('E_FLUX_IN', np.float32, 'e-'), ('E_FLUX_REAL', np.float32, 'e-'), ('FLAGS_IN', np.int16, ''),
+                  ('X_PEAK', np.float32, 'pix'), ('Y_PEAK', np.float32, 'pix'), ('SCORR_OUT', np.float32, ''), ('E_FLUX_OUT', np.float32, 'e-'),
+                  ('E_FLUXERR_OUT', np.float32, 'e-'), ('E_FLUX_OUT_AT', np.float32, 'e-'), ('FOUND', np.int16, ''), ('NUMBER_TRANS', np.int32, ''))
 THUMBNAILS = ('RED', 'REF', 'D', 'SCORR')                     # plane order of zogy.thumbnail_stamps; blackbox.py:2701
 THUMBNAIL_COLUMNS = tuple('THUMBNAIL_' + c for c in THUMBNAILS)
 
@@ -110,6 +118,10 @@ def format_cat(table, cat_output, cat_type='new', header2add=None):
         for name, dt, unit in TRANSSHAPE_COLUMNS:
             cols[name] = np.asarray(table[name]).astype(dt)
             units[name] = unit
+    if cat_type == 'trans' and table is not None and FAKE_COLUMNS[0][0] in table:
+        for name, dt, unit in FAKE_COLUMNS:
+            cols[name] = np.asarray(table[name]).astype(dt)
+            units[name] = unit
     if cat_type == 'trans' and table is not None and THUMBNAIL_COLUMNS[0] in table:
         for name in THUMBNAIL_COLUMNS:
             cols[name] = np.asarray(table[name]).astype(np.float32)
@@ -120,12 +132,14 @@ def format_cat(table, cat_output, cat_type='new', header2add=None):
     return cat_output
 
 
-def transient_table(transients, thumbnails=None):
+def transient_table(transients, thumbnails=None, fake_star=False):
     """list of dict(y, x, scorr, fpsf, fpsferr[, flags]) (zogy.optimal_subtraction) -> column dict (FITS
     pixel coordinates, 1-based); thumbnails: float32 [n, 4, S, S] (res['thumbnails'] on the host) -> the four
-    THUMBNAIL_* columns and FLAGS_MASK as well"""
+    THUMBNAIL_* columns and FLAGS_MASK as well; fake_star: the table of a frame with fake stars: FAKE_STAR also where it has no row"""
     t = transients or []
     tab = _transient_columns(t)
+    if fake_star and 'FAKE_STAR' not in tab:
+        tab['FAKE_STAR'] = np.array([d.get('fake_star', 0) for d in t], np.int16)
     if thumbnails is not None:
         th = np.asarray(thumbnails, np.float32)
         if th.ndim != 4 or th.shape[0] != len(t) or th.shape[1] != 4:
@@ -152,7 +166,16 @@ def _transient_columns(t):
         for name, dt, _ in TRANSSHAPE_COLUMNS:
             key = name.lower()
             tab[name] = np.array([d[key] + 1.0 if name[:2] in ('X_', 'Y_') else d[key] for d in t], dt)
+    if t and all('fake_star' in d for d in t):
+        tab['FAKE_STAR'] = np.array([d['fake_star'] for d in t], np.int16)
     return tab
+
+
+def fakestar_cat(table, cat_output, header2add=None):
+    """`_trans_fakestars.fits`: the table of fakestars.fake_table with its fixed column set (FAKESTAR_TABLE)"""
+    cols = {name: np.asarray(table[name]).astype(dt) for name, dt, _ in FAKESTAR_TABLE}
+    fitsio.write_table(cat_output, cols, header2add, units={name: unit for name, _, unit in FAKESTAR_TABLE})
+    return cat_output
 
 
 def _png_gray8(plane):
@@ -201,7 +224,9 @@ def write_small_products(jobs):
     kind in 'image' (fitsio.write_image), 'header' (fitsio.write_header), 'psf' (fitsio.write_psfex: path, model with a host
     basis, header), 'cat' (format_cat), 'trans' (format_cat of
     transient_table(args[0]); an optional fourth argument dict(thumbnails=float32 [n, 4, S, S] or None, png8=uint8 [n, 4, S, S] or
-    None, png_dir=) adds the thumbnail columns and / or writes the PNG files of the rows, NUMBER = 1..n)"""
+    None, png_dir=[, fake_star=True]) adds the thumbnail columns and / or writes the PNG files of the rows, NUMBER = 1..n; fake_star: the
+    FAKE_STAR column even without a row), 'fakestars' (fakestar_cat:
+    table, path, header)"""
     done = []
     for kind, args in jobs:
         if kind == 'image':
@@ -214,10 +239,13 @@ def write_small_products(jobs):
             format_cat(args[0], args[1], cat_type=args[2], header2add=args[3])
         elif kind == 'trans':
             extra = args[3] if len(args) > 3 and args[3] else {}
-            format_cat(transient_table(args[0], extra.get('thumbnails')), args[1], cat_type='trans', header2add=args[2])
+            format_cat(transient_table(args[0], extra.get('thumbnails'), fake_star=bool(extra.get('fake_star'))), args[1], cat_type='trans',
+                       header2add=args[2])
             if extra.get('png8') is not None:
                 save_png_thumbnails(extra['png8'], np.arange(1, len(args[0] or []) + 1), extra['png_dir'])
+        elif kind == 'fakestars':
+            fakestar_cat(args[0], args[1], header2add=args[2])
         else:
             raise ValueError('unknown small product {!r}'.format(kind))
-        done.append(args[1] if kind in ('cat', 'trans') else args[0])
+        done.append(args[1] if kind in ('cat', 'trans', 'fakestars') else args[0])
     return done

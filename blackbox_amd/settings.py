@@ -154,6 +154,18 @@ limmag = False                 # _red_limmag.fits; LIMMAG-P LIMNSIG LIMEFLUX LIM
 limmag_nsigma = 5.0            # [sigma] significance of the limit (finding_chart.py:232)
 limmag_psf_frac = 1e-4         # share of sum PSF^2 the window may leave out (0: the whole stamp)
 
+# ---- fake stars: injection at a set S/N into the background-subtracted new frame, recovery from Scorr / Fpsf and the candidate
+# list (T-NFAKE, T-FAKESN: blackbox.py:3192-3193; bbx_fake_inject, bbx_fake_recover; [EXT] zogy's fake stars: the
+# rules of include/bbx.h here, this project's own) ----
+# Off by default: no kernel of bbx_fake.hip is launched, no T-FK* key or FAKE_STAR column is added, no file is written.
+nfakestars = 0                 # stars per sub-image; _trans_fakestars.fits, FAKE_STAR in _trans.fits, T-NFAKE T-FAKESN T-FK*
+fakestar_s2n = 10.0            # asked S/N, source noise included: one number or up to 8, taken in turn
+fakestar_seed = 0              # of the positions and of the source noise
+fakestar_noise = True          # add the stars' own Poisson noise (a normal deviate of variance F P per pixel)
+fakestar_radius = 2            # [pix] recovery window about the injected pixel (<= 4)
+fake_clear_half = 3            # [pix] half side of the window that must be free of mask bits and sources
+fake_clear_nsigma = 5.0        # [sigma] |new| or |ref| above this in that window: the star is not planted (FLAGS_IN 2)
+
 # ---- PSF model from the frame's own stars (`_psf.fits`, header keys PSF-*: blackbox.py:3085-3110, set_qc.py:293-296;
 # [EXT] PSFEx in zogy: the rules of include/bbx.h here; this project's own unless a PSFEx parameter is named) ----
 # Off by default: a frame without --psf_new is processed without a PSF as before.

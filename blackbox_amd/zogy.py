@@ -46,6 +46,9 @@ from .limflux import check_parameters as _limflux_parameters, limflux_header, li
 from .align import (ALIGN_CLIP, ALIGN_DET, ALIGN_FAR, ALIGN_FEW_PAIRS, ALIGN_NMIN, ALIGN_NOT_PD, ALIGN_PAIR_CAP,         # noqa: F401
                     ALIGN_VOTE_FAILED, RefStars, _expect_list, align_apply, align_fit, align_grid, align_grid_host, align_grid_shape,
                     align_header, align_reference, align_sort, align_vote, remap_mask)
+from .fakestars import (FAKE_COLS, FAKE_MASKED, FAKE_NO_FLUX, FAKE_NO_PSF, FAKE_OFF_FRAME, FAKE_ON_SOURCE, FOUND_KEPT, FOUND_PEAK,         # noqa: F401
+                        FOUND_ROW, check_apart, fake_header, fake_inject, fake_launch, fake_layout, fake_match, fake_prepare, fake_recover,
+                        fake_s2n_list, fake_table)
 
 BBX_ERR_OVERFLOW, BBX_ERR_PSFWIN = -4, -6          # include/bbx.h
 BBX_OPT_ZOGY_KWIN_OFF = 4
@@ -53,6 +56,7 @@ _trans_psffit = trans_psffit                                         # (_optimal
 _trans_shapefit = trans_shapefit                                     # (_optimal_subtraction's switch bears the name)
 _aper_phot = aper_phot                                               # (_optimal_subtraction's switch bears the name)
 _limflux_image = limflux_image                                       # (the stage calls it by this name)
+_fake_launch, _fake_recover = fake_launch, fake_recover              # (the stage calls them by these names)
 
 
 def optimal_subtraction(ctx, *args, **kw):
@@ -78,7 +82,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          trans_shapefit=False, trans_shape_size=None, trans_fwhm_gauss_min=None, trans_fwhm_gauss_max=None,
                          trans_elong_gauss_max=None, ref_align=False, align_poldeg=None, align_max_shift=None, align_bin=None,
                          align_nbright=None, align_rounds=None, ref_stars=None, aper_phot=False, apphot_radii=None, apphot_sky_inout=None,
-                         apphot_local_sky=None, limmag=False, limmag_nsigma=None, limmag_psf_frac=None):
+                         apphot_local_sky=None, limmag=False, limmag_nsigma=None, limmag_psf_frac=None, fake_stars=0, fake_s2n=None,
+                         fake_seed=None, fake_noise=None, fake_radius=None, fake_clear_nsigma=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -192,6 +197,19 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       and LIMFNU are 'None' here).  Without a PSF, or on an exception in the stage: the frame goes on, LIMMAG-P
                       False, the other keys 'None', no res['limflux'].  False: no kernel of bbx_limflux.hip is launched, no such keys.
                       A limmag_nsigma that is not positive or a limmag_psf_frac outside [0, 1): ValueError before anything is queued
+      fake_stars    : N > 0 (with a reference and PSF stamps of the new frame): N stars per sub-image of the S/N values fake_s2n (taken
+                      in turn) are added to the background-subtracted new frame IN PLACE (fake_layout, bbx_fake_inject)
+                      behind the catalogue, the PSF build, the star match and the registration -- none of which sees a fake star --
+                      and immediately before the frame is cut into sub-images; they ride the one subtraction and are read back from
+                      Scorr / Fpsf / Fpsferr (bbx_fake_recover, within fake_radius pixels) in the copy back that follows it.  After
+                      the call res['data_bkgsub'], D, Scorr, Fpsf, Fpsferr and the thumbnails CARRY THE STARS, by design, as in zogy;
+                      `new` is untouched.  res['fakestars'] = dict(table (FAKE_COLS), layout); every row of res['transients'] gains
+                      fake_star (the 1-based star, 0: a real candidate; the rows stay, T-NTRANS counts them); header_trans gets T-FKP,
+                      T-NFAKE, T-FAKESN, T-FKNASK, T-FKNREJ, T-FKSEED, T-FKNOIS, T-FKRAD, T-NFKTR, per asked S/N T-FKSNk T-FKNk T-FKEFk
+                      T-FKVTk, and T-FKFRAT T-FKFSTD T-FKPULL T-FKSCRT (fake_header).  An exception before the kernel is queued
+                      (a layout that does not fit the sub-image, ...): the frame goes on untouched, T-FKP False, T-NFAKE 0.  0: no
+                      kernel of bbx_fake.hip is launched, no such keys.  fake_s2n, fake_seed, fake_noise, fake_radius,
+                      fake_clear_nsigma: settings
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
             header (= header_new additions), header_trans)"""
     size = subimage_size or settings.subimage_size
@@ -579,6 +597,33 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     # ---- reference frame on the new frame's grid: background-subtracted image + sigma image
     rwork, rbstd, sdr, sub_pr, frame_path = ref_side if ref_side is not None else prepare_reference()
 
+    # ---- fake stars: planted in the frame that is about to be cut, behind everything that reads the frame as it was observed
+    fk = None
+    if fake_stars and int(fake_stars) > 0:
+        fk_noise = settings.fakestar_noise if fake_noise is None else bool(fake_noise)
+        fk_radius = int(settings.fakestar_radius if fake_radius is None else fake_radius)
+        fk_prep = None
+        try:
+            # everything that can fail before the frame is touched (fake_prepare): an exception leaves the frame as it is
+            if sub_pn is None:
+                raise ValueError('no PSF stamps of the new frame')
+            if not 0 <= fk_radius <= 4:
+                raise ValueError('fake_radius: 0 .. 4 pixels expected')
+            lay = fake_layout(ny, nx, size, nsy, nsx, int(sub_pn.shape[1]), int(fake_stars), settings.fakestar_s2n if fake_s2n is None else fake_s2n,
+                              settings.fakestar_seed if fake_seed is None else fake_seed)
+            fk_prep = fake_prepare(ctx, work, rwork, bstd, new_mask, ref_mask if ref_grid is None else ref_mask_remapped, psf_new, sub_pn,
+                                   lay, nsx, size, clear_half=settings.fake_clear_half,
+                                   clear_nsigma=settings.fake_clear_nsigma if fake_clear_nsigma is None else fake_clear_nsigma,
+                                   noise=fk_noise, seed=lay['seed'])
+        except Exception as ex:
+            logging.getLogger(__name__).warning('fake stars were not injected: %s', ex)
+            hdr_t.update(fake_header(False))
+        if fk_prep is not None:
+            # the launch itself is not survived: a frame that may carry stars is never subtracted under T-FKP False
+            fk_inj, fk_peaks = _fake_launch(ctx, fk_prep)
+            fk = dict(layout=lay)
+            del fk_prep
+
     # ---- sub-images
     scal = np.zeros((nsub, 6), np.float32)
     scal[:, 0], scal[:, 1] = scal_n, tile_medians(sdr)
@@ -700,7 +745,12 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                             frame_clipped_stats_enqueue(ctx, res['Fpsferr'], new_mask)])
     if d_fl is not None and not d_fl.numel():
         d_fl = None
-    back = [t for t in (d_fe, d_st, d_fl, d_tf, d_ts, d_edge) if t is not None]
+    d_fk = None
+    if fk is not None:
+        # the stars read back, with what the injection wrote per star: one more tensor in the same copy back
+        d_rec = _fake_recover(ctx, res['Scorr'], res['Fpsf'], res['Fpsferr'], fk['layout'], fk_radius, d_peaks=fk_peaks)
+        d_fk = torch.cat([d_rec.reshape(-1)] + [t.to(torch.float32) for t in fk_inj])
+    back = [t for t in (d_fe, d_st, d_fl, d_tf, d_ts, d_edge, d_fk) if t is not None]
     got = (fetch(ctx, *back) if len(back) > 1 else [fetch(ctx, back[0])]) if back else []
     fe = got.pop(0) if d_fe is not None else None
     st = got.pop(0) if d_st is not None else None
@@ -708,12 +758,22 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     tf = got.pop(0) if d_tf is not None else None
     ts = got.pop(0) if d_ts is not None else None
     edge_at = got.pop(0) if d_edge is not None else None
+    if d_fk is not None:
+        nfk = int(fk['layout']['ys'].size)
+        fkh = got.pop(0)
+        fk_rec, fk_host = fkh[:6 * nfk].reshape(nfk, 6), [fkh[(6 + j) * nfk:(7 + j) * nfk] for j in range(3)] + [fkh[9 * nfk:].astype(np.uint8)]
+        fk_first = np.zeros(0, np.int32)
     if tys.size:
         res['transients'] = [dict(y=y, x=x, scorr=sc, fpsf=f, fpsferr=e)
                              for y, x, sc, f, e in zip(tys.tolist(), txs.tolist(), tsc.tolist(), fe[0].tolist(), fe[1].tolist())]
         if fl is not None:
             for d, v in zip(res['transients'], fl.tolist()):
                 d['flags'] = v
+        if d_fk is not None:
+            # the rows that are fake stars: flagged here, so that every drop below carries the flag along with its row
+            fk_first = fake_match(res['transients'], fk['layout'], fk_radius, flags=fk_host[3])
+            for d, v in zip(res['transients'], fk_first.tolist()):
+                d['fake_star'] = v
         if tf is not None:
             n = int(tys.size)
             cols, fold = tf[:6 * n].reshape(6, n), tf[6 * n:]
@@ -754,6 +814,10 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             hdr_t['T-NVET'] = (len(keep), 'number of transient candidates that passed the vetting')
     else:
         res['transients'] = []
+    if d_fk is not None:
+        tab = fake_table(fk['layout'], fk_host, fk_rec, nsig, fk_first, [d['fake_star'] for d in res['transients']])
+        res['fakestars'] = dict(table=tab, layout=fk['layout'])
+        hdr_t.update(fake_header(True, tab, fk['layout'], fk_noise, fk_radius, int((fk_first > 0).sum())))
     if ref_mask_remapped is not None and 'T-NOFFR' not in hdr_t:
         hdr_t['T-NOFFR'] = (0, 'candidates dropped: no reference there')
     hdr['Z-P'] = (True, 'successfully processed by ZOGY?')

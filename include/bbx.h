@@ -1142,6 +1142,56 @@ int bbx_align_grid(bbx_ctx *ctx, const double *d_coef, int ny, int nx, int step,
 int bbx_remap_mask(bbx_ctx *ctx, int in_ny, int in_nx, const uint8_t *d_mask, int out_ny, int out_nx, const double *d_grid,
                    int gny, int gnx, int step, int edge_bit, uint8_t *d_out, int64_t *d_nedge, void *stream);
 
+/* ---- fake stars (bbx_fake.hip): stars of an asked S/N added to the background-subtracted new frame IN PLACE before
+ * it is cut into sub-images, and read back from Scorr / Fpsf / Fpsferr.  zogy's fake-star code is [EXT], not in the reference tree:
+ * only the key names T-NFAKE, T-FAKESN follow the reference, the rules below are THIS PROJECT'S OWN and parity is unpinned.
+ * Per star s < nstar at the integer pixel (d_ys, d_xs) of d_frame[ny][nx], S odd, <= 49; the first rule of 1-2 that holds is the
+ * star's flag (one bit), and a flagged star adds nothing and gets 0 in its three floats:
+ *  1 the stamp P[S][S] as steps 1-3 of bbx_psf_optflux_shift form it (d_terms or d_idx: exactly one; the same device functions),
+ *    shifted by (dy, dx) = d_off[s], divided by its float64 sum.  FAKE_NO_PSF 8: the sum is not positive and finite, or an offset
+ *    is not within [-0.5, 0.5].
+ *  2 FAKE_OFF_FRAME 4: the S x S stamp about the pixel leaves the frame.  Then, in the (2 clear_half + 1)^2 window about the pixel
+ *    (0 <= clear_half <= S / 2: the window lies inside the star's own stamp; clipped to the frame): FAKE_MASKED 1: d_mask_new or
+ *    d_mask_ref (either may be NULL) is not 0 at a pixel; FAKE_ON_SOURCE 2: the frame's value, or d_ref's (d_ref may be NULL: the
+ *    reference's background-subtracted frame on the same grid), is not finite or |value| > clear_nsigma * sigma in float32, sigma
+ *    the new frame's at that pixel, from the frame d_sigma[ny][nx] or read off sigma_mini (bbx_psf_optflux_shift's reader: exactly
+ *    one of the two).  FAKE_NO_FLUX 16: d_s2n[s] is not positive and finite, a sigma of the stamp's pixels is not positive and
+ *    finite (or its float32 square is 0), or A, q or F below leave the range of finite numbers (F: of float32).
+ *  3 the flux F: S/N(F) = F sqrt(sum_i P_i^2 / (v_i + F max(P_i, 0))) = d_s2n[s], v_i = sigma_i sigma_i in float32, everything else
+ *    float64 (the variance model of bbx_psf_optflux_shift's step 4 for a source on an empty sky).  S/N^2 is convex and increasing
+ *    in F: Newton's iteration from F_hi, kept inside [F_lo, F_hi] by bisection, until the step is below 1e-15 F; F_lo = s / sqrt(A),
+ *    F_hi = (s^2 q + sqrt(s^4 q^2 + 4 A s^2)) / (2 A), A = sum P_i^2 / v_i, q = max_i max(P_i, 0) / v_i.  F is rounded to float32,
+ *    and that float32 is the flux of everything below.
+ *  4 frame_i = (float)((double) frame_i + F P_i + [noise] sqrt(F max(P_i, 0)) g_i): float64, one rounding per pixel.  g_i is the
+ *    standard normal of (seed, s, i), i = row * S + column of the stamp, stateless:
+ *      Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53 on word 0, 0xCD9E8D57 on word 2, key increments 0x9E3779B9,
+ *      0xBB67AE85 after every round) on the counter (i, s, 0, 0) with the key (seed & 0xffffffff, seed >> 32) -> words r0..r3;
+ *      u1 = (r0 + 0.5) / 2^32, u2 = (r1 + 0.5) / 2^32, g = sqrt(-2 ln u1) cos(2 pi u2), in float64 (r2, r3 are not used).
+ *  5 d_flux[s] = F; d_real[s] = the float64 sum of everything step 4 added (before the rounding of the frame), as float32;
+ *    d_snr_sky[s] = F sqrt(A) as float32; d_flags[s] u8.
+ * The CALLER guarantees that the stamps of two stars do not overlap (Chebyshev distance of their pixels >= S): every frame pixel is
+ * then read and written by one thread of one workgroup, which is what makes the in-place add free of races without atomics.
+ * Deterministic: no atomics, no state, every sum in a fixed order (bbx_psf_optflux_shift's): same arguments -> same bits.
+ * nstar == 0: nothing is launched.  One workgroup of 256 per star, no host wait.                                             */
+#define BBX_FAKE_MASKED    1
+#define BBX_FAKE_ON_SOURCE 2
+#define BBX_FAKE_OFF_FRAME 4
+#define BBX_FAKE_NO_PSF    8
+#define BBX_FAKE_NO_FLUX   16
+int bbx_fake_inject(bbx_ctx *ctx, int ny, int nx, float *d_frame, const float *d_ref, const float *d_sigma,
+                    const bbx_spline_image *sigma_mini, const uint8_t *d_mask_new, const uint8_t *d_mask_ref, int S,
+                    int nplane, const float *d_cube, const float *d_terms, const int32_t *d_idx, int nstar,
+                    const int32_t *d_ys, const int32_t *d_xs, const float *d_off, const float *d_s2n, int clear_half,
+                    float clear_nsigma, int noise, uint64_t seed, float *d_flux, float *d_real, float *d_snr_sky,
+                    uint8_t *d_flags, void *stream);
+
+/* The stars read back: per star the largest finite value of d_scorr[ny][nx] in the (2 radius + 1)^2 window about (d_ys, d_xs)
+ * clipped to the frame, radius <= 4; equal values: the lowest row, then the lowest column.  d_out[nstar][6] float32 = (dy, dx of
+ * that pixel relative to the star's, Scorr, Fpsf, Fpsferr there, Fpsf at the star's own pixel -- 0 where that is off the frame).  A
+ * window without a finite value: dy = dx = NaN, the four values 0.  One wave per star, nstar == 0: nothing is launched.  */
+int bbx_fake_recover(bbx_ctx *ctx, int ny, int nx, const float *d_scorr, const float *d_fpsf, const float *d_fpsferr,
+                     int nstar, const int32_t *d_ys, const int32_t *d_xs, int radius, float *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
