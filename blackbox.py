@@ -105,6 +105,33 @@ def align_keywords(a, S, tel=None):
     return kw
 
 
+def astrometry_keywords(a, S, tel=None):
+    """the keywords --astrometry adds to the subtraction's, without the catalogue itself: the switch, and the ast_* settings with the
+    command line over them (only degrees 1 and 2, parity +1 or -1).  The pointing is not among them: it is the frame's"""
+    kw = dict(astrometry=True)
+    for key, arg, name in (('ast_poldeg', 'ast_poldeg', 'ast_poldeg'), ('ast_max_shift', 'ast_max_shift', 'ast_max_shift'),
+                           ('ast_bin', 'ast_bin', 'ast_bin'), ('ast_rounds', 'ast_rounds', 'ast_rounds'), ('ast_dist', 'ast_dist', 'ast_dist'),
+                           ('ast_rot', 'ast_rot', 'ast_rot'), ('ast_parity', 'ast_parity', 'ast_parity'), ('ast_pixscale', 'ast_pixscale', 'pixscale'),
+                           ('ast_mag_zp', 'ast_mag_zp', 'ast_mag_zp')):
+        v = getattr(a, arg, None)
+        kw[key] = S.get_par(getattr(S, name), tel) if v is None else v
+    if kw['ast_dist'] is None:
+        kw['ast_dist'] = S.get_par(S.match_dist_pix, tel)
+    if kw['ast_poldeg'] not in (1, 2):
+        raise ValueError('--ast_poldeg: degree 1 or 2, got {}'.format(kw['ast_poldeg']))
+    if kw['ast_parity'] not in (1, -1):
+        raise ValueError('--ast_parity: +1 or -1, got {}'.format(kw['ast_parity']))
+    return kw
+
+
+def name_list(v):
+    """'RA,DEC,MAG' -> ('RA', 'DEC', 'MAG')"""
+    out = tuple(t.strip() for t in str(v).split(',') if t.strip())
+    if len(out) != 3:
+        raise argparse.ArgumentTypeError('three comma separated column names expected, got %r' % (v,))
+    return out
+
+
 def float_list(v):
     """'0.66,1.5,5' -> (0.66, 1.5, 5.0)"""
     try:
@@ -341,7 +368,8 @@ class Reducer:
         # inputs of the subtraction stage
         self.sub = None
         from blackbox_amd import settings as _S
-        if args.cat_extract or args.trans_extract or (_S.get_par(_S.limmag, tel) if args.limmag is None else args.limmag):
+        if args.cat_extract or args.trans_extract or (_S.get_par(_S.limmag, tel) if args.limmag is None else args.limmag) or \
+                (_S.get_par(_S.astrometry, tel) if args.astrometry is None else args.astrometry):
             self.sub = self._load_subtraction_inputs(load)
         _mark('calibration_and_reference_files_in_hbm')
 
@@ -431,6 +459,16 @@ class Reducer:
                 sub['limmag_nsigma'] = a.limmag_nsigma
             if a.limmag_psf_frac is not None:
                 sub['limmag_psf_frac'] = a.limmag_psf_frac
+        if par(a.astrometry, 'astrometry'):
+            # the astrometric solution of every frame against one catalogue, read once per run; the keywords are only passed when
+            # switched on.  No catalogue, a missing column, too many rows: an error here, before any frame runs
+            from blackbox_amd import astrometry
+            path = par(a.ast_cat, 'ast_cat')
+            if not path:
+                raise ValueError('--astrometry True needs --ast_cat (or settings.ast_cat)')
+            sub.update(astrometry_keywords(a, S, self.tel))
+            sub['ast_catalog'] = astrometry.load_catalog(self.ctx, path, par(a.ast_cat_cols, 'ast_cat_cols'))
+            log.info('astrometric catalogue %s: %d rows', path, sub['ast_catalog'].n)
         if par(a.objmask, 'objmask'):
             # object mask + second background pass, whenever the subtraction stage runs; the keywords are only passed when switched on
             sub['objmask'] = True
@@ -700,6 +738,10 @@ class Reducer:
         try:
             if res is None:
                 kw = {k: v for k, v in self.sub.items() if k not in ('ref', 'ref_mask', 'psf_new', 'psf_ref')}
+                if self.sub.get('astrometry'):
+                    # the pointing is the frame's own: its header's RA, DEC, with --ast_ra --ast_dec over them
+                    from blackbox_amd import astrometry
+                    kw['ast_pointing'] = astrometry.frame_pointing(header, self.args.ast_ra, self.args.ast_dec)
                 res = G.optimal_subtraction(self.ctx, data, self.sub['ref'], mask, self.sub['ref_mask'],
                                             self.sub['psf_new'], self.sub['psf_ref'], **kw)
                 self.ctx.sync()
@@ -953,7 +995,8 @@ class _ListRun:
                       header_hook=self.header_hook, stage_limmag=r._limmag_is_flux)
         self.pipe = pipeline.FramePipeline(r.ctx, r.tel, geom, mflat=r.mflat, mbias=r.mbias, bpm=r.bpm, xtalk_coeffs=r.xtalk,
                                            exptime=self.exptime, depth=depth, lanes=min(lanes, depth), do_finish=True, detect_sats=True,
-                                           keep_outputs=True, subtract=dict(r.sub) if r.sub is not None else None, log=log, **kw)
+                                           keep_outputs=True, subtract=dict(r.sub) if r.sub is not None else None, log=log,
+                                           ast_pointing=(r.args.ast_ra, r.args.ast_dec), **kw)
         # unsigned 16-bit raw frames (plain or fpacked: what the telescopes deliver) come through the input stage: reader
         # threads, one upload per file, the Rice decode on the device, nothing of it on the orchestrating thread
         if self.first_raw.dtype == r.torch.uint16 and len(self.todo) > 1:
@@ -1312,6 +1355,29 @@ def build_parser():
     ap.add_argument('--align_max_shift', type=float, default=None,
                     help='[pix] --ref_align: largest offset new - ref the vote looks for (settings.align_max_shift)')
     ap.add_argument('--align_bin', type=float, default=None, help='[pix] --ref_align: bin of the vote\'s histogram (settings.align_bin)')
+    ap.add_argument('--astrometry', type=str2bool, default=None,
+                    help='solve the new frame against --ast_cat from its own star list (needs --psf_new or --psf_build): the TAN[-SIP] WCS, '
+                         'A-P A-PSCALE A-PSCALX A-PSCALY A-ROT A-ROTX A-ROTY A-CAT-F A-NAST A-TNAST A-DRA A-DRASTD A-DDEC A-DDESTD RA-CNTR '
+                         'DEC-CNTR A-PLDG A-NVOTE A-MSHFT A-FLAGS in the header of _red, RA DEC in _red_cat, RA_PEAK DEC_PEAK [RA_PSF_D '
+                         'DEC_PSF_D] in _red_trans; a solve that fails leaves A-P False and today\'s products (default: settings.astrometry)')
+    ap.add_argument('--ast_cat', type=str, default=None,
+                    help='--astrometry: the star catalogue, a FITS binary table with positions in degrees (ICRS) and a magnitude (settings.ast_cat)')
+    ap.add_argument('--ast_cat_cols', type=name_list, default=None,
+                    help='--astrometry: its three column names, comma separated (settings.ast_cat_cols: RA,DEC,MAG)')
+    ap.add_argument('--ast_ra', type=float, default=None, help='[deg] --astrometry: the pointing of every frame, over the header\'s RA')
+    ap.add_argument('--ast_dec', type=float, default=None, help='[deg] --astrometry: the pointing of every frame, over the header\'s DEC')
+    ap.add_argument('--ast_pixscale', type=float, default=None, help='[arcsec/pix] --astrometry: nominal pixel scale (settings.pixscale)')
+    ap.add_argument('--ast_rot', type=float, default=None, help='[deg] --astrometry: nominal rotation, FITS CROTA2 convention (settings.ast_rot)')
+    ap.add_argument('--ast_parity', type=int, choices=(-1, 1), default=None,
+                    help='--astrometry: +1 north up, east left at rotation 0; -1 mirrored (settings.ast_parity)')
+    ap.add_argument('--ast_max_shift', type=float, default=None,
+                    help='[pix] --astrometry: largest pointing error the vote looks for (settings.ast_max_shift)')
+    ap.add_argument('--ast_bin', type=float, default=None, help='[pix] --astrometry: bin of the vote\'s histogram (settings.ast_bin)')
+    ap.add_argument('--ast_poldeg', type=int, choices=(1, 2), default=None,
+                    help='--astrometry: degree of the solution, 1 (TAN) or 2 (TAN-SIP) (settings.ast_poldeg)')
+    ap.add_argument('--ast_rounds', type=int, default=None, help='--astrometry: rounds of match and fit behind the vote (settings.ast_rounds)')
+    ap.add_argument('--ast_dist', type=float, default=None, help='[pix] --astrometry: largest distance of a match (settings.ast_dist, else match_dist_pix)')
+    ap.add_argument('--ast_mag_zp', type=float, default=None, help='--astrometry: zeropoint of the catalogue fluxes (settings.ast_mag_zp)')
     ap.add_argument('--subimage_size', type=int, default=None)
     ap.add_argument('--flat_norm_sec', type=section, default=None,
                     help='y0:y1,x0:x1: flat normalisation / statistics section (default set_bb.flat_norm_sec of the telescope)')

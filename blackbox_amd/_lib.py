@@ -167,6 +167,9 @@ SIGNATURES = {
     'bbx_fake_inject': (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _i, C.c_uint64,
                             _vp, _vp, _vp, _vp, _vp]),
     'bbx_fake_recover': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    'bbx_wcs_cat_list': (_i, [_vp, _i, _vp, _vp, C.c_double, C.c_double, _i, _i, _pd, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'bbx_wcs_pix2sky': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _pd, C.c_double, C.c_double, _vp, _vp]),
+    'bbx_wcs_pair_stats': (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _pd, C.c_double, C.c_double, _vp, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError if the export is missing

@@ -219,6 +219,29 @@ def align_header(fit=None, shape=None, poldeg=None, n_edge=None):
     return hdr
 
 
+def align_chain(ctx, a, b, shape, poldeg, rounds, dist, snr_min=None, nbright=None, max_shift=None, bin=None):
+    """The chain both solves share (the registration of the reference, and astrometry.solve with the catalogue on its virtual
+    grid as b): the vote of the lists a, b (five columns each; a sorted by (y, x)), the affine fit of its pairs, [rounds] times
+    (b through the inverse of T, sort, bbx_match_mutual within dist, clipped fit of degree poldeg).  Queued on ctx's stream,
+    no host wait -> device (info int32 [8], coarse float64 [2], coef float64 [12], stats float64 [4], items int32 [N, 2],
+    kept uint8 [N]): the pairs the last fit was given and which of them it kept"""
+    n_a = _expect_list(a, 'new list')
+    _expect_list(b, 'reference list')
+    info, coarse, items = align_vote(ctx, a, b, nbright, max_shift, bin)
+    coef, stats, kept = align_fit(ctx, a, b, items, shape, 1, snr_min)
+    ar = torch.arange(n_a, dtype=torch.int32, device=ctx.device)
+    for _ in range(rounds):
+        sy, sx, so, perm = align_sort(*align_apply(ctx, b[:3], coef, shape, poldeg))
+        m = match_mutual(ctx, a[:3], (sy, sx, so), dist)
+        if perm.numel():
+            ib = torch.where(m >= 0, perm[m.clamp(min=0).to(torch.int64)].to(torch.int32), torch.full_like(m, -1))
+        else:
+            ib = torch.full_like(m, -1)
+        items = torch.stack([torch.where(m >= 0, ar, torch.full_like(ar, -1)), ib], dim=1).contiguous()
+        coef, stats, kept = align_fit(ctx, a, b, items, shape, poldeg, snr_min)
+    return info, coarse, coef, stats, items, kept
+
+
 def align_reference(ctx, new_lists, ref_stars, shape_new, shape_ref, ref_mask=None, poldeg=None, max_shift=None, bin=None, dist=None,
                     snr_min=None, step=32, rounds=None, nbright=None):
     """The registration of the reference on the new frame: new_lists = the new frame's (ys, xs, off, flux, err), sorted by
@@ -233,20 +256,7 @@ def align_reference(ctx, new_lists, ref_stars, shape_new, shape_ref, ref_mask=No
         raise ValueError('align_reference: degree 1 or 2, got {}'.format(poldeg))
     a = tuple(new_lists)
     b = tuple(ref_stars.lists()) if hasattr(ref_stars, 'lists') else tuple(ref_stars)
-    n_a = _expect_list(a, 'new list')
-    _expect_list(b, 'reference list')
-    info, coarse, pairs = align_vote(ctx, a, b, nbright, max_shift, bin)
-    coef, stats, _ = align_fit(ctx, a, b, pairs, shape_new, 1, snr_min)
-    ar = torch.arange(n_a, dtype=torch.int32, device=ctx.device)
-    for _ in range(rounds):
-        sy, sx, so, perm = align_sort(*align_apply(ctx, b[:3], coef, shape_new, poldeg))
-        m = match_mutual(ctx, a[:3], (sy, sx, so), dist)
-        if perm.numel():
-            ib = torch.where(m >= 0, perm[m.clamp(min=0).to(torch.int64)].to(torch.int32), torch.full_like(m, -1))
-        else:
-            ib = torch.full_like(m, -1)
-        items = torch.stack([torch.where(m >= 0, ar, torch.full_like(ar, -1)), ib], dim=1).contiguous()
-        coef, stats, _ = align_fit(ctx, a, b, items, shape_new, poldeg, snr_min)
+    info, coarse, coef, stats, _, _ = align_chain(ctx, a, b, shape_new, poldeg, rounds, dist, snr_min, nbright, max_shift, bin)
     grid = align_grid(ctx, coef, shape_new, step)
     mask, nedge = remap_mask(ctx, ref_mask, shape_ref, grid, shape_new, step)
     h_coef, h_stats, h_info, h_coarse, h_nedge = fetch(ctx, coef, stats, info, coarse, nedge)

@@ -4,9 +4,9 @@ versions for red-flagged images (qc.py:451-503 -> zogy.format_cat).
 
 [EXT] zogy.format_cat is not part of /root/reference; the column names follow the BlackGEM /
 MeerLICHT catalogue conventions for the quantities the hot path produces (pixel positions,
-PSF-weighted optimal fluxes, ZOGY significance and PSF flux); everything that needs astrometry,
-photometric calibration or the real-bogus classifier (RA/DEC, MAG_*, CLASS_REAL) is out of scope
-and absent.
+PSF-weighted optimal fluxes, ZOGY significance and PSF flux); everything that needs the photometric
+calibration or the real-bogus classifier (MAG_*, CLASS_REAL) is out of scope and absent; sky
+positions come with the astrometric solution (below).
 
 Thumbnails (settings.save_thumbnails / save_thumbnails_pngs, both off by default): a transient
 table that carries them is written with THUMBNAIL_RED, THUMBNAIL_REF, THUMBNAIL_D, THUMBNAIL_SCORR
@@ -23,6 +23,10 @@ FLAGS_OPT (PHOT_COLUMNS: 1 no centroid, 2 masked pixels left out, 4 no PSF sum) 
 Aperture photometry (settings.cat_apphot, off by default): a 'new' table that carries it is written with the columns of
 aper_columns(table) after those: E_FLUX_APER_R<r>xFWHM / E_FLUXERR_APER_R<r>xFWHM per radius (qc.py:489-502), BKG_APER, BKGSTD_APER,
 NSKY_APER, FWHM_APER, FLAGS_APER; the dummy catalogue keeps the seven.
+
+Astrometric solution (settings.astrometry, off by default): a 'new' table of a frame that was solved is written with RA, DEC (float64,
+degrees, ICRS) after those, at the very position its X_POS / Y_POS state; a 'trans' table with RA_PEAK, DEC_PEAK at X_PEAK / Y_PEAK and,
+where it carries the fit of P_D, RA_PSF_D, DEC_PSF_D at X_PSF_D / Y_PSF_D.  A frame that was not solved, and the dummy catalogues: none.
 """
 import os
 import shutil
@@ -67,7 +71,12 @@ FAKESTAR_TABLE = (('NUMBER', np.int32, ''), ('X_IN', np.float32, 'pix'), ('Y_IN'
                   ('SNR_SKY_IN', np.float32, ''), ('E_FLUX_IN', np.float32, 'e-'), ('E_FLUX_REAL', np.float32, 'e-'), ('FLAGS_IN', np.int16, ''),
                   ('X_PEAK', np.float32, 'pix'), ('Y_PEAK', np.float32, 'pix'), ('SCORR_OUT', np.float32, ''), ('E_FLUX_OUT', np.float32, 'e-'),
                   ('E_FLUXERR_OUT', np.float32, 'e-'), ('E_FLUX_OUT_AT', np.float32, 'e-'), ('FOUND', np.int16, ''), ('NUMBER_TRANS', np.int32, ''))
-THUMBNAILS = ('RED', 'REF', 'D', 'SCORR')                     # plane order of zogy.thumbnail_stamps; blackbox.py:2701
+# astrometric solution (settings.astrometry; zogy.optimal_subtraction(astrometry=True)): the sky position at the table's own X_POS /
+# Y_POS ('new'), X_PEAK / Y_PEAK and, with TRANSFIT_COLUMNS, X_PSF_D / Y_PSF_D ('trans'), appended to a table that carries them
+AST_COLUMNS = (('RA', np.float64, 'deg'), ('DEC', np.float64, 'deg'))
+AST_TRANS_COLUMNS = (('RA_PEAK', np.float64, 'deg'), ('DEC_PEAK', np.float64, 'deg'))
+AST_TRANSFIT_COLUMNS = (('RA_PSF_D', np.float64, 'deg'), ('DEC_PSF_D', np.float64, 'deg'))
+THUMBNAILS = ('RED', 'REF', 'D', 'SCORR')                    # plane order of zogy.thumbnail_stamps; blackbox.py:2701
 THUMBNAIL_COLUMNS = tuple('THUMBNAIL_' + c for c in THUMBNAILS)
 
 
@@ -122,6 +131,11 @@ def format_cat(table, cat_output, cat_type='new', header2add=None):
         for name, dt, unit in FAKE_COLUMNS:
             cols[name] = np.asarray(table[name]).astype(dt)
             units[name] = unit
+    for ctype, group in (('new', AST_COLUMNS), ('trans', AST_TRANS_COLUMNS), ('trans', AST_TRANSFIT_COLUMNS)):
+        if cat_type == ctype and table is not None and group[0][0] in table:
+            for name, dt, unit in group:
+                cols[name] = np.asarray(table[name]).astype(dt)
+                units[name] = unit
     if cat_type == 'trans' and table is not None and THUMBNAIL_COLUMNS[0] in table:
         for name in THUMBNAIL_COLUMNS:
             cols[name] = np.asarray(table[name]).astype(np.float32)
@@ -168,6 +182,11 @@ def _transient_columns(t):
             tab[name] = np.array([d[key] + 1.0 if name[:2] in ('X_', 'Y_') else d[key] for d in t], dt)
     if t and all('fake_star' in d for d in t):
         tab['FAKE_STAR'] = np.array([d['fake_star'] for d in t], np.int16)
+    for group in (AST_TRANS_COLUMNS, AST_TRANSFIT_COLUMNS):
+        # the astrometric solution (zogy.optimal_subtraction(astrometry=True)): degrees, float64
+        if t and all(group[0][0].lower() in d for d in t):
+            for name, dt, _ in group:
+                tab[name] = np.array([d[name.lower()] for d in t], dt)
     return tab
 
 

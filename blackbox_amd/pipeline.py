@@ -294,7 +294,7 @@ class FramePipeline:
     def __init__(self, ctx, tel, geom, mflat=None, mbias=None, bpm=None, xtalk_coeffs=None, exptime=60.0,
                  pool=None, depth=4, do_cosmics=True, do_finish=False, accum='f32seq', keep_outputs=False, lanes=2,
                  detect_sats=False, subtract=None, log=None, outstage=None, out_base=None, on_written=None, header_hook=None,
-                 stage_limmag=True):
+                 stage_limmag=True, ast_pointing=None):
         """do_finish: crosstalk, mask counts, edge fill (the tail of blackbox_reduce);
         detect_sats: satellite trails before them (blackbox.py:1919-1952);
         subtract: dict of keyword arguments for zogy.optimal_subtraction (ref=, ref_mask=, psf_new=,
@@ -305,8 +305,11 @@ class FramePipeline:
         `.fits.fz` by the stage's writer threads (blackbox.py:1981-1990, 812-857); out_base(idx, header) -> path of the
         frame's _red product without '.fits'; on_written(frame, group) is called by a writer thread when the last file
         of the frame is on disk; header_hook(frame, headers) -> headers lets the caller complete the headers of the
-        frame's files ({path: header, None: default}) when the frame's scalars are in, before the writers use them"""
+        frame's files ({path: header, None: default}) when the frame's scalars are in, before the writers use them;
+        ast_pointing: (RA, DEC) in degrees, either may be None: with subtract['astrometry'] every frame's pointing is read off its
+        own header (astrometry.frame_pointing) with these over it, and goes to zogy.optimal_subtraction as a per-frame argument"""
         self.ctx, self.tel, self.geom = ctx, tel, geom
+        self.ast_pointing = tuple(ast_pointing) if ast_pointing is not None else (None, None)
         # stage-C lanes: (context, stream); lane 0 is the caller's context
         self.own_ctx = [R.Context(ctx.device.index) for _ in range(max(1, lanes) - 1)]
         self.lane_stream = [torch.cuda.Stream(device=ctx.device) for _ in range(max(1, lanes))]
@@ -675,6 +678,9 @@ class FramePipeline:
             try:
                 align = bool(self.subtract.get('ref_align'))
                 more = dict(ref_stars=self.ref_stars) if align else {}
+                if self.subtract.get('astrometry'):
+                    from . import astrometry
+                    more['ast_pointing'] = astrometry.frame_pointing(h, *self.ast_pointing)
                 sub = G.optimal_subtraction(ctx, data, new_mask=mask, zogy_gate=self.zogy_gate, ref_bkg_std=self.ref_bkg_std,
                                             ref_rows=self.ref_rows, ref_psf=self.ref_psf, ref_catalog=self.ref_catalog, **more, **self.subtract)
                 if align and self.ref_stars is None and sub.get('ref_stars') is not None:

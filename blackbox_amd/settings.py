@@ -123,6 +123,22 @@ align_bin = 4.0                # [pix] bin of the vote's histogram of pair diffe
 align_nbright = 2048           # sources of each list that vote (at most 2048)
 align_rounds = 3               # rounds of (reference list through T^-1, match, fit) behind the vote
 
+# ---- astrometric solution from a star catalogue (bbx_wcs.hip + the chain of bbx_align.hip; [EXT] astrometry.net in
+# zogy: only the A-* key names follow the reference, blackbox.py:3067-3084, 3144-3145; the method is this project's own) ----
+# Off by default: no kernel of bbx_wcs.hip is launched, no WCS or A-* key and no RA / DEC column is added.
+astrometry = False             # --ast_cat on the new frame's star list: the TAN[-SIP] WCS and the A-* keys in _red.fits, RA DEC columns
+ast_cat = None                 # the catalogue: a FITS binary table with positions in degrees (ICRS) and a magnitude
+ast_cat_cols = ('RA', 'DEC', 'MAG')    # its column names
+ast_cat_max = 2000000          # more rows than this: an error at load
+ast_rot = 0.0                  # [deg] nominal rotation (FITS CROTA2 convention); the scale is pixscale below
+ast_parity = 1                 # +1: north up, east left at rotation 0; -1: mirrored
+ast_max_shift = 256.0          # [pix] largest pointing error the vote looks for, in either axis (2.4 arcmin at 0.564 arcsec/px)
+ast_bin = 4.0                  # [pix] bin of the vote's histogram
+ast_poldeg = 2                 # degree of T, 1 (TAN) or 2 (TAN-SIP)
+ast_rounds = 3                 # rounds of (catalogue through T^-1, match, fit) behind the vote
+ast_dist = None                # [pix] largest distance of a match; None: match_dist_pix
+ast_mag_zp = 25.0              # flux of a catalogue row = 10^(-0.4 (mag - ast_mag_zp)): only the brightness ranking rests on it
+
 # ---- source shapes of `_cat.fits` and the frame's seeing statistics (header keys S-NOBJ S-FWHM S-FWSTD S-SEEING S-SEESTD
 # S-ELONG S-ELOSTD, blackbox.py:3051-3057; [EXT] SExtractor in zogy: adaptive second moments here) ----
 # Off by default: `_cat.fits` keeps its seven columns and the header gets none of the keys.

@@ -46,6 +46,8 @@ from .limflux import check_parameters as _limflux_parameters, limflux_header, li
 from .align import (ALIGN_CLIP, ALIGN_DET, ALIGN_FAR, ALIGN_FEW_PAIRS, ALIGN_NMIN, ALIGN_NOT_PD, ALIGN_PAIR_CAP,         # noqa: F401
                     ALIGN_VOTE_FAILED, RefStars, _expect_list, align_apply, align_fit, align_grid, align_grid_host, align_grid_shape,
                     align_header, align_reference, align_sort, align_vote, remap_mask)
+from . import astrometry as _ast                                     # (_optimal_subtraction's switch bears the module's name)
+from .astrometry import AstCatalog, ast_header, frame_pointing, wcs_header, wcs_pix2sky         # noqa: F401
 from .fakestars import (FAKE_COLS, FAKE_MASKED, FAKE_NO_FLUX, FAKE_NO_PSF, FAKE_OFF_FRAME, FAKE_ON_SOURCE, FOUND_KEPT, FOUND_PEAK,         # noqa: F401
                         FOUND_ROW, check_apart, fake_header, fake_inject, fake_launch, fake_layout, fake_match, fake_prepare, fake_recover,
                         fake_s2n_list, fake_table)
@@ -83,7 +85,9 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                          trans_elong_gauss_max=None, ref_align=False, align_poldeg=None, align_max_shift=None, align_bin=None,
                          align_nbright=None, align_rounds=None, ref_stars=None, aper_phot=False, apphot_radii=None, apphot_sky_inout=None,
                          apphot_local_sky=None, limmag=False, limmag_nsigma=None, limmag_psf_frac=None, fake_stars=0, fake_s2n=None,
-                         fake_seed=None, fake_noise=None, fake_radius=None, fake_clear_nsigma=None):
+                         fake_seed=None, fake_noise=None, fake_radius=None, fake_clear_nsigma=None, astrometry=False, ast_catalog=None,
+                         ast_pointing=None, ast_poldeg=None, ast_max_shift=None, ast_bin=None, ast_rounds=None, ast_dist=None, ast_rot=None,
+                         ast_parity=None, ast_pixscale=None, ast_mag_zp=None):
     """The numerical core of zogy.optimal_subtraction(new_fits, ref_fits, ...) (call sites
     blackbox.py:2350-2354 new-only, 2460-2465 new + ref) on device tensors: background mesh +
     subtraction, variance images, [remapping of the reference to the new frame's grid],
@@ -210,6 +214,22 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       (a layout that does not fit the sub-image, ...): the frame goes on untouched, T-FKP False, T-NFAKE 0.  0: no
                       kernel of bbx_fake.hip is launched, no such keys.  fake_s2n, fake_seed, fake_noise, fake_radius,
                       fake_clear_nsigma: settings
+      astrometry    : True (with ast_catalog, an astrometry.AstCatalog kept by the caller for the run, and a PSF of the new frame; no
+                      reference is needed): the frame is solved against the catalogue (astrometry.solve_enqueue): the
+                      list the registration takes (windowed centroids + PSF fluxes of the catalogue's peaks) against the catalogue
+                      on a virtual grid about ast_pointing = (RA, DEC) in degrees -- a PER-FRAME argument: the caller reads it off
+                      the frame's header (astrometry.frame_pointing) -- through the registration's own chain (align_chain), queued
+                      behind the photometry; its six small tensors and the RA / DEC of the catalogue's rows (bbx_wcs_pix2sky at the
+                      very positions X_POS / Y_POS state) ride the photometry's copy back, the RA / DEC of the transient rows the
+                      transients': NO host wait is added.  res['astrometry'] = astrometry.solve_finish's dict; header_new gets the
+                      TAN[-SIP] WCS (CTYPE CRVAL CRPIX CD [A_ B_ terms] RADESYS), A-P A-PSCALE A-PSCALX A-PSCALY A-ROT A-ROTX A-ROTY
+                      A-CAT-F A-NAST A-TNAST A-DRA A-DRASTD A-DDEC A-DDESTD RA-CNTR DEC-CNTR A-PLDG A-NVOTE A-MSHFT A-FLAGS;
+                      res['catalog'] gains RA, DEC (float64), every transient ra_peak, dec_peak and, with trans_psffit, ra_psf_d,
+                      dec_psf_d.  A solve that fails (the chain's flag word, a coefficient that is not finite, no pointing, no PSF,
+                      an exception in the stage): A-P False, 'None' for the other keys, no WCS key and no column; the frame goes on
+                      exactly as without the switch.  ast_poldeg, ast_max_shift, ast_bin, ast_rounds, ast_dist, ast_rot, ast_parity,
+                      ast_pixscale (pixscale), ast_mag_zp: settings.  False: no kernel of bbx_wcs.hip is launched, no such keys or
+                      columns
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
             header (= header_new additions), header_trans)"""
     size = subimage_size or settings.subimage_size
@@ -229,6 +249,8 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     do_aper = bool(aper_phot) and bool(cat_extract) and have_psf
     do_align = bool(ref_align) and have_ref
     do_lim = bool(limmag)
+    do_ast = bool(astrometry)
+    ast_pending = ast_sol = None
     if do_lim:
         lim_nsigma, lim_frac = _limflux_parameters(limmag_nsigma, limmag_psf_frac)
     if do_align and ref_grid is not None:
@@ -238,7 +260,7 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     # ---- new frame: mesh, subtraction, sigma image, variance
     mini, mini_std = get_back(ctx, new, new_mask, bkg_boxsize=box)
     work = torch.empty_like(new)
-    want_phot = cat_extract or do_match or do_align
+    want_phot = cat_extract or do_match or do_align or do_ast
     want_cat =(want_phot or (build_here and have_ref)) and have_psf
     second_pass = False
     if objmask:
@@ -428,6 +450,28 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         res['limflux_info'] = dict(stat=got[0] if got else None, win=got[1] if got else None, nsigma=lim_nsigma, frac=lim_frac)
         hdr.update(limflux_header(got is not None, *(got or (None, None)), nsigma=lim_nsigma, frac=lim_frac))
 
+    def astrometry_enqueue(new_list):
+        """astrometry: the solve of the frame's list (ys, xs, off, flux, err on the device) against the catalogue, queued -> what
+        astrometry.solve_finish wants; None (and a warning) where the stage fails before it is queued"""
+        try:
+            if ast_catalog is None:
+                raise ValueError('no catalogue (ast_catalog)')
+            return _ast.solve_enqueue(ctx, new_list, ast_catalog, ast_pointing, (ny, nx), pixscale=ast_pixscale, rot=ast_rot, parity=ast_parity,
+                                      max_shift=ast_max_shift, bin=ast_bin, poldeg=ast_poldeg, rounds=ast_rounds, dist=ast_dist,
+                                      snr_min=match_snr_min, mag_zp=ast_mag_zp)
+        except Exception as ex:                                      # the frame goes on without a solution
+            logging.getLogger(__name__).warning('astrometric solve failed: %s', ex)
+            return None
+
+    def astrometry_sky(**where):
+        """the sky positions of device positions by the frame's solution -> device float64 [n, 2]; None where that fails"""
+        p = ast_pending
+        try:
+            return _ast.pix2sky(ctx, p['coef'], p['shape'], p['cd'], p['pointing'], **where)
+        except Exception as ex:
+            logging.getLogger(__name__).warning('sky positions by the astrometric solution failed: %s', ex)
+            return None
+
     ref_side = None
     # ---- full-source catalogue (a17): peaks of the background-subtracted frame above
     # cat_nsigma x S-BKGSTD, PSF-weighted optimal flux at each (zogy.get_psfoptflux)
@@ -468,8 +512,9 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             d_ys, d_xs = push(ctx, ys.astype(np.int64), xs.astype(np.int64))
             d_mk = new_mask[d_ys, d_xs]
             peaks_off = None
-            if phot_centroid or do_shapes or do_align or do_aper:
-                # the windowed centroids once: for the photometry (phot_centroid), the shapes, the apertures, the registration and the star match
+            if phot_centroid or do_shapes or do_align or do_aper or do_ast:
+                # the windowed centroids once: for the photometry (phot_centroid), the shapes, the apertures, the registration, the
+                # astrometric solve and the star match
                 d_y32, d_x32 = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
                 sigw = window_sigma(sub_pn)
             if phot_centroid:
@@ -478,15 +523,19 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             else:
                 stamps = source_psfs(ctx, psf_new, sub_pn, ys, xs, nsx, size)
                 f, e = psf_optflux(ctx, work, bstd, stamps, ys, xs, v_is_sigma=True)        # (bstd: frame or MiniImage)
-            if do_align:
-                # the registration: the new frame's list as the star match sees it (a peak on a masked pixel: no offset, no flux),
-                # then the reference on this frame's grid -- before anything below asks for it
+            if do_align or do_ast:
+                # the new frame's list as the star match sees it (a peak on a masked pixel: no offset, no flux)
                 if peaks_off is None:
                     peaks_off = (d_y32, d_x32, win_centroid(ctx, work, d_y32, d_x32, sigw, size, nsy, nsx))
                 bad = d_mk != 0
                 a_off = torch.where(bad[:, None], torch.full_like(peaks_off[2], float('nan')), peaks_off[2]).contiguous()
-                if register_reference((d_y32, d_x32, a_off, torch.where(bad, torch.zeros_like(f), f).contiguous(), e)):
+                new_list = (d_y32, d_x32, a_off, torch.where(bad, torch.zeros_like(f), f).contiguous(), e)
+            if do_align:
+                # the registration, then the reference on this frame's grid -- before anything below asks for it
+                if register_reference(new_list):
                     ref_side = prepare_reference()
+            if do_ast:
+                ast_pending = astrometry_enqueue(new_list)           # queued: read back with the photometry
             back = [d_mk, f, e]
             if do_shapes:
                 # the moments and their statistics are queued behind the photometry and come back with it
@@ -524,7 +573,24 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             d_lim = limflux_enqueue() if do_lim else None            # behind the photometry, in the same copy back
             if d_lim is not None:
                 back += d_lim
+            d_csky = None
+            if ast_pending is not None:
+                # the solution's six small tensors, and the sky positions of the catalogue's rows at the float32 positions X_POS /
+                # Y_POS will state (formed here as below: shapes', else the photometry's centroids, else the peaks), in the same copy back
+                if cat_extract:
+                    if do_shapes:
+                        o32 = torch.where(torch.isnan(d_shp[:, :2]), torch.zeros_like(d_shp[:, :2]), d_shp[:, :2])
+                    elif phot_centroid:
+                        o32 = torch.where(((d_pfl & PHOT_NO_CENTROID) == 0)[:, None], peaks_off[2], torch.zeros_like(peaks_off[2]))
+                    else:
+                        o32 = torch.zeros((int(ys.size), 2), dtype=torch.float32, device=ctx.device)
+                    p32 = (torch.stack([d_x32, d_y32], dim=1).to(torch.float32) + 1.0) + o32.flip(1)
+                    d_csky = astrometry_sky(pos=(p32.to(torch.float64) - 1.0).contiguous())
+                back += ast_pending['back'] + ([d_csky] if d_csky is not None else [])
             got = fetch(ctx, *back)
+            if ast_pending is not None:
+                csky = got.pop() if d_csky is not None else None     # (the last seven: the rows' sky positions, the solution)
+                ast_sol = _ast.solve_finish(ast_pending, [got.pop() for _ in range(6)][::-1])
             if do_lim:
                 limflux_finish([got.pop() for _ in range(2)][::-1] if d_lim is not None else None)     # (the last two: statistic, windows)
             aper = [got.pop() for _ in range(5)][::-1] if d_aper is not None else None      # (the last five: flux, err, sky, flags, FWHM)
@@ -581,6 +647,18 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             res['aper'] = dict(fwhm=aper[4], radii=_aper_radii(apphot_radii), n_good=hdr['AP-NSTAR'][0])
         elif do_aper:
             hdr.update(aper_header(False))
+        if ast_sol is not None:
+            res['astrometry'] = ast_sol
+            hdr.update(ast_sol['header'])
+            if ast_sol['ok'] and cat_extract and csky is not None:
+                res['catalog'].update(RA=csky[ok, 0].copy(), DEC=csky[ok, 1].copy())
+            elif not ast_sol['ok']:
+                logging.getLogger(__name__).warning('astrometric solve failed: flag word %d (vote %s)', ast_sol['flags'],
+                                                    np.asarray(ast_sol['fit']['info']).tolist())
+    if do_ast and 'astrometry' not in res:
+        # no list was formed (no PSF of the new frame, nothing above the threshold) or the stage failed before it was queued
+        res['astrometry'] = None
+        hdr.update(ast_header(None))
     if do_lim and 'limflux_info' not in res:
         # no photometry was read back (no catalogue asked for, no PSF, or nothing above the threshold): a copy back of its own
         d_lim = limflux_enqueue() if sub_pn is not None else None
@@ -750,7 +828,17 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         # the stars read back, with what the injection wrote per star: one more tensor in the same copy back
         d_rec = _fake_recover(ctx, res['Scorr'], res['Fpsf'], res['Fpsferr'], fk['layout'], fk_radius, d_peaks=fk_peaks)
         d_fk = torch.cat([d_rec.reshape(-1)] + [t.to(torch.float32) for t in fk_inj])
-    back = [t for t in (d_fe, d_st, d_fl, d_tf, d_ts, d_edge, d_fk) if t is not None]
+    d_tsky = None
+    if tys.size and ast_sol is not None and ast_sol['ok']:
+        # the sky positions of the candidates' peaks and, with the fit of P_D, of the fitted positions as X_PSF_D / Y_PSF_D will state
+        # them (float32, formed here as catalogs.transient_table does): one more tensor in the same copy back
+        t_y32, t_x32 = d_ys.to(torch.int32), d_xs.to(torch.int32)
+        parts = [astrometry_sky(ys=t_y32, xs=t_x32)]
+        if d_tf is not None:
+            pf = torch.stack([t_x32.to(torch.float32) + fit[3], t_y32.to(torch.float32) + fit[2]], dim=1)
+            parts.append(astrometry_sky(pos=((pf.to(torch.float64) + 1.0).to(torch.float32).to(torch.float64) - 1.0).contiguous()))
+        d_tsky = torch.cat(parts) if all(p is not None for p in parts) else None
+    back = [t for t in (d_fe, d_st, d_fl, d_tf, d_ts, d_edge, d_fk, d_tsky) if t is not None]
     got = (fetch(ctx, *back) if len(back) > 1 else [fetch(ctx, back[0])]) if back else []
     fe = got.pop(0) if d_fe is not None else None
     st = got.pop(0) if d_st is not None else None
@@ -763,9 +851,16 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
         fkh = got.pop(0)
         fk_rec, fk_host = fkh[:6 * nfk].reshape(nfk, 6), [fkh[(6 + j) * nfk:(7 + j) * nfk] for j in range(3)] + [fkh[9 * nfk:].astype(np.uint8)]
         fk_first = np.zeros(0, np.int32)
+    tsky = got.pop(0) if d_tsky is not None else None
     if tys.size:
         res['transients'] = [dict(y=y, x=x, scorr=sc, fpsf=f, fpsferr=e)
                              for y, x, sc, f, e in zip(tys.tolist(), txs.tolist(), tsc.tolist(), fe[0].tolist(), fe[1].tolist())]
+        if tsky is not None:
+            n = int(tys.size)
+            for i, d in enumerate(res['transients']):
+                d.update(ra_peak=float(tsky[i, 0]), dec_peak=float(tsky[i, 1]))
+                if len(tsky) == 2 * n:
+                    d.update(ra_psf_d=float(tsky[n + i, 0]), dec_psf_d=float(tsky[n + i, 1]))
         if fl is not None:
             for d, v in zip(res['transients'], fl.tolist()):
                 d['flags'] = v

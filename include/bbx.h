@@ -1192,6 +1192,45 @@ int bbx_fake_inject(bbx_ctx *ctx, int ny, int nx, float *d_frame, const float *d
 int bbx_fake_recover(bbx_ctx *ctx, int ny, int nx, const float *d_scorr, const float *d_fpsf, const float *d_fpsferr,
                      int nstar, const int32_t *d_ys, const int32_t *d_xs, int radius, float *d_out, void *stream);
 
+/* ---- astrometric solution from a star catalogue (bbx_wcs.hip).  zogy solves with astrometry.net ([EXT]); only the
+ * key names A-* follow the reference, the method and every rule below are THIS PROJECT'S OWN, stated in float64 numpy by
+ * tests/astrometry_ref.py, and parity is unpinned.  The solve itself is the chain of bbx_align_* with A = the frame's star list and
+ * B = the catalogue on a virtual pixel grid of the frame's shape; these three entries are the sphere.  Everything is float64.
+ *
+ * Rule 1, standard coordinates about the pointing (ra0, dec0), all angles in degrees at the interface (d2r = pi / 180):
+ *   D = sin dec0 sin dec + cos dec0 cos dec cos(ra - ra0), xi = cos dec sin(ra - ra0) / D,
+ *   eta = (cos dec0 sin dec - sin dec0 cos dec cos(ra - ra0)) / D, both times 180 / pi.  D <= 0 or a non-finite xi, eta: the row is
+ *   not in the field.  Inverse, with xi, eta in radians: den = cos dec0 - eta sin dec0, ra = ra0 + atan2(xi, den) brought into
+ *   [0, 360) (a - 360 floor(a / 360); 360 itself: 0), dec = atan2(sin dec0 + eta cos dec0, hypot(xi, den)).
+ * Rule 2, the virtual grid: (xi, eta) = CD0 (x - xc, y - yc), xc = (nx - 1) / 2, yc = (ny - 1) / 2, cd[4] = CD0 row-major in
+ *   deg / pix (HOST array; the caller forms it: (s / 3600) [[-p cos r, -sin r], [-p sin r, cos r]]).  The kernel inverts it in closed
+ *   form: x = xc + (cd[3] xi - cd[1] eta) / det, y = yc + (cd[0] eta - cd[2] xi) / det.
+ * Rule 3, list B: a row is eligible when it is in the field, its magnitude is finite, -margin <= x <= nx - 1 + margin and the same
+ *   in y, and its flux = (float) 10^(-0.4 ((double) mag - mag_zp)) is positive and finite.  Eligible: integer = floor(v + 0.5), offset
+ *   = (float)(v - integer) as (dy, dx), err = flux / 1000 (float32).  Else integers 0, offsets NaN, flux = err = 0: the row neither
+ *   votes in bbx_align_vote nor matches in bbx_match_mutual.  d_count[1] = the eligible rows (integer adds).
+ * d_sky[n][2] = (ra, dec) float64, d_mag[n] float32.  n == 0: d_count is cleared, nothing is launched.                        */
+int bbx_wcs_cat_list(bbx_ctx *ctx, int n, const double *d_sky, const float *d_mag, double ra0, double dec0, int ny, int nx,
+                     const double *cd, double margin, double mag_zp, int32_t *d_ys, int32_t *d_xs, float *d_off, float *d_flux,
+                     float *d_err, int32_t *d_count, void *stream);
+
+/* Rule 5, pixel to sky: the position (x, y), 0-based, of row i is d_pos[i] = (x, y) float64 where d_pos is given, else
+ * d_xs[i] + (double) d_off[i][1], d_ys[i] + (double) d_off[i][0] (d_off NULL: the integers).  (X, Y) = T(x, y) by bbx_align_grid's
+ * operations on d_coef[12] (DEVICE, bbx_align_fit's basis with the frame's ny, nx), (xi, eta) = CD0 (X - xc, Y - yc), then the
+ * inverse of rule 1 -> d_sky[n][2] = (ra, dec).  A position that is not finite gives NaN.  n == 0: nothing is launched.        */
+int bbx_wcs_pix2sky(bbx_ctx *ctx, int n, const double *d_pos, const int32_t *d_ys, const int32_t *d_xs, const float *d_off,
+                    const double *d_coef, int ny, int nx, const double *cd, double ra0, double dec0, double *d_sky, void *stream);
+
+/* Rule 6, residuals: over the items i of bbx_align_fit's d_items[n_items][2] with d_kept[i] set and both indices inside their
+ * lists: (ra, dec) of A's position by rule 5 against d_cat_sky[ib]: dra = (ra - ra_cat, brought into [-180, 180)) cos dec_cat,
+ * ddec = dec - dec_cat, both times 3600.  d_out[8] = {count, mean dra, std dra, mean ddec, std ddec, 0, 0, 0}, std =
+ * sqrt(sum (d - mean)^2 / count) (no pair: count 0, NaN).  One workgroup of 256: per thread over the items t, t + 256, ... in that
+ * order, the 256 partial sums added in thread order; the means first, then the deviations.  n_items == 0: nothing is launched and
+ * d_out is left as it is.                                                                                                    */
+int bbx_wcs_pair_stats(bbx_ctx *ctx, int n_items, const int32_t *d_items, const uint8_t *d_kept, int n_a, const int32_t *d_a_ys,
+                       const int32_t *d_a_xs, const float *d_a_off, int n_b, const double *d_cat_sky, const double *d_coef, int ny,
+                       int nx, const double *cd, double ra0, double dec0, double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
