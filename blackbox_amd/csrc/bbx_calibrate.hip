@@ -108,61 +108,64 @@ template <int RAW_T, bool NONLIN>
 __global__ __launch_bounds__(256) void k_calibrate_v4(calib_args a) {
     const bbx_dims& d = a.d;
     const int X = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (X >= d.nx) return;
-    const int ix = X / d.xsz, x = X - ix * d.xsz;
     const int Y0 = blockIdx.y * CAL_ROWS;
-    const int iy = Y0 / d.ysz;                                   // CAL_ROWS divides ysize_chan (checked by the host)
-    const int c = iy * 8 + ix;
-    const double os0 = a.oscan[c * d.xsz + x], os1 = a.oscan[c * d.xsz + x + 1],
-                 os2 = a.oscan[c * d.xsz + x + 2], os3 = a.oscan[c * d.xsz + x + 3];
-    const float g = a.gain.v[c], sat = a.sat.v[c];
     unsigned satbits = 0;                                        // bit 4*k + q: pixel q of row k is saturated
+    // (no early return for the lanes right of the frame: the queue reservation below is a scan over all 64 lanes of
+    // the wave, and the wave's total is read from lane 63)
+    if (X < d.nx) {
+        const int ix = X / d.xsz, x = X - ix * d.xsz;
+        const int iy = Y0 / d.ysz;                                   // CAL_ROWS divides ysize_chan (checked by the host)
+        const int c = iy * 8 + ix;
+        const double os0 = a.oscan[c * d.xsz + x], os1 = a.oscan[c * d.xsz + x + 1],
+                     os2 = a.oscan[c * d.xsz + x + 2], os3 = a.oscan[c * d.xsz + x + 3];
+        const float g = a.gain.v[c], sat = a.sat.v[c];
 #pragma unroll
-    for (int k = 0; k < CAL_ROWS; k++) {
-        const int Y = Y0 + k;
-        const int y = Y - iy * d.ysz;
-        const int rl = (iy == 0) ? y : (d.os_y + y);
-        const size_t ri = (size_t)(iy * d.dy + rl) * d.nx_raw + (size_t)ix * d.dx + x;
-        const size_t o = (size_t)Y * d.nx + X;
-        float r[4];
-        if (RAW_T == BBX_RAW_U16) {
-            const ushort4 u = *(const ushort4*)((const uint16_t*)a.raw + ri);
-            r[0] = u.x; r[1] = u.y; r[2] = u.z; r[3] = u.w;
-        } else {
-            const float4 f = *(const float4*)((const float*)a.raw + ri);
-            r[0] = f.x; r[1] = f.y; r[2] = f.z; r[3] = f.w;
-        }
-        const double vf = a.vfit[c * d.dy + rl];
-        float fl[4] = {1.f, 1.f, 1.f, 1.f}, bi[4] = {0.f, 0.f, 0.f, 0.f};
-        uint8_t m[4] = {0, 0, 0, 0};
-        // (CAL_NT: the masters and the raw frame stream through once, the outputs are written once: non-temporal, see
-        // tools/exp/tile_bw.hip -- plain stores of a read + write stream crowd the reads out of L2)
-        typedef float cv4 __attribute__((ext_vector_type(4)));
-        if (a.flat) { const cv4 t = CAL_NT ? __builtin_nontemporal_load((const cv4*)(a.flat + o)) : *(const cv4*)(a.flat + o); fl[0] = t.x; fl[1] = t.y; fl[2] = t.z; fl[3] = t.w; }
-        if (a.bias) { const cv4 t = CAL_NT ? __builtin_nontemporal_load((const cv4*)(a.bias + o)) : *(const cv4*)(a.bias + o); bi[0] = t.x; bi[1] = t.y; bi[2] = t.z; bi[3] = t.w; }
-        if (a.bpm) { const uchar4 t = *(const uchar4*)(a.bpm + o); m[0] = t.x; m[1] = t.y; m[2] = t.z; m[3] = t.w; }
-        const double os[4] = {os0, os1, os2, os3};
-        float ov[4];
+        for (int k = 0; k < CAL_ROWS; k++) {
+            const int Y = Y0 + k;
+            const int y = Y - iy * d.ysz;
+            const int rl = (iy == 0) ? y : (d.os_y + y);
+            const size_t ri = (size_t)(iy * d.dy + rl) * d.nx_raw + (size_t)ix * d.dx + x;
+            const size_t o = (size_t)Y * d.nx + X;
+            float r[4];
+            if (RAW_T == BBX_RAW_U16) {
+                const ushort4 u = *(const ushort4*)((const uint16_t*)a.raw + ri);
+                r[0] = u.x; r[1] = u.y; r[2] = u.z; r[3] = u.w;
+            } else {
+                const float4 f = *(const float4*)((const float*)a.raw + ri);
+                r[0] = f.x; r[1] = f.y; r[2] = f.z; r[3] = f.w;
+            }
+            const double vf = a.vfit[c * d.dy + rl];
+            float fl[4] = {1.f, 1.f, 1.f, 1.f}, bi[4] = {0.f, 0.f, 0.f, 0.f};
+            uint8_t m[4] = {0, 0, 0, 0};
+            // (CAL_NT: the masters and the raw frame stream through once, the outputs are written once: non-temporal, see
+            // tools/exp/tile_bw.hip -- plain stores of a read + write stream crowd the reads out of L2)
+            typedef float cv4 __attribute__((ext_vector_type(4)));
+            if (a.flat) { const cv4 t = CAL_NT ? __builtin_nontemporal_load((const cv4*)(a.flat + o)) : *(const cv4*)(a.flat + o); fl[0] = t.x; fl[1] = t.y; fl[2] = t.z; fl[3] = t.w; }
+            if (a.bias) { const cv4 t = CAL_NT ? __builtin_nontemporal_load((const cv4*)(a.bias + o)) : *(const cv4*)(a.bias + o); bi[0] = t.x; bi[1] = t.y; bi[2] = t.z; bi[3] = t.w; }
+            if (a.bpm) { const uchar4 t = *(const uchar4*)(a.bpm + o); m[0] = t.x; m[1] = t.y; m[2] = t.z; m[3] = t.w; }
+            const double os[4] = {os0, os1, os2, os3};
+            float ov[4];
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            float v = r[q];
-            if (RAW_T == BBX_RAW_F32 && !isfinite(v)) v = 0.f;
-            v = v * g;
-            v = (float)((double)v - vf);
-            v = (float)((double)v - os[q]);
-            if (NONLIN) v = nl_apply(a.nonlin, c, v, g);
-            if (a.bias) v = v - bi[q];
-            if (!isfinite(v)) { v = 0.f; if (m[q] == 0) m[q] |= BBX_MASK_BAD; }
-            if (v >= sat) { m[q] |= BBX_MASK_SAT; satbits |= 1u << (4 * k + q); }
-            if (a.flat) v = v / fl[q];
-            ov[q] = v;
-        }
-        if (CAL_NT) {
-            __builtin_nontemporal_store(cv4{ov[0], ov[1], ov[2], ov[3]}, (cv4*)(a.data + o));
-            __builtin_nontemporal_store((unsigned)m[0] | ((unsigned)m[1] << 8) | ((unsigned)m[2] << 16) | ((unsigned)m[3] << 24), (unsigned*)(a.mask + o));
-        } else {
-            *(float4*)(a.data + o) = make_float4(ov[0], ov[1], ov[2], ov[3]);
-            *(uchar4*)(a.mask + o) = make_uchar4(m[0], m[1], m[2], m[3]);
+            for (int q = 0; q < 4; q++) {
+                float v = r[q];
+                if (RAW_T == BBX_RAW_F32 && !isfinite(v)) v = 0.f;
+                v = v * g;
+                v = (float)((double)v - vf);
+                v = (float)((double)v - os[q]);
+                if (NONLIN) v = nl_apply(a.nonlin, c, v, g);
+                if (a.bias) v = v - bi[q];
+                if (!isfinite(v)) { v = 0.f; if (m[q] == 0) m[q] |= BBX_MASK_BAD; }
+                if (v >= sat) { m[q] |= BBX_MASK_SAT; satbits |= 1u << (4 * k + q); }
+                if (a.flat) v = v / fl[q];
+                ov[q] = v;
+            }
+            if (CAL_NT) {
+                __builtin_nontemporal_store(cv4{ov[0], ov[1], ov[2], ov[3]}, (cv4*)(a.data + o));
+                __builtin_nontemporal_store((unsigned)m[0] | ((unsigned)m[1] << 8) | ((unsigned)m[2] << 16) | ((unsigned)m[3] << 24), (unsigned*)(a.mask + o));
+            } else {
+                *(float4*)(a.data + o) = make_float4(ov[0], ov[1], ov[2], ov[3]);
+                *(uchar4*)(a.mask + o) = make_uchar4(m[0], m[1], m[2], m[3]);
+            }
         }
     }
     // saturated-pixel queue: one reservation per wave for all the rows of the block (a returning
