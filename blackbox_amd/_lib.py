@@ -285,6 +285,27 @@ def fetch(ctx, *tensors, check_device_errors=False):
     return out if len(out) > 1 else out[0]
 
 
+class Readback:
+    """A copy back whose parts have names: add(name, *tensors) any number of times, then ONE fetch over all tensors in the order
+    they were added -> {name: [arrays]} (a list under every name, for one tensor too)"""
+
+    def __init__(self):
+        self.parts = {}
+
+    def add(self, name, *tensors):
+        if name in self.parts:
+            raise ValueError('Readback: %r was added already' % (name,))
+        self.parts[name] = list(tensors)
+
+    def fetch(self, ctx, check_device_errors=False):
+        flat = [t for ts in self.parts.values() for t in ts]
+        if not flat:                                                 # nothing to copy: no library call, no host wait
+            return {name: [] for name in self.parts}
+        got = fetch(ctx, *flat, check_device_errors=check_device_errors)
+        got = iter(got if len(flat) > 1 else [got])
+        return {name: [next(got) for _ in ts] for name, ts in self.parts.items()}
+
+
 def f32x16(values):
     arr = (C.c_float * 16)(*[float(v) for v in values])
     return arr

@@ -145,6 +145,64 @@ def vet_transients(rows, chi2_max=None, fwhm_gauss_min=None, fwhm_gauss_max=None
     return [rows[i] for i in keep], keep
 
 
+# ---- the candidate table from the host copies of what the subtraction queued (numpy arrays and lists of dicts only: nothing
+# here touches the device)
+def candidate_rows(ys, xs, scorr, fe):
+    """the rows of the candidate table: the peaks of Scorr and (Fpsf, Fpsferr) = fe[0], fe[1] at them"""
+    return [dict(y=y, x=x, scorr=sc, fpsf=f, fpsferr=e)
+            for y, x, sc, f, e in zip(ys.tolist(), xs.tolist(), scorr.tolist(), fe[0].tolist(), fe[1].tolist())]
+
+
+def sky_columns(rows, sky):
+    """ra_peak, dec_peak from sky [n, 2] and, where the fitted positions' rows follow ([2n, 2]), ra_psf_d, dec_psf_d"""
+    n = len(rows)
+    for i, d in enumerate(rows):
+        d.update(ra_peak=float(sky[i, 0]), dec_peak=float(sky[i, 1]))
+        if len(sky) == 2 * n:
+            d.update(ra_psf_d=float(sky[n + i, 0]), dec_psf_d=float(sky[n + i, 1]))
+
+
+def pd_columns(rows, tf):
+    """the columns of the fit of P_D from its flat copy back: six planes of n (flux, error, dy, dx, chi2, flags), then the fold
+    of P_D per sub-image, which is returned"""
+    n = len(rows)
+    cols, fold = tf[:6 * n].reshape(6, n), tf[6 * n:]
+    for i, d in enumerate(rows):
+        d.update(y_psf_d=float(d['y'] + cols[2, i]), x_psf_d=float(d['x'] + cols[3, i]), flux_psf_d=float(cols[0, i]),
+                 fluxerr_psf_d=float(cols[1, i]), chi2_psf_d=float(cols[4, i]), flags_psf_d=int(cols[5, i]))
+    return fold
+
+
+def shapefit_columns(rows, ts):
+    """the sixteen Gauss / Moffat columns from the flat copy back of the shape fits: two models x seven planes of n (dy, dx, yerr,
+    xerr, fwhm, elongation, chi2), then two flag planes"""
+    n = len(rows)
+    planes, sfl = ts[:14 * n].reshape(2, 7, n), ts[14 * n:].reshape(2, n)
+    for m, name in enumerate(('gauss', 'moffat')):
+        for i, d in enumerate(rows):
+            d.update({'x_%s_d' % name: float(d['x'] + planes[m, 1, i]), 'xerr_%s_d' % name: float(planes[m, 3, i]),
+                      'y_%s_d' % name: float(d['y'] + planes[m, 0, i]), 'yerr_%s_d' % name: float(planes[m, 2, i]),
+                      'fwhm_%s_d' % name: float(planes[m, 4, i]), 'elong_%s_d' % name: float(planes[m, 5, i]),
+                      'chi2_%s_d' % name: float(planes[m, 6, i]), 'flags_%s_d' % name: int(sfl[m, i])})
+
+
+def drop_edge_rows(rows, edge_at):
+    """the rows with a reference under their peak (edge_at: the registered reference's edge bit per row) -> (kept rows, their indices)"""
+    keep = [i for i, v in enumerate(edge_at.tolist()) if not v]
+    return [rows[i] for i in keep], keep
+
+
+def vet_rows(rows, have_fit, have_shapes, chi2_max=None, fwhm_gauss_min=None, fwhm_gauss_max=None, elong_gauss_max=None):
+    """the vetting with the bounds that apply: the chi2 bound needs the fit of P_D, the Gauss bounds the shape fits -> (kept rows,
+    their indices); (rows, None) where no bound applies"""
+    bounds = dict(chi2_max=chi2_max if have_fit else None)
+    if have_shapes:
+        bounds.update(fwhm_gauss_min=fwhm_gauss_min, fwhm_gauss_max=fwhm_gauss_max, elong_gauss_max=elong_gauss_max)
+    if not any(v is not None for v in bounds.values()):
+        return rows, None
+    return vet_transients(rows, **{k: None if v is None else float(v) for k, v in bounds.items()})
+
+
 def thumbnail_stamps(ctx, res, frames, ys, xs, size, new_mask, ref_mask=None, floats=True, pngs=False, flag_win=None):
     """bbx_thumbnails (+ bbx_thumb_png8) at the integer positions (ys, xs) of the four frames (RED, REF, D, SCORR): puts
     'thumbnails' (device float32 [n, 4, size, size], when [floats]) and 'thumbnail_png8' (device uint8, same shape, when [pngs])

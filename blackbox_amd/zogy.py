@@ -8,6 +8,7 @@ SExtractor and the real-bogus CNN stay out of scope: PSF images and a WCS-aligne
 reference frame are inputs.
 """
 import ctypes as C                                    # noqa: F401  (zogy.C)
+import inspect
 import logging
 import os
 
@@ -16,12 +17,13 @@ import torch
 from scipy import ndimage                             # noqa: F401  (zogy.ndimage)
 
 from . import settings
-from ._lib import lib, check, fetch, push, ptr as _p, BBXError as _lib_BBXError, SplineImage as _SplineImage         # noqa: F401
+from ._lib import lib, check, fetch, push, ptr as _p, BBXError as _lib_BBXError, Readback, SplineImage as _SplineImage         # noqa: F401
 from ._lib import BBX_OPT_ZOGY_KSMALL_OFF          # noqa: F401  (k_n, k_r through the full grid: tests and timings compare the paths)
 from .catalogs import format_cat, transient_table         # noqa: F401  (zogy.format_cat)
 # The stages, one module each, in import order: a module imports only from those above it.  This module is the facade:
-# callers and tests reach every stage function as zogy.<name>, and _optimal_subtraction finds them in this module's globals
-# (a test that counts calls assigns zogy.<name>).  The lists are the index of the package.
+# callers and tests reach every stage function as zogy.<name>, and _optimal_subtraction's own stages, which live below it in
+# this file, find them in this module's globals at call time (a test that counts calls assigns zogy.<name>).  The lists are
+# the index of the package.
 from .zoom import (NPAD, SPLINE_POLE, MiniImage, _axis_map, _bspline_weights, _device_taps, _tap_tables,         # noqa: F401
                    device_zoom_coefficients, mini2back, remap_mini, zoom_coefficients, zoom_plan)
 from .background import (_objmask_counts, _objmask_stage, frame_clipped_stats, frame_clipped_stats_enqueue, get_back,         # noqa: F401
@@ -47,6 +49,7 @@ from .align import (ALIGN_CLIP, ALIGN_DET, ALIGN_FAR, ALIGN_FEW_PAIRS, ALIGN_NMI
                     ALIGN_VOTE_FAILED, RefStars, _expect_list, align_apply, align_fit, align_grid, align_grid_host, align_grid_shape,
                     align_header, align_reference, align_sort, align_vote, remap_mask)
 from . import astrometry as _ast                                     # (_optimal_subtraction's switch bears the module's name)
+from . import transients as _tr                                      # (the candidate table's host functions: _transient_rows)
 from .astrometry import AstCatalog, ast_header, frame_pointing, wcs_header, wcs_pix2sky         # noqa: F401
 from .fakestars import (FAKE_COLS, FAKE_MASKED, FAKE_NO_FLUX, FAKE_NO_PSF, FAKE_OFF_FRAME, FAKE_ON_SOURCE, FOUND_KEPT, FOUND_PEAK,         # noqa: F401
                         FOUND_ROW, check_apart, fake_header, fake_inject, fake_launch, fake_layout, fake_match, fake_prepare, fake_recover,
@@ -232,69 +235,122 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
                       columns
     -> dict(D, Scorr, Fpsf, Fpsferr, bkg_mini_new, bkg_std_mini_new, ..., transients, catalog,
             header (= header_new additions), header_trans)"""
-    size = subimage_size or settings.subimage_size
-    border = settings.subimage_border if subimage_border is None else subimage_border
-    box = bkg_boxsize or settings.bkg_boxsize
-    ny, nx = new.shape
-    L = size + 2 * border
-    res, hdr, hdr_t = {}, {}, {}
-    nsy, nsx = ny // size, nx // size
-    nsub = nsy * nsx
-    have_ref = ref is not None and trans_extract
-    build_here = bool(psf_build) and psf_new is None                 # the PSF of the new frame is made below, behind the peak search
-    have_psf = psf_new is not None or build_here
-    do_match = bool(match) and have_ref and have_psf and psf_ref is not None
-    do_shapes = bool(shapes) and bool(cat_extract) and have_psf
-    phot_centroid = bool(phot_centroid)
-    do_aper = bool(aper_phot) and bool(cat_extract) and have_psf
-    do_align = bool(ref_align) and have_ref
-    do_lim = bool(limmag)
-    do_ast = bool(astrometry)
-    ast_pending = ast_sol = None
-    if do_lim:
-        lim_nsigma, lim_frac = _limflux_parameters(limmag_nsigma, limmag_psf_frac)
-    if do_align and ref_grid is not None:
-        raise ValueError('ref_align=True makes the lattice itself: a ref_grid beside it is refused')
-    ref_mask_remapped = ref_grid_host = None                        # set by a registration that succeeded
+    c = _setup(dict(locals()))                                       # (the arguments, by name)
+    _new_frame_background(c)
+    _catalogue(c)
+    res = c.res
+    if not c.have_ref:
+        c.hdr['Z-P'] = (False, 'successfully processed by ZOGY?')
+        res['header'], res['header_new'], res['header_trans'], res['transients'] = _HeaderView(c.hdr, c.hdr_t), c.hdr, c.hdr_t, []
+        return res
+    if c.ref_side is None:
+        # the reference frame on the new frame's grid, where neither the star match nor the registration asked for it before
+        c.ref_side = _prepare_reference(c)
+    fk = _fake_stars(c)
+    scal, ms, frame_args = _subtract(c)
+    tys, txs, tsc, ntrans = _transient_search(c, frame_args)
+    got = _transient_readback(c, scal, fk, tys, txs)
+    _transient_rows(c, got, fk, tys, txs, tsc)
+    _closing_headers(c, scal, ms, got.get('stats'), ntrans)
+    return res
 
-    # ---- new frame: mesh, subtraction, sigma image, variance
+
+class _Call:
+    """The state of one _optimal_subtraction call, which its stage functions share: an attribute bag (a misspelt name raises)"""
+    __slots__ = tuple(inspect.signature(_optimal_subtraction).parameters) + (
+        # the arguments under their own names (psf_new, ref_grid and phot_centroid are rebound on the way), and their geometry
+        'ny', 'nx', 'size', 'border', 'box', 'L', 'nsy', 'nsx', 'nsub', 'bs',
+        # settings with their defaults filled in
+        'lim_nsigma', 'lim_frac', 'nsig', 'fit_size', 'shape_size',
+        # the switches: what the call was asked for and is able to do; a stage that fails clears those that rested on it
+        'have_ref', 'have_psf', 'build_here', 'do_match', 'do_shapes', 'do_aper', 'do_align', 'do_lim', 'do_ast', 'want_phot', 'want_cat',
+        'use_mini',
+        # what one stage makes and a later one reads or replaces
+        'mini_std', 'd_sstd', 'work', 'sdn', 'bstd', 'sub_pn', 'sub_pr', 'peaks_off', 'ref_grid_host', 'ref_mask_remapped', 'ref_side', 'own', 'scal_n',
+        'mtab', 'ast_pending', 'ast_sol',
+        # the result and the two headers
+        'res', 'hdr', 'hdr_t')
+
+
+def _setup(args):
+    """the call's state from _optimal_subtraction's arguments (by name), with the refusals that come before anything is queued"""
+    c = _Call()
+    for k, v in args.items():
+        setattr(c, k, v)
+    c.size = c.subimage_size or settings.subimage_size
+    c.border = settings.subimage_border if c.subimage_border is None else c.subimage_border
+    c.box = c.bkg_boxsize or settings.bkg_boxsize
+    c.ny, c.nx = c.new.shape
+    c.L = c.size + 2 * c.border
+    c.res, c.hdr, c.hdr_t = {}, {}, {}
+    c.nsy, c.nsx = c.ny // c.size, c.nx // c.size
+    c.nsub = c.nsy * c.nsx
+    c.bs = c.size // c.box if c.size % c.box == 0 else None
+    c.have_ref = c.ref is not None and c.trans_extract
+    c.build_here = bool(c.psf_build) and c.psf_new is None         # the PSF of the new frame is made behind the catalogue's peak search
+    c.have_psf = c.psf_new is not None or c.build_here
+    c.do_match = bool(c.match) and c.have_ref and c.have_psf and c.psf_ref is not None
+    c.do_shapes = bool(c.shapes) and bool(c.cat_extract) and c.have_psf
+    c.phot_centroid = bool(c.phot_centroid)
+    c.do_aper = bool(c.aper_phot) and bool(c.cat_extract) and c.have_psf
+    c.do_align = bool(c.ref_align) and c.have_ref
+    c.do_lim = bool(c.limmag)
+    c.do_ast = bool(c.astrometry)
+    c.want_phot = c.cat_extract or c.do_match or c.do_align or c.do_ast
+    c.want_cat = (c.want_phot or (c.build_here and c.have_ref)) and c.have_psf
+    c.nsig = settings.transient_nsigma if c.nsigma is None else c.nsigma
+    c.fit_size = int(settings.trans_fit_size if c.trans_fit_size is None else c.trans_fit_size)
+    c.shape_size = int(settings.trans_shape_size if c.trans_shape_size is None else c.trans_shape_size)
+    c.d_sstd = c.peaks_off = c.ref_side = c.scal_n = c.mtab = c.ast_pending = c.ast_sol = c.sub_pr = None
+    c.own = []
+    if c.do_lim:
+        c.lim_nsigma, c.lim_frac = _limflux_parameters(c.limmag_nsigma, c.limmag_psf_frac)
+    if c.do_align and c.ref_grid is not None:
+        raise ValueError('ref_align=True makes the lattice itself: a ref_grid beside it is refused')
+    c.ref_mask_remapped = c.ref_grid_host = None                    # set by a registration that succeeded
+    return c
+
+
+def _new_frame_background(c):
+    """the new frame: mesh, [object mask and second pass], subtraction, sigma image, the mini images on the host, the BKG keys"""
+    ctx, new, new_mask, box, res, hdr = c.ctx, c.new, c.new_mask, c.box, c.res, c.hdr
+    ny, nx = c.ny, c.nx
     mini, mini_std = get_back(ctx, new, new_mask, bkg_boxsize=box)
     work = torch.empty_like(new)
-    want_phot = cat_extract or do_match or do_align or do_ast
-    want_cat =(want_phot or (build_here and have_ref)) and have_psf
     second_pass = False
-    if objmask:
+    if c.objmask:
         # the first pass's frame (no candidate list: it is not the frame the catalogue is searched on), the object mask made of
         # it, and -- when the mask is usable -- the mesh once more without the masked pixels
         mini2back(ctx, mini, (ny, nx), bkg_boxsize=box, interp_Xchan=True, subtract_from=new, subtract_into=work)
-        om = _objmask_stage(ctx, new, new_mask, work, mini, mini_std, box, objmask_nsigma, objmask_minarea, objmask_grow, objmask_max_frac)
+        om = _objmask_stage(ctx, new, new_mask, work, mini, mini_std, box, c.objmask_nsigma, c.objmask_minarea, c.objmask_grow,
+                            c.objmask_max_frac)
         hdr.update(om['header'])
         if om['objmask'] is not None:
             second_pass = True
             mini, mini_std = om['mini'], om['mini_std']
             res['objmask'], res['bkg_mini_pass1'], res['bkg_std_mini_pass1'] = om['objmask'], om['bkg_mini_pass1'], om['bkg_std_mini_pass1']
-    if want_cat and (second_pass or not objmask):
+    if c.want_cat and (second_pass or not c.objmask):
         # the kernel that writes the background-subtracted frame lists the pixels above cat_nsigma x S-BKGSTD for the
         # catalogue's peak search; S-BKGSTD = median of the sigma mini image, taken on the device for that
         # (a frame that fell back to its first pass has that frame already: bbx_find_peaks makes its own pass)
-        d_sstd = torch.empty(1, dtype=torch.float32, device=ctx.device)
-        check(lib.bbx_mini_median(ctx.h, mini_std.numel(), _p(mini_std), _p(d_sstd), ctx.stream()), 'bbx_mini_median', ctx.h)
-        check(lib.bbx_zoom_candidates(ctx.h, _p(d_sstd), float(cat_nsigma)), 'bbx_zoom_candidates', ctx.h)
-    if second_pass or not objmask:
+        # (the call keeps the median: the peak search reads it on the device, to see that its threshold is the list's)
+        c.d_sstd = torch.empty(1, dtype=torch.float32, device=ctx.device)
+        check(lib.bbx_mini_median(ctx.h, mini_std.numel(), _p(mini_std), _p(c.d_sstd), ctx.stream()), 'bbx_mini_median', ctx.h)
+        check(lib.bbx_zoom_candidates(ctx.h, _p(c.d_sstd), float(c.cat_nsigma)), 'bbx_zoom_candidates', ctx.h)
+    if second_pass or not c.objmask:
         mini2back(ctx, mini, (ny, nx), bkg_boxsize=box, interp_Xchan=True, subtract_from=new, subtract_into=work)
     # the sigma image of the new frame: read off its mini image by the kernels that need it (catalogue photometry, the cut
     # into sub-images) where the geometry allows, a frame otherwise
-    use_mini = frame_path_supported(L) and not sigma_frames and not os.environ.get('BBX_SIGMA_FRAMES')     # (the switch: A/B timing)
+    c.use_mini = frame_path_supported(c.L) and not c.sigma_frames and not os.environ.get('BBX_SIGMA_FRAMES')     # (the switch: A/B timing)
     bstd = None
-    if use_mini:
+    if c.use_mini:
         try:
             bstd = MiniImage(ctx, mini_std, box, interp_Xchan=False)
-            use_mini = mini_path_supported((ny, nx), size, border, box, bstd)
+            c.use_mini = mini_path_supported((ny, nx), c.size, c.border, box, bstd)
         except ValueError:
-            use_mini = False
-    if not use_mini:
+            c.use_mini = False
+    if not c.use_mini:
         bstd = mini2back(ctx, mini_std, (ny, nx), bkg_boxsize=box, interp_Xchan=False)
-    Vn = None                                                        # variance image: only where a consumer needs it
     res['bkg_mini_new'], sdn = fetch(ctx, mini, mini_std)
     res['bkg_std_mini_new'] = sdn
     hdr['BKG-SIZE'] = (box, '[pix] background boxsize used')
@@ -304,469 +360,541 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     hdr['BKG-CORR'] = (False, 'channel background correction applied?')
     hdr['S-BKGSTD'] = (float(np.median(sdn)), '[e-] sigma (STD) background full-frame image')
     res['data_bkgsub'], res['bkg_std'] = work, bstd
-    bs = size // box if size % box == 0 else None
+    c.mini_std, c.work, c.sdn, c.bstd = mini_std, work, sdn, bstd
+    c.sub_pn = subimage_psfs(ctx, c.psf_new, c.nsy, c.nsx, c.size) if c.psf_new is not None else None
 
-    def tile_medians(a):
-        """median of the mini image over the boxes of each sub-image (or over all of it)"""
-        if bs and a.shape == (nsy * bs, nsx * bs):
-            return np.median(a.reshape(nsy, bs, nsx, bs).transpose(0, 2, 1, 3).reshape(nsub, bs * bs), axis=1)
-        if bs:
-            return np.asarray([np.median(a[(k // nsx) * bs:(k // nsx + 1) * bs, (k % nsx) * bs:(k % nsx + 1) * bs]) for k in range(nsub)])
-        return np.full(nsub, np.median(a))
-    scal_n = None
 
-    def host_side_meanwhile():
-        """host work that needs nothing from the device: done while a search runs there"""
-        hdr['S-BKG'] = (float(np.median(res['bkg_mini_new'])), '[e-] median background full-frame image')
-        return tile_medians(sdn) if have_ref else None
+def _tile_medians(c, a):
+    """median of the mini image over the boxes of each sub-image (or over all of it)"""
+    bs, nsy, nsx, nsub = c.bs, c.nsy, c.nsx, c.nsub
+    if bs and a.shape == (nsy * bs, nsx * bs):
+        return np.median(a.reshape(nsy, bs, nsx, bs).transpose(0, 2, 1, 3).reshape(nsub, bs * bs), axis=1)
+    if bs:
+        return np.asarray([np.median(a[(k // nsx) * bs:(k // nsx + 1) * bs, (k % nsx) * bs:(k % nsx + 1) * bs]) for k in range(nsub)])
+    return np.full(nsub, np.median(a))
 
-    sub_pn = subimage_psfs(ctx, psf_new, nsy, nsx, size) if psf_new is not None else None
 
-    own = []
+def _host_side_meanwhile(c):
+    """host work that needs nothing from the device: done while a search runs there"""
+    c.hdr['S-BKG'] = (float(np.median(c.res['bkg_mini_new'])), '[e-] median background full-frame image')
+    return _tile_medians(c, c.sdn) if c.have_ref else None
 
-    def reference_own_grid():
-        """the reference as it comes, on its own grid: background-subtracted image + sigma mini image (made once per call: the
-        registration measures its stars on it before prepare_reference brings it to the new frame)"""
-        if own:
-            return own[0]
-        rny, rnx = ref.shape
-        if ref_is_bkgsub:
-            rwork = ref
-            if ref_bkg_std_mini is None:
-                _, rstd_mini = get_back(ctx, ref, ref_mask, bkg_boxsize=box)
-                sdr = fetch(ctx, rstd_mini)
-            else:
-                sdr = np.asarray(ref_bkg_std_mini, np.float32)
+
+def _reference_own_grid(c):
+    """the reference as it comes, on its own grid: background-subtracted image + sigma mini image (made once per call: the
+    registration measures its stars on it before _prepare_reference brings it to the new frame)"""
+    if c.own:
+        return c.own[0]
+    ctx, ref, box, res = c.ctx, c.ref, c.box, c.res
+    rny, rnx = ref.shape
+    if c.ref_is_bkgsub:
+        rwork = ref
+        if c.ref_bkg_std_mini is None:
+            _, rstd_mini = get_back(ctx, ref, c.ref_mask, bkg_boxsize=box)
+            sdr = fetch(ctx, rstd_mini)
         else:
-            rmini, rstd_mini = get_back(ctx, ref, ref_mask, bkg_boxsize=box)
-            rwork = torch.empty_like(ref)
-            mini2back(ctx, rmini, (rny, rnx), bkg_boxsize=box, interp_Xchan=True, subtract_from=ref, subtract_into=rwork)
-            res['bkg_mini_ref'], sdr_meas = fetch(ctx, rmini, rstd_mini)
-            sdr = sdr_meas if ref_bkg_std_mini is None else np.asarray(ref_bkg_std_mini, np.float32)
-        res['bkg_std_mini_ref'] = sdr
-        own.append((rwork, sdr))
-        return own[0]
+            sdr = np.asarray(c.ref_bkg_std_mini, np.float32)
+    else:
+        rmini, rstd_mini = get_back(ctx, ref, c.ref_mask, bkg_boxsize=box)
+        rwork = torch.empty_like(ref)
+        mini2back(ctx, rmini, (rny, rnx), bkg_boxsize=box, interp_Xchan=True, subtract_from=ref, subtract_into=rwork)
+        res['bkg_mini_ref'], sdr_meas = fetch(ctx, rmini, rstd_mini)
+        sdr = sdr_meas if c.ref_bkg_std_mini is None else np.asarray(c.ref_bkg_std_mini, np.float32)
+    res['bkg_std_mini_ref'] = sdr
+    c.own.append((rwork, sdr))
+    return c.own[0]
 
-    def prepare_reference():
-        """the reference frame on the new frame's grid: background-subtracted image + sigma image (before the star match
-        where that is asked for, else where the subtraction needs it)"""
-        nonlocal bstd
-        rny, rnx = ref.shape
-        rwork, sdr = reference_own_grid()
-        if ref_grid is not None:
-            from . import coadd
-            ones = torch.ones_like(rwork)
-            rwork, _ = coadd.resample(ctx, rwork, ones, ref_grid, (ny, nx), 1.0, ref_grid_step)
-            # (a registration's lattice lives on the device: the mini image is remapped with its host twin)
-            sdr = remap_mini(sdr, ref_grid_host if ref_grid_host is not None else np.asarray(ref_grid), (rny, rnx), box, ref_grid_step,
-                             shape_out=(ny, nx))
-        elif (rny, rnx) != (ny, nx):
-            raise ValueError('reference frame of another shape needs ref_grid')
-        # co-added reference: no channel structure in its noise -> interpolation across the frame
-        # (a RefPsf of this psf_ref: its own stamp tensor, the one its spectra were made of -- the library knows them by pointer)
-        rpsf = ref_psf if ref_psf is not None and ref_psf.matches(psf_ref, (ny, nx), size, border) else None
-        sub_pr = rpsf.stamps if rpsf is not None else subimage_psfs(ctx, psf_ref, nsy, nsx, size)
-        frame_path = frame_path_supported(L) and sub_pn.shape[1] == sub_pr.shape[1]
-        if ref_bkg_std is not None and ref_grid is None and tuple(ref_bkg_std.shape) == (ny, nx) and isinstance(ref_bkg_std, MiniImage) == use_mini:
-            rbstd = ref_bkg_std
-        elif use_mini and frame_path:
-            rbstd = MiniImage(ctx, np.asarray(sdr, np.float32), box, interp_Xchan=True)
-            if not mini_path_supported((ny, nx), size, border, box, rbstd):
-                rbstd = rbstd.frame(ctx)
-        else:
-            rbstd = mini2back(ctx, sdr, (ny, nx), bkg_boxsize=box, interp_Xchan=True)
-        if isinstance(bstd, MiniImage) and not (frame_path and isinstance(rbstd, MiniImage)):
-            bstd = res['bkg_std'] = bstd.frame(ctx)                   # the other side needs frames: both as frames
-            if isinstance(rbstd, MiniImage):
-                rbstd = rbstd.frame(ctx)
-        res['ref_bkgsub'], res['bkg_std_ref'] = rwork, rbstd
-        hdr_t['S-BKGSTDR'] = (float(np.median(sdr)), '[e-] sigma (STD) background reference image')
-        return rwork, rbstd, sdr, sub_pr, frame_path
 
-    def register_reference(new_list):
-        """ref_align: the reference's star list on its own grid (the caller's RefStars of this very reference, else made
-        here), the registration against the new frame's list (ys, xs, off, flux, err on the device; None: the frame has none)
-        and, where it succeeds, the lattice in place of ref_grid and the remapped mask in place of ref_mask.  Where it fails the
-        frame goes on as one without a reference"""
-        nonlocal ref_grid, ref_grid_host, ref_mask_remapped, have_ref, do_match
-        al, why = None, None
-        try:
-            if new_list is None:
-                raise ValueError('the new frame has no source list (no PSF, or nothing above the threshold)')
-            if psf_ref is None:
-                raise ValueError('no PSF of the reference')
-            rs = ref_stars if ref_stars is not None and ref_stars.matches(ref) else None
-            if rs is None:
-                rwork_own, sdr_own = reference_own_grid()
-                rny, rnx = ref.shape
-                if isinstance(psf_ref, dict) or psf_ref.dim() == 2:
-                    r_nsy, r_nsx = max(1, rny // size), max(1, rnx // size)
-                else:                                                # stamps of the new frame's tiling: the clamped tile's plane
-                    r_nsy, r_nsx = nsy, nsx
-                stamps = subimage_psfs(ctx, psf_ref, r_nsy, r_nsx, size).contiguous()
-                sig_med = float(np.median(sdr_own))
-                try:
-                    sig = mini2back(ctx, sdr_own, (rny, rnx), bkg_boxsize=box, interp_Xchan=True)
-                except (ValueError, _lib_BBXError):                  # a reference that is no multiple of the box: one level
-                    sig = torch.full((rny, rnx), sig_med, dtype=torch.float32, device=ctx.device)
-                rs = RefStars(ctx, rwork_own, sig, ref_mask, stamps, r_nsy, r_nsx, size, cat_nsigma, sigma_median=sig_med,
-                              max_sources=max_sources, made_of=ref)
-            res['ref_stars'] = rs
-            al = align_reference(ctx, new_list, rs, (ny, nx), tuple(ref.shape), ref_mask, poldeg=align_poldeg, max_shift=align_max_shift,
-                                 bin=align_bin, dist=match_dist, snr_min=match_snr_min, step=ref_grid_step, rounds=align_rounds,
-                                 nbright=align_nbright)
-            if al['flags'] != 0:
-                why = 'flag word %d (vote %s)' % (al['flags'], np.asarray(al['fit']['info']).tolist())
-        except Exception as e:                                       # the frame goes on without its reference
-            al, why = None, str(e)
-        res['align'] = al
-        if why is None:
-            ref_grid, ref_grid_host, ref_mask_remapped = al['grid'], align_grid_host(al['coef'], (ny, nx), ref_grid_step), al['mask']
-            res['ref_mask_remapped'] = al['mask']
-            hdr_t.update(al['header'])
-            return True
-        logging.getLogger(__name__).warning('registration of the reference failed (%s): processing the new image only', why)
-        hdr_t.update(al['header'] if al is not None else align_header(None))
-        hdr_t['T-NOFFR'] = ('None', 'candidates dropped: no reference there')
-        hdr.update({k: v for k, v in hdr_t.items() if k.startswith('A-')})         # (no _trans products will carry them: the frame's own header does)
-        have_ref = do_match = False
-        return False
+def _prepare_reference(c):
+    """the reference frame on the new frame's grid: background-subtracted image + sigma image (before the star match
+    where that is asked for, else where the subtraction needs it) -> (image, sigma image, sigma mini image on the host, PSF stamps
+    of the sub-images, hand-written path?)"""
+    ctx, ref, box, res, size, border = c.ctx, c.ref, c.box, c.res, c.size, c.border
+    ny, nx = c.ny, c.nx
+    rny, rnx = ref.shape
+    rwork, sdr = _reference_own_grid(c)
+    if c.ref_grid is not None:
+        from . import coadd
+        ones = torch.ones_like(rwork)
+        rwork, _ = coadd.resample(ctx, rwork, ones, c.ref_grid, (ny, nx), 1.0, c.ref_grid_step)
+        # (a registration's lattice lives on the device: the mini image is remapped with its host twin)
+        sdr = remap_mini(sdr, c.ref_grid_host if c.ref_grid_host is not None else np.asarray(c.ref_grid), (rny, rnx), box, c.ref_grid_step,
+                         shape_out=(ny, nx))
+    elif (rny, rnx) != (ny, nx):
+        raise ValueError('reference frame of another shape needs ref_grid')
+    # co-added reference: no channel structure in its noise -> interpolation across the frame
+    # (a RefPsf of this psf_ref: its own stamp tensor, the one its spectra were made of -- the library knows them by pointer)
+    rpsf = c.ref_psf if c.ref_psf is not None and c.ref_psf.matches(c.psf_ref, (ny, nx), size, border) else None
+    sub_pr = rpsf.stamps if rpsf is not None else subimage_psfs(ctx, c.psf_ref, c.nsy, c.nsx, size)
+    frame_path = frame_path_supported(c.L) and c.sub_pn.shape[1] == sub_pr.shape[1]
+    ref_bkg_std = c.ref_bkg_std
+    if ref_bkg_std is not None and c.ref_grid is None and tuple(ref_bkg_std.shape) == (ny, nx) and isinstance(ref_bkg_std, MiniImage) == c.use_mini:
+        rbstd = ref_bkg_std
+    elif c.use_mini and frame_path:
+        rbstd = MiniImage(ctx, np.asarray(sdr, np.float32), box, interp_Xchan=True)
+        if not mini_path_supported((ny, nx), size, border, box, rbstd):
+            rbstd = rbstd.frame(ctx)
+    else:
+        rbstd = mini2back(ctx, sdr, (ny, nx), bkg_boxsize=box, interp_Xchan=True)
+    if isinstance(c.bstd, MiniImage) and not (frame_path and isinstance(rbstd, MiniImage)):
+        c.bstd = res['bkg_std'] = c.bstd.frame(ctx)                # the other side needs frames: both as frames
+        if isinstance(rbstd, MiniImage):
+            rbstd = rbstd.frame(ctx)
+    res['ref_bkgsub'], res['bkg_std_ref'] = rwork, rbstd
+    c.hdr_t['S-BKGSTDR'] = (float(np.median(sdr)), '[e-] sigma (STD) background reference image')
+    return rwork, rbstd, sdr, sub_pr, frame_path
 
-    def limflux_enqueue():
-        """the limiting-flux image and its frame statistic, queued on the frame's stream -> [statistic [8] float64, windows [nsub]
-        int32] on the device; None (and a warning) where the stage fails"""
-        try:
-            lim, win = _limflux_image(ctx, bstd, new_mask, sub_pn.contiguous(), size, nsy, nsx, nsigma=lim_nsigma, frac=lim_frac)
-            d_lst = frame_clipped_stats_enqueue(ctx, lim, new_mask)
-            res['limflux'] = lim
-            return [d_lst, win]
-        except Exception as ex:                                      # the frame goes on without the image
-            logging.getLogger(__name__).warning('limiting-flux image of the reduced frame failed: %s', ex)
-            res.pop('limflux', None)
-            return None
 
-    def limflux_finish(got):
-        """got: the host copies of limflux_enqueue's pair, or None"""
-        res['limflux_info'] = dict(stat=got[0] if got else None, win=got[1] if got else None, nsigma=lim_nsigma, frac=lim_frac)
-        hdr.update(limflux_header(got is not None, *(got or (None, None)), nsigma=lim_nsigma, frac=lim_frac))
+def _register_reference(c, new_list):
+    """ref_align: the reference's star list on its own grid (the caller's RefStars of this very reference, else made
+    here), the registration against the new frame's list (ys, xs, off, flux, err on the device; None: the frame has none)
+    and, where it succeeds, the lattice in place of ref_grid and the remapped mask in place of ref_mask.  Where it fails the
+    frame goes on as one without a reference"""
+    ctx, ref, psf_ref, size, box, res, hdr, hdr_t = c.ctx, c.ref, c.psf_ref, c.size, c.box, c.res, c.hdr, c.hdr_t
+    ny, nx = c.ny, c.nx
+    al, why = None, None
+    try:
+        if new_list is None:
+            raise ValueError('the new frame has no source list (no PSF, or nothing above the threshold)')
+        if psf_ref is None:
+            raise ValueError('no PSF of the reference')
+        rs = c.ref_stars if c.ref_stars is not None and c.ref_stars.matches(ref) else None
+        if rs is None:
+            rwork_own, sdr_own = _reference_own_grid(c)
+            rny, rnx = ref.shape
+            if isinstance(psf_ref, dict) or psf_ref.dim() == 2:
+                r_nsy, r_nsx = max(1, rny // size), max(1, rnx // size)
+            else:                                                # stamps of the new frame's tiling: the clamped tile's plane
+                r_nsy, r_nsx = c.nsy, c.nsx
+            stamps = subimage_psfs(ctx, psf_ref, r_nsy, r_nsx, size).contiguous()
+            sig_med = float(np.median(sdr_own))
+            try:
+                sig = mini2back(ctx, sdr_own, (rny, rnx), bkg_boxsize=box, interp_Xchan=True)
+            except (ValueError, _lib_BBXError):                  # a reference that is no multiple of the box: one level
+                sig = torch.full((rny, rnx), sig_med, dtype=torch.float32, device=ctx.device)
+            rs = RefStars(ctx, rwork_own, sig, c.ref_mask, stamps, r_nsy, r_nsx, size, c.cat_nsigma, sigma_median=sig_med,
+                          max_sources=c.max_sources, made_of=ref)
+        res['ref_stars'] = rs
+        al = align_reference(ctx, new_list, rs, (ny, nx), tuple(ref.shape), c.ref_mask, poldeg=c.align_poldeg, max_shift=c.align_max_shift,
+                             bin=c.align_bin, dist=c.match_dist, snr_min=c.match_snr_min, step=c.ref_grid_step, rounds=c.align_rounds,
+                             nbright=c.align_nbright)
+        if al['flags'] != 0:
+            why = 'flag word %d (vote %s)' % (al['flags'], np.asarray(al['fit']['info']).tolist())
+    except Exception as e:                                       # the frame goes on without its reference
+        al, why = None, str(e)
+    res['align'] = al
+    if why is None:
+        c.ref_grid, c.ref_grid_host, c.ref_mask_remapped = al['grid'], align_grid_host(al['coef'], (ny, nx), c.ref_grid_step), al['mask']
+        res['ref_mask_remapped'] = al['mask']
+        hdr_t.update(al['header'])
+        return True
+    logging.getLogger(__name__).warning('registration of the reference failed (%s): processing the new image only', why)
+    hdr_t.update(al['header'] if al is not None else align_header(None))
+    hdr_t['T-NOFFR'] = ('None', 'candidates dropped: no reference there')
+    hdr.update({k: v for k, v in hdr_t.items() if k.startswith('A-')})         # (no _trans products will carry them: the frame's own header does)
+    c.have_ref = c.do_match = False
+    return False
 
-    def astrometry_enqueue(new_list):
-        """astrometry: the solve of the frame's list (ys, xs, off, flux, err on the device) against the catalogue, queued -> what
-        astrometry.solve_finish wants; None (and a warning) where the stage fails before it is queued"""
-        try:
-            if ast_catalog is None:
-                raise ValueError('no catalogue (ast_catalog)')
-            return _ast.solve_enqueue(ctx, new_list, ast_catalog, ast_pointing, (ny, nx), pixscale=ast_pixscale, rot=ast_rot, parity=ast_parity,
-                                      max_shift=ast_max_shift, bin=ast_bin, poldeg=ast_poldeg, rounds=ast_rounds, dist=ast_dist,
-                                      snr_min=match_snr_min, mag_zp=ast_mag_zp)
-        except Exception as ex:                                      # the frame goes on without a solution
-            logging.getLogger(__name__).warning('astrometric solve failed: %s', ex)
-            return None
 
-    def astrometry_sky(**where):
-        """the sky positions of device positions by the frame's solution -> device float64 [n, 2]; None where that fails"""
-        p = ast_pending
-        try:
-            return _ast.pix2sky(ctx, p['coef'], p['shape'], p['cd'], p['pointing'], **where)
-        except Exception as ex:
-            logging.getLogger(__name__).warning('sky positions by the astrometric solution failed: %s', ex)
-            return None
+def _limflux_enqueue(c):
+    """the limiting-flux image and its frame statistic, queued on the frame's stream -> [statistic [8] float64, windows [nsub]
+    int32] on the device; None (and a warning) where the stage fails"""
+    try:
+        lim, win = _limflux_image(c.ctx, c.bstd, c.new_mask, c.sub_pn.contiguous(), c.size, c.nsy, c.nsx, nsigma=c.lim_nsigma, frac=c.lim_frac)
+        d_lst = frame_clipped_stats_enqueue(c.ctx, lim, c.new_mask)
+        c.res['limflux'] = lim
+        return [d_lst, win]
+    except Exception as ex:                                      # the frame goes on without the image
+        logging.getLogger(__name__).warning('limiting-flux image of the reduced frame failed: %s', ex)
+        c.res.pop('limflux', None)
+        return None
 
-    ref_side = None
-    # ---- full-source catalogue (a17): peaks of the background-subtracted frame above
-    # cat_nsigma x S-BKGSTD, PSF-weighted optimal flux at each (zogy.get_psfoptflux)
+
+def _limflux_finish(c, got):
+    """got: the host copies of _limflux_enqueue's pair, or None"""
+    c.res['limflux_info'] = dict(stat=got[0] if got else None, win=got[1] if got else None, nsigma=c.lim_nsigma, frac=c.lim_frac)
+    c.hdr.update(limflux_header(got is not None, *(got or (None, None)), nsigma=c.lim_nsigma, frac=c.lim_frac))
+
+
+def _astrometry_enqueue(c, new_list):
+    """astrometry: the solve of the frame's list (ys, xs, off, flux, err on the device) against the catalogue, queued -> what
+    astrometry.solve_finish wants; None (and a warning) where the stage fails before it is queued"""
+    try:
+        if c.ast_catalog is None:
+            raise ValueError('no catalogue (ast_catalog)')
+        return _ast.solve_enqueue(c.ctx, new_list, c.ast_catalog, c.ast_pointing, (c.ny, c.nx), pixscale=c.ast_pixscale, rot=c.ast_rot,
+                                  parity=c.ast_parity, max_shift=c.ast_max_shift, bin=c.ast_bin, poldeg=c.ast_poldeg, rounds=c.ast_rounds,
+                                  dist=c.ast_dist, snr_min=c.match_snr_min, mag_zp=c.ast_mag_zp)
+    except Exception as ex:                                      # the frame goes on without a solution
+        logging.getLogger(__name__).warning('astrometric solve failed: %s', ex)
+        return None
+
+
+def _astrometry_sky(c, **where):
+    """the sky positions of device positions by the frame's solution -> device float64 [n, 2]; None where that fails"""
+    p = c.ast_pending
+    try:
+        return _ast.pix2sky(c.ctx, p['coef'], p['shape'], p['cd'], p['pointing'], **where)
+    except Exception as ex:
+        logging.getLogger(__name__).warning('sky positions by the astrometric solution failed: %s', ex)
+        return None
+
+
+def _catalogue(c):
+    """full-source catalogue (a17): peaks of the background-subtracted frame above cat_nsigma x S-BKGSTD, PSF-weighted optimal
+    flux at each (zogy.get_psfoptflux), what is queued behind the photometry and read in its copy back, and the ends of the
+    frames on which no list was formed"""
+    res, hdr = c.res, c.hdr
     res['catalog'] = None
-    mtab = None
-    if want_cat:
-        thr = float(cat_nsigma) * hdr['S-BKGSTD'][0]
-        if np.isfinite(thr) and thr > 0:
-            pending = find_peaks_enqueue(ctx, work, thr, max_out=max_sources)
-            if do_match and not build_here and not do_align:         # (a reference to be registered is prepared behind the photometry)
-                ref_side = prepare_reference()                       # (behind the search: its zoom would drop the candidate list)
-            scal_n = host_side_meanwhile()
-            ys, xs, pk = find_peaks_collect(ctx, pending)
-        else:                                                        # no usable noise level: nothing is significant
-            lib.bbx_zoom_candidates(ctx.h, None, 0.0)
-            if do_match and not build_here and not do_align:
-                ref_side = prepare_reference()
-            scal_n = host_side_meanwhile()
-            ys = xs = np.zeros(0, np.int32); pk = np.zeros(0, np.float32)
-        keep = pk > 0
-        ys, xs, pk = ys[keep], xs[keep], pk[keep]
-        if build_here:
-            # the model from this very list of peaks; from here on the frame is one whose PSF was given
-            res['psf'] = build_psf(ctx, work, mini_std, new_mask, size, nsy, nsx, cat_nsigma, sigma_median=hdr['S-BKGSTD'][0],
-                                   peaks=(ys, xs, pk), psf_size=psf_size, poldeg=psf_poldeg, max_sources=max_sources)
-            hdr.update(res['psf']['header'])
-            psf_new = res['psf']['model']
-            if psf_new is not None:
-                sub_pn = subimage_psfs(ctx, psf_new, nsy, nsx, size)
-                if do_match and not do_align:
-                    ref_side = prepare_reference()
-            else:                                                    # no model: the frame of today without --psf_new
-                want_phot = do_match = do_shapes = do_aper = have_ref = False
-    if want_phot and sub_pn is not None:
-        if ys.size:
-            # peaks on masked pixels are dropped; their mask values come back with the fluxes (one host wait: the photometry
-            # of the few masked ones is made and thrown away)
-            d_ys, d_xs = push(ctx, ys.astype(np.int64), xs.astype(np.int64))
-            d_mk = new_mask[d_ys, d_xs]
-            peaks_off = None
-            if phot_centroid or do_shapes or do_align or do_aper or do_ast:
-                # the windowed centroids once: for the photometry (phot_centroid), the shapes, the apertures, the registration, the
-                # astrometric solve and the star match
-                d_y32, d_x32 = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
-                sigw = window_sigma(sub_pn)
-            if phot_centroid:
-                peaks_off = (d_y32, d_x32, win_centroid(ctx, work, d_y32, d_x32, sigw, size, nsy, nsx))
-                f, e, d_pfl = psf_optflux_centroid(ctx, work, bstd, psf_new, sub_pn, ys, xs, peaks_off[2], new_mask, nsx, size, d_peaks=(d_y32, d_x32))
-            else:
-                stamps = source_psfs(ctx, psf_new, sub_pn, ys, xs, nsx, size)
-                f, e = psf_optflux(ctx, work, bstd, stamps, ys, xs, v_is_sigma=True)        # (bstd: frame or MiniImage)
-            if do_align or do_ast:
-                # the new frame's list as the star match sees it (a peak on a masked pixel: no offset, no flux)
-                if peaks_off is None:
-                    peaks_off = (d_y32, d_x32, win_centroid(ctx, work, d_y32, d_x32, sigw, size, nsy, nsx))
-                bad = d_mk != 0
-                a_off = torch.where(bad[:, None], torch.full_like(peaks_off[2], float('nan')), peaks_off[2]).contiguous()
-                new_list = (d_y32, d_x32, a_off, torch.where(bad, torch.zeros_like(f), f).contiguous(), e)
-            if do_align:
-                # the registration, then the reference on this frame's grid -- before anything below asks for it
-                if register_reference(new_list):
-                    ref_side = prepare_reference()
-            if do_ast:
-                ast_pending = astrometry_enqueue(new_list)           # queued: read back with the photometry
-            back = [d_mk, f, e]
-            if do_shapes:
-                # the moments and their statistics are queued behind the photometry and come back with it
-                if peaks_off is None:
-                    peaks_off = (d_y32, d_x32, win_centroid(ctx, work, d_y32, d_x32, sigw, size, nsy, nsx))
-                d_shp, d_sfl = src_shapes(ctx, work, new_mask, d_y32, d_x32, peaks_off[2], sigw, size, nsy, nsx)
-                d_stab = shape_stats(ctx, d_y32, d_x32, d_shp, d_sfl, f, e, size, nsy, nsx, shape_snr_min)
-            if do_match:
-                # the star match rides on the same copy back: centroids, match against the reference's catalogue (the run's,
-                # or made here) and the table of clipped statistics are queued behind the photometry
-                rc = ref_catalog if ref_catalog is not None and ref_catalog.matches(ref_side[0], ref_side[1], size, border, phot_centroid) else \
-                    RefCatalog(ctx, ref_side[0], ref_side[1], ref_mask if ref_grid is None else ref_mask_remapped, psf_ref, size, border,
-                               cat_nsigma=cat_nsigma, sigma_median=hdr_t['S-BKGSTDR'][0], sub_psfs=ref_side[3], max_sources=max_sources,
-                               phot_centroid=phot_centroid)
-                back += match_enqueue(ctx, work, ys, xs, d_mk, f, e, sub_pn, rc, size, nsy, nsx, match_dist, match_snr_min,
-                                      peaks_off=peaks_off)
-            d_aper = None
-            if do_aper:
-                # the apertures and the annulus are queued behind the photometry and come back with it, the frame's FWHM too
-                try:
-                    if peaks_off is None:
-                        peaks_off = (d_y32, d_x32, win_centroid(ctx, work, d_y32, d_x32, sigw, size, nsy, nsx))
-                    d_afw = aper_fwhm(sub_pn)
-                    d_aper = _aper_phot(ctx, work, bstd, new_mask, d_y32, d_x32, peaks_off[2], d_afw.expand(nsub).contiguous(), size, nsy, nsx,
-                                        radii=apphot_radii, sky_inout=apphot_sky_inout, sub_sky=apphot_local_sky)
-                except Exception as ex:                              # the frame keeps today's catalogue
-                    logging.getLogger(__name__).warning('aperture photometry of the catalogue failed: %s', ex)
-                    d_aper = None
-            if do_shapes:
-                back += [d_shp, d_sfl, d_stab]
-            if phot_centroid:
-                back += [peaks_off[2], d_pfl]
-            if d_aper is not None:
-                back += list(d_aper) + [d_afw]
-            d_lim = limflux_enqueue() if do_lim else None            # behind the photometry, in the same copy back
-            if d_lim is not None:
-                back += d_lim
-            d_csky = None
-            if ast_pending is not None:
-                # the solution's six small tensors, and the sky positions of the catalogue's rows at the float32 positions X_POS /
-                # Y_POS will state (formed here as below: shapes', else the photometry's centroids, else the peaks), in the same copy back
-                if cat_extract:
-                    if do_shapes:
-                        o32 = torch.where(torch.isnan(d_shp[:, :2]), torch.zeros_like(d_shp[:, :2]), d_shp[:, :2])
-                    elif phot_centroid:
-                        o32 = torch.where(((d_pfl & PHOT_NO_CENTROID) == 0)[:, None], peaks_off[2], torch.zeros_like(peaks_off[2]))
-                    else:
-                        o32 = torch.zeros((int(ys.size), 2), dtype=torch.float32, device=ctx.device)
-                    p32 = (torch.stack([d_x32, d_y32], dim=1).to(torch.float32) + 1.0) + o32.flip(1)
-                    d_csky = astrometry_sky(pos=(p32.to(torch.float64) - 1.0).contiguous())
-                back += ast_pending['back'] + ([d_csky] if d_csky is not None else [])
-            got = fetch(ctx, *back)
-            if ast_pending is not None:
-                csky = got.pop() if d_csky is not None else None     # (the last seven: the rows' sky positions, the solution)
-                ast_sol = _ast.solve_finish(ast_pending, [got.pop() for _ in range(6)][::-1])
-            if do_lim:
-                limflux_finish([got.pop() for _ in range(2)][::-1] if d_lim is not None else None)     # (the last two: statistic, windows)
-            aper = [got.pop() for _ in range(5)][::-1] if d_aper is not None else None      # (the last five: flux, err, sky, flags, FWHM)
-            mk, f, e = got[:3]
-            if do_match:
-                mtab, npairs = got[3:5]
-                res['ref_catalog'] = rc
-                res['match'] = dict(n_new=int((mk == 0).sum()), n_ref=rc.n, n_pairs=int(npairs[0]))
-            ok = mk == 0
-            ys, xs, pk, f, e = ys[ok], xs[ok], pk[ok], f[ok], e[ok]
-            if phot_centroid:
-                pfl, poff = got.pop()[ok], got.pop()[ok]              # (the last two: the flags, then the offsets)
-            if do_shapes:
-                shp, sfl, stab = got[-3][ok], got[-2][ok], got[-1]
-            if aper is not None:
-                aper = [a[ok] for a in aper[:4]] + [float(aper[4][0])]
-        else:
-            if do_align:
-                register_reference(None)
-            f = e = np.zeros(0, np.float32)
-            shp, sfl, stab = np.zeros((0, 8), np.float32), np.zeros(0, np.uint8), empty_shape_table(nsub)
-            poff, pfl = np.zeros((0, 2), np.float32), np.zeros(0, np.uint8)
-            aper = None
-            if do_aper:
-                try:
-                    na = len(_aper_radii(apphot_radii))
-                    aper = [np.zeros((0, na), np.float32), np.zeros((0, na), np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.uint8),
-                            float(fetch(ctx, aper_fwhm(sub_pn))[0])]
-                except Exception as ex:
-                    logging.getLogger(__name__).warning('aperture photometry of the catalogue failed: %s', ex)
-        if cat_extract:
-            peaks = ys
-            res['catalog'] = dict(Y_POS=ys.astype(np.float32) + 1, X_POS=xs.astype(np.float32) + 1,
-                                  E_FLUX_PEAK=pk.astype(np.float32), E_FLUX_OPT=f, E_FLUXERR_OPT=e,
-                                  SNR_OPT=np.where(e > 0, f / np.where(e > 0, e, 1), 0).astype(np.float32))
-            hdr['NOBJECTS'] = (len(peaks), 'number of objects detected')
-            if phot_centroid:
-                # positions as shape_columns forms them: peak + 1 + offset, the integer peak where there is no centroid
-                cen = ((pfl & PHOT_NO_CENTROID) == 0)[:, None]
-                o = np.where(cen, poff, np.float32(0)).astype(np.float32)
-                res['catalog'].update(Y_POS=(ys.astype(np.float32) + np.float32(1)) + o[:, 0], X_POS=(xs.astype(np.float32) + np.float32(1)) + o[:, 1],
-                                      FLAGS_OPT=pfl.astype(np.uint8))
-        if phot_centroid:
-            hdr['PHOT-CEN'] = (True, 'PSF placed on the centroids in the catalogue photometry?')
-        if do_shapes:
-            res['catalog'].update(shape_columns(ys, xs, shp, sfl))
-            res['shapes'] = dict(table=stab, n_good=int(stab[nsub, _SC['n_fwhm']]))
-            hdr.update(shape_header(stab, len(ys), settings.shape_nmin, settings.pixscale))
-        if do_aper and aper is not None:
-            cat = res['catalog']
-            acols = aper_columns(*aper, radii=apphot_radii)
-            hdr.update(aper_header(True, aper[4], apphot_radii, apphot_sky_inout, apphot_local_sky, acols, cat['E_FLUX_OPT'], cat['SNR_OPT']))
-            cat.update(acols)
-            res['aper'] = dict(fwhm=aper[4], radii=_aper_radii(apphot_radii), n_good=hdr['AP-NSTAR'][0])
-        elif do_aper:
-            hdr.update(aper_header(False))
-        if ast_sol is not None:
-            res['astrometry'] = ast_sol
-            hdr.update(ast_sol['header'])
-            if ast_sol['ok'] and cat_extract and csky is not None:
-                res['catalog'].update(RA=csky[ok, 0].copy(), DEC=csky[ok, 1].copy())
-            elif not ast_sol['ok']:
-                logging.getLogger(__name__).warning('astrometric solve failed: flag word %d (vote %s)', ast_sol['flags'],
-                                                    np.asarray(ast_sol['fit']['info']).tolist())
-    if do_ast and 'astrometry' not in res:
+    if c.want_cat:
+        ys, xs, pk = _catalogue_peaks(c)
+    if c.want_phot and c.sub_pn is not None:
+        _catalogue_photometry(c, ys, xs, pk)
+    if c.do_ast and 'astrometry' not in res:
         # no list was formed (no PSF of the new frame, nothing above the threshold) or the stage failed before it was queued
         res['astrometry'] = None
         hdr.update(ast_header(None))
-    if do_lim and 'limflux_info' not in res:
+    if c.do_lim and 'limflux_info' not in res:
         # no photometry was read back (no catalogue asked for, no PSF, or nothing above the threshold): a copy back of its own
-        d_lim = limflux_enqueue() if sub_pn is not None else None
-        limflux_finish(fetch(ctx, *d_lim) if d_lim is not None else None)
+        rb = Readback()
+        d_lim = _limflux_enqueue(c) if c.sub_pn is not None else None
+        if d_lim is not None:
+            rb.add('lim', *d_lim)
+        _limflux_finish(c, rb.fetch(c.ctx).get('lim'))
     if 'S-BKG' not in hdr:
-        scal_n = host_side_meanwhile()
-    if do_align and have_ref and 'align' not in res:
-        register_reference(None)                                     # (no photometry ran: no PSF of the new frame)
-    if not have_ref:
-        hdr['Z-P'] = (False, 'successfully processed by ZOGY?')
-        res['header'], res['header_new'], res['header_trans'], res['transients'] = _HeaderView(hdr, hdr_t), hdr, hdr_t, []
-        return res
+        c.scal_n = _host_side_meanwhile(c)
+    if c.do_align and c.have_ref and 'align' not in res:
+        _register_reference(c, None)                                 # (no photometry ran: no PSF of the new frame)
 
-    # ---- reference frame on the new frame's grid: background-subtracted image + sigma image
-    rwork, rbstd, sdr, sub_pr, frame_path = ref_side if ref_side is not None else prepare_reference()
 
-    # ---- fake stars: planted in the frame that is about to be cut, behind everything that reads the frame as it was observed
-    fk = None
-    if fake_stars and int(fake_stars) > 0:
-        fk_noise = settings.fakestar_noise if fake_noise is None else bool(fake_noise)
-        fk_radius = int(settings.fakestar_radius if fake_radius is None else fake_radius)
-        fk_prep = None
+def _catalogue_peaks(c):
+    """the peak search of the catalogue, with the host's work and the match-only preparation of the reference behind its launch,
+    and the PSF build from these very peaks -> ys, xs, pk on the host"""
+    ctx, res, hdr = c.ctx, c.res, c.hdr
+    thr = float(c.cat_nsigma) * hdr['S-BKGSTD'][0]
+    if np.isfinite(thr) and thr > 0:
+        pending = find_peaks_enqueue(ctx, c.work, thr, max_out=c.max_sources)
+        if c.do_match and not c.build_here and not c.do_align:       # (a reference to be registered is prepared behind the photometry)
+            c.ref_side = _prepare_reference(c)                       # (behind the search: its zoom would drop the candidate list)
+        c.scal_n = _host_side_meanwhile(c)
+        ys, xs, pk = find_peaks_collect(ctx, pending)
+    else:                                                            # no usable noise level: nothing is significant
+        lib.bbx_zoom_candidates(ctx.h, None, 0.0)
+        if c.do_match and not c.build_here and not c.do_align:
+            c.ref_side = _prepare_reference(c)
+        c.scal_n = _host_side_meanwhile(c)
+        ys = xs = np.zeros(0, np.int32); pk = np.zeros(0, np.float32)
+    keep = pk > 0
+    ys, xs, pk = ys[keep], xs[keep], pk[keep]
+    if c.build_here:
+        # the model from this very list of peaks; from here on the frame is one whose PSF was given
+        res['psf'] = build_psf(ctx, c.work, c.mini_std, c.new_mask, c.size, c.nsy, c.nsx, c.cat_nsigma, sigma_median=hdr['S-BKGSTD'][0],
+                               peaks=(ys, xs, pk), psf_size=c.psf_size, poldeg=c.psf_poldeg, max_sources=c.max_sources)
+        hdr.update(res['psf']['header'])
+        c.psf_new = res['psf']['model']
+        if c.psf_new is not None:
+            c.sub_pn = subimage_psfs(ctx, c.psf_new, c.nsy, c.nsx, c.size)
+            if c.do_match and not c.do_align:
+                c.ref_side = _prepare_reference(c)
+        else:                                                        # no model: the frame of today without --psf_new
+            c.want_phot = c.do_match = c.do_shapes = c.do_aper = c.have_ref = False
+    return ys, xs, pk
+
+
+def _centroids(c, d_y32, d_x32, sigw):
+    """the windowed centroids of the catalogue's peaks, taken on first use and once: for the photometry (phot_centroid), the shapes,
+    the apertures, the registration, the astrometric solve and the star match"""
+    if c.peaks_off is None:
+        c.peaks_off = (d_y32, d_x32, win_centroid(c.ctx, c.work, d_y32, d_x32, sigw, c.size, c.nsy, c.nsx))
+    return c.peaks_off[2]
+
+
+def _catalogue_photometry(c, ys, xs, pk):
+    """the photometry of the peaks with everything that rides its copy back, and the catalogue's columns and header keys"""
+    if ys.size:
+        rb, rc = _catalogue_enqueue(c, ys, xs)
+        m = _catalogue_measured(c, rb.fetch(c.ctx), rc)
+        ok = m['ok']
+        ys, xs, pk = ys[ok], xs[ok], pk[ok]
+    else:
+        m = _catalogue_of_no_peaks(c)
+    _catalogue_table(c, ys, xs, pk, m)
+
+
+def _catalogue_enqueue(c, ys, xs):
+    """queued on the frame's stream: the photometry at the peaks and, behind it, the registration, the astrometric solve, the
+    shapes, the star match, the apertures, the limiting-flux image -> the copy back of all of them, the reference's catalogue"""
+    ctx, new_mask, size, nsy, nsx = c.ctx, c.new_mask, c.size, c.nsy, c.nsx
+    # peaks on masked pixels are dropped; their mask values come back with the fluxes (one host wait: the photometry
+    # of the few masked ones is made and thrown away)
+    d_ys, d_xs = push(ctx, ys.astype(np.int64), xs.astype(np.int64))
+    d_mk = new_mask[d_ys, d_xs]
+    if c.phot_centroid or c.do_shapes or c.do_align or c.do_aper or c.do_ast:
+        # what _centroids wants: the peaks as int32 and the window
+        d_y32, d_x32 = push(ctx, ys.astype(np.int32), xs.astype(np.int32))
+        sigw = window_sigma(c.sub_pn)
+    if c.phot_centroid:
+        f, e, d_pfl = psf_optflux_centroid(ctx, c.work, c.bstd, c.psf_new, c.sub_pn, ys, xs, _centroids(c, d_y32, d_x32, sigw), new_mask, nsx,
+                                           size, d_peaks=(d_y32, d_x32))
+    else:
+        stamps = source_psfs(ctx, c.psf_new, c.sub_pn, ys, xs, nsx, size)
+        f, e = psf_optflux(ctx, c.work, c.bstd, stamps, ys, xs, v_is_sigma=True)        # (bstd: frame or MiniImage)
+    if c.do_align or c.do_ast:
+        # the new frame's list as the star match sees it (a peak on a masked pixel: no offset, no flux)
+        off = _centroids(c, d_y32, d_x32, sigw)
+        bad = d_mk != 0
+        a_off = torch.where(bad[:, None], torch.full_like(off, float('nan')), off).contiguous()
+        new_list = (d_y32, d_x32, a_off, torch.where(bad, torch.zeros_like(f), f).contiguous(), e)
+    if c.do_align:
+        # the registration, then the reference on this frame's grid -- before anything below asks for it
+        if _register_reference(c, new_list):
+            c.ref_side = _prepare_reference(c)
+    if c.do_ast:
+        c.ast_pending = _astrometry_enqueue(c, new_list)             # queued: read back with the photometry
+    rb = Readback()
+    rb.add('phot', d_mk, f, e)
+    if c.do_shapes:
+        # the moments and their statistics are queued behind the photometry and come back with it
+        d_shp, d_sfl = src_shapes(ctx, c.work, new_mask, d_y32, d_x32, _centroids(c, d_y32, d_x32, sigw), sigw, size, nsy, nsx)
+        d_stab = shape_stats(ctx, d_y32, d_x32, d_shp, d_sfl, f, e, size, nsy, nsx, c.shape_snr_min)
+    rc = None
+    if c.do_match:
+        # the star match rides on the same copy back: centroids, match against the reference's catalogue (the run's,
+        # or made here) and the table of clipped statistics are queued behind the photometry
+        rwork, rbstd, _, sub_pr, _ = c.ref_side
+        rc = c.ref_catalog if c.ref_catalog is not None and c.ref_catalog.matches(rwork, rbstd, size, c.border, c.phot_centroid) else \
+            RefCatalog(ctx, rwork, rbstd, c.ref_mask if c.ref_grid is None else c.ref_mask_remapped, c.psf_ref, size, c.border,
+                       cat_nsigma=c.cat_nsigma, sigma_median=c.hdr_t['S-BKGSTDR'][0], sub_psfs=sub_pr, max_sources=c.max_sources,
+                       phot_centroid=c.phot_centroid)
+        rb.add('match', *match_enqueue(ctx, c.work, ys, xs, d_mk, f, e, c.sub_pn, rc, size, nsy, nsx, c.match_dist, c.match_snr_min,
+                                       peaks_off=c.peaks_off))
+    d_aper = None
+    if c.do_aper:
+        # the apertures and the annulus are queued behind the photometry and come back with it, the frame's FWHM too
         try:
-            # everything that can fail before the frame is touched (fake_prepare): an exception leaves the frame as it is
-            if sub_pn is None:
-                raise ValueError('no PSF stamps of the new frame')
-            if not 0 <= fk_radius <= 4:
-                raise ValueError('fake_radius: 0 .. 4 pixels expected')
-            lay = fake_layout(ny, nx, size, nsy, nsx, int(sub_pn.shape[1]), int(fake_stars), settings.fakestar_s2n if fake_s2n is None else fake_s2n,
-                              settings.fakestar_seed if fake_seed is None else fake_seed)
-            fk_prep = fake_prepare(ctx, work, rwork, bstd, new_mask, ref_mask if ref_grid is None else ref_mask_remapped, psf_new, sub_pn,
-                                   lay, nsx, size, clear_half=settings.fake_clear_half,
-                                   clear_nsigma=settings.fake_clear_nsigma if fake_clear_nsigma is None else fake_clear_nsigma,
-                                   noise=fk_noise, seed=lay['seed'])
-        except Exception as ex:
-            logging.getLogger(__name__).warning('fake stars were not injected: %s', ex)
-            hdr_t.update(fake_header(False))
-        if fk_prep is not None:
-            # the launch itself is not survived: a frame that may carry stars is never subtracted under T-FKP False
-            fk_inj, fk_peaks = _fake_launch(ctx, fk_prep)
-            fk = dict(layout=lay)
-            del fk_prep
+            off = _centroids(c, d_y32, d_x32, sigw)
+            d_afw = aper_fwhm(c.sub_pn)
+            d_aper = _aper_phot(ctx, c.work, c.bstd, new_mask, d_y32, d_x32, off, d_afw.expand(c.nsub).contiguous(), size, nsy, nsx,
+                                radii=c.apphot_radii, sky_inout=c.apphot_sky_inout, sub_sky=c.apphot_local_sky)
+        except Exception as ex:                                  # the frame keeps today's catalogue
+            logging.getLogger(__name__).warning('aperture photometry of the catalogue failed: %s', ex)
+            d_aper = None
+    if c.do_shapes:
+        rb.add('shapes', d_shp, d_sfl, d_stab)
+    if c.phot_centroid:
+        rb.add('centroid', c.peaks_off[2], d_pfl)
+    if d_aper is not None:
+        rb.add('aper', *d_aper, d_afw)                               # (flux, err, sky, flags, FWHM)
+    d_lim = _limflux_enqueue(c) if c.do_lim else None                # behind the photometry, in the same copy back
+    if d_lim is not None:
+        rb.add('lim', *d_lim)
+    if c.ast_pending is not None:
+        # the solution's six small tensors, and the sky positions of the catalogue's rows at the float32 positions X_POS /
+        # Y_POS will state (formed here as below: shapes', else the photometry's centroids, else the peaks), in the same copy back
+        d_csky = None
+        if c.cat_extract:
+            if c.do_shapes:
+                o32 = torch.where(torch.isnan(d_shp[:, :2]), torch.zeros_like(d_shp[:, :2]), d_shp[:, :2])
+            elif c.phot_centroid:
+                o32 = torch.where(((d_pfl & PHOT_NO_CENTROID) == 0)[:, None], c.peaks_off[2], torch.zeros_like(c.peaks_off[2]))
+            else:
+                o32 = torch.zeros((int(ys.size), 2), dtype=torch.float32, device=ctx.device)
+            p32 = (torch.stack([d_x32, d_y32], dim=1).to(torch.float32) + 1.0) + o32.flip(1)
+            d_csky = _astrometry_sky(c, pos=(p32.to(torch.float64) - 1.0).contiguous())
+        rb.add('ast', *c.ast_pending['back'])
+        if d_csky is not None:
+            rb.add('csky', d_csky)
+    return rb, rc
 
-    # ---- sub-images
+
+def _catalogue_measured(c, got, rc):
+    """the host copies of _catalogue_enqueue's copy back -> what _catalogue_table wants, without the peaks on masked pixels ('ok')"""
+    res = c.res
+    if c.ast_pending is not None:
+        c.ast_sol = _ast.solve_finish(c.ast_pending, got['ast'])
+    if c.do_lim:
+        _limflux_finish(c, got.get('lim'))
+    mk, f, e = got['phot']
+    if c.do_match:
+        c.mtab, npairs = got['match']
+        res['ref_catalog'] = rc
+        res['match'] = dict(n_new=int((mk == 0).sum()), n_ref=rc.n, n_pairs=int(npairs[0]))
+    ok = mk == 0
+    m = dict(ok=ok, f=f[ok], e=e[ok], aper=None, csky=got['csky'][0] if 'csky' in got else None)
+    if c.phot_centroid:
+        m['poff'], m['pfl'] = [a[ok] for a in got['centroid']]
+    if c.do_shapes:
+        shp, sfl, m['stab'] = got['shapes']
+        m['shp'], m['sfl'] = shp[ok], sfl[ok]
+    if 'aper' in got:
+        m['aper'] = [a[ok] for a in got['aper'][:4]] + [float(got['aper'][4][0])]
+    return m
+
+
+def _catalogue_of_no_peaks(c):
+    """what _catalogue_table wants for a frame with nothing above the threshold (the registration fails for want of a list)"""
+    if c.do_align:
+        _register_reference(c, None)
+    m = dict(ok=None, f=np.zeros(0, np.float32), e=np.zeros(0, np.float32), shp=np.zeros((0, 8), np.float32), sfl=np.zeros(0, np.uint8),
+             stab=empty_shape_table(c.nsub), poff=np.zeros((0, 2), np.float32), pfl=np.zeros(0, np.uint8), aper=None, csky=None)
+    if c.do_aper:
+        try:
+            na = len(_aper_radii(c.apphot_radii))
+            m['aper'] = [np.zeros((0, na), np.float32), np.zeros((0, na), np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.uint8),
+                         float(fetch(c.ctx, aper_fwhm(c.sub_pn))[0])]
+        except Exception as ex:
+            logging.getLogger(__name__).warning('aperture photometry of the catalogue failed: %s', ex)
+    return m
+
+
+def _catalogue_table(c, ys, xs, pk, m):
+    """res['catalog'] and the header keys of the catalogue and of what rode its copy back (m: _catalogue_measured's dict)"""
+    res, hdr, f, e, aper = c.res, c.hdr, m['f'], m['e'], m['aper']
+    if c.cat_extract:
+        res['catalog'] = dict(Y_POS=ys.astype(np.float32) + 1, X_POS=xs.astype(np.float32) + 1,
+                              E_FLUX_PEAK=pk.astype(np.float32), E_FLUX_OPT=f, E_FLUXERR_OPT=e,
+                              SNR_OPT=np.where(e > 0, f / np.where(e > 0, e, 1), 0).astype(np.float32))
+        hdr['NOBJECTS'] = (len(ys), 'number of objects detected')
+        if c.phot_centroid:
+            # positions as shape_columns forms them: peak + 1 + offset, the integer peak where there is no centroid
+            cen = ((m['pfl'] & PHOT_NO_CENTROID) == 0)[:, None]
+            o = np.where(cen, m['poff'], np.float32(0)).astype(np.float32)
+            res['catalog'].update(Y_POS=(ys.astype(np.float32) + np.float32(1)) + o[:, 0], X_POS=(xs.astype(np.float32) + np.float32(1)) + o[:, 1],
+                                  FLAGS_OPT=m['pfl'].astype(np.uint8))
+    if c.phot_centroid:
+        hdr['PHOT-CEN'] = (True, 'PSF placed on the centroids in the catalogue photometry?')
+    if c.do_shapes:
+        res['catalog'].update(shape_columns(ys, xs, m['shp'], m['sfl']))
+        res['shapes'] = dict(table=m['stab'], n_good=int(m['stab'][c.nsub, _SC['n_fwhm']]))
+        hdr.update(shape_header(m['stab'], len(ys), settings.shape_nmin, settings.pixscale))
+    if c.do_aper and aper is not None:
+        cat = res['catalog']
+        acols = aper_columns(*aper, radii=c.apphot_radii)
+        hdr.update(aper_header(True, aper[4], c.apphot_radii, c.apphot_sky_inout, c.apphot_local_sky, acols, cat['E_FLUX_OPT'], cat['SNR_OPT']))
+        cat.update(acols)
+        res['aper'] = dict(fwhm=aper[4], radii=_aper_radii(c.apphot_radii), n_good=hdr['AP-NSTAR'][0])
+    elif c.do_aper:
+        hdr.update(aper_header(False))
+    ast_sol = c.ast_sol
+    if ast_sol is not None:
+        res['astrometry'] = ast_sol
+        hdr.update(ast_sol['header'])
+        if ast_sol['ok'] and c.cat_extract and m['csky'] is not None:
+            res['catalog'].update(RA=m['csky'][m['ok'], 0].copy(), DEC=m['csky'][m['ok'], 1].copy())
+        elif not ast_sol['ok']:
+            logging.getLogger(__name__).warning('astrometric solve failed: flag word %d (vote %s)', ast_sol['flags'],
+                                                np.asarray(ast_sol['fit']['info']).tolist())
+
+
+def _fake_stars(c):
+    """fake stars: planted in the frame that is about to be cut, behind everything that reads the frame as it was observed ->
+    dict(layout, inj, peaks, noise, radius) of the stars that ride the subtraction; None without the switch or where nothing was planted"""
+    if not (c.fake_stars and int(c.fake_stars) > 0):
+        return None
+    ctx, sub_pn, size = c.ctx, c.sub_pn, c.size
+    fk_noise = settings.fakestar_noise if c.fake_noise is None else bool(c.fake_noise)
+    fk_radius = int(settings.fakestar_radius if c.fake_radius is None else c.fake_radius)
+    fk_prep = None
+    try:
+        # everything that can fail before the frame is touched (fake_prepare): an exception leaves the frame as it is
+        if sub_pn is None:
+            raise ValueError('no PSF stamps of the new frame')
+        if not 0 <= fk_radius <= 4:
+            raise ValueError('fake_radius: 0 .. 4 pixels expected')
+        lay = fake_layout(c.ny, c.nx, size, c.nsy, c.nsx, int(sub_pn.shape[1]), int(c.fake_stars),
+                          settings.fakestar_s2n if c.fake_s2n is None else c.fake_s2n, settings.fakestar_seed if c.fake_seed is None else c.fake_seed)
+        fk_prep = fake_prepare(ctx, c.work, c.ref_side[0], c.bstd, c.new_mask, c.ref_mask if c.ref_grid is None else c.ref_mask_remapped,
+                               c.psf_new, sub_pn, lay, c.nsx, size, clear_half=settings.fake_clear_half,
+                               clear_nsigma=settings.fake_clear_nsigma if c.fake_clear_nsigma is None else c.fake_clear_nsigma,
+                               noise=fk_noise, seed=lay['seed'])
+    except Exception as ex:
+        logging.getLogger(__name__).warning('fake stars were not injected: %s', ex)
+        c.hdr_t.update(fake_header(False))
+    if fk_prep is None:
+        return None
+    # the launch itself is not survived: a frame that may carry stars is never subtracted under T-FKP False
+    fk_inj, fk_peaks = _fake_launch(ctx, fk_prep)
+    return dict(layout=lay, inj=fk_inj, peaks=fk_peaks, noise=fk_noise, radius=fk_radius)
+
+
+def _subtract(c):
+    """the sub-images: their scalars (sigmas, and fratio, dx, dy as given or as the star match measured them), then cut, variance
+    images, ZOGY and stitching on the hand-written path or through rocFFT -> scal [nsub, 6], the match's scalars or None, and on
+    the hand-written path what _zogy_frame_call wants for a second call"""
+    ctx, res, size, border, nsub = c.ctx, c.res, c.size, c.border, c.nsub
+    rwork, rbstd, sdr, sub_pr, frame_path = c.ref_side
     scal = np.zeros((nsub, 6), np.float32)
-    scal[:, 0], scal[:, 1] = scal_n, tile_medians(sdr)
+    scal[:, 0], scal[:, 1] = c.scal_n, _tile_medians(c, sdr)
     # fratio, dx, dy: one number for the frame or one per sub-image (zogy measures them per sub-image from the matched stars)
     ms = None
-    if do_match:
+    if c.do_match:
         # measured here (match=True): per sub-image where it has the pairs, the frame's values elsewhere, the caller's as fallback
-        if mtab is None:
-            mtab = empty_match_table(nsub)
-            res['match'] = dict(n_new=0, n_ref=ref_catalog.n if ref_catalog is not None else 0, n_pairs=0)
-        ms = match_scalars(mtab, fratio, dx, dy, settings.match_nmin if match_nmin is None else match_nmin)
+        if c.mtab is None:
+            c.mtab = empty_match_table(nsub)
+            res['match'] = dict(n_new=0, n_ref=c.ref_catalog.n if c.ref_catalog is not None else 0, n_pairs=0)
+        ms = match_scalars(c.mtab, c.fratio, c.dx, c.dy, settings.match_nmin if c.match_nmin is None else c.match_nmin)
         if not ms['success']:
             logging.getLogger(__name__).warning('star match: %d qualifying pairs in the frame, fewer than the minimum: fratio, dx, dy as given '
-                                                'by the caller', int(mtab[nsub, 0]))
-        res['match'].update(success=ms['success'], table=mtab, fratio_sub=ms['fratio_sub'], dx_sub=ms['dx_sub'], dy_sub=ms['dy_sub'])
+                                                'by the caller', int(c.mtab[nsub, 0]))
+        res['match'].update(success=ms['success'], table=c.mtab, fratio_sub=ms['fratio_sub'], dx_sub=ms['dx_sub'], dy_sub=ms['dy_sub'])
         fratio_in, dx_in, dy_in = ms['fratio_sub'], ms['dx_sub'], ms['dy_sub']
     else:
-        fratio_in, dx_in, dy_in = fratio, dx, dy
+        fratio_in, dx_in, dy_in = c.fratio, c.dx, c.dy
     fr = np.broadcast_to(np.asarray(fratio_in, np.float64), (nsub,))
     scal[:, 2], scal[:, 3] = 1.0, np.where(fr != 0, 1.0 / np.where(fr != 0, fr, 1.0), 1.0)
     scal[:, 4], scal[:, 5] = np.broadcast_to(np.asarray(dx_in, np.float64), (nsub,)), np.broadcast_to(np.asarray(dy_in, np.float64), (nsub,))
+    c.sub_pr = sub_pr
     if frame_path:
         # hand-written FFT path: cut, variance images, ZOGY and stitching in one library call
-        outs = zogy_frame_outputs(work)                           # allocated on the caller's stream, filled inside the gate
-        sub_pn, sub_pr = sub_pn.contiguous(), sub_pr.contiguous()
-        nsig_cand = float(settings.transient_nsigma if nsigma is None else nsigma)
-        rows = ref_rows if ref_rows is not None and ref_rows.matches(rwork, rbstd, size, border) else None
+        outs = zogy_frame_outputs(c.work)                         # allocated on the caller's stream, filled inside the gate
+        c.sub_pn, c.sub_pr = c.sub_pn.contiguous(), sub_pr.contiguous()
+        rows = c.ref_rows if c.ref_rows is not None and c.ref_rows.matches(rwork, rbstd, size, border) else None
         # prepared reference PSF spectra: with prepared rows only, and only where sub_pr is the tensor they were made of
-        rpsf = ref_psf if rows is not None and ref_psf is not None and sub_pr is ref_psf.stamps else None
-
-        def zogy_frame_call():
-            # the kernel that writes Scorr lists the pixels above the transient threshold for the peak search below
-            check(lib.bbx_zogy_candidates(ctx.h, nsig_cand), 'bbx_zogy_candidates', ctx.h)
-            with (zogy_gate or _NoGate()):
-                return run_zogy_frame(ctx, work, rwork, bstd, rbstd, sub_pn, sub_pr, scal, size, border, outs=outs, ref_rows=rows, ref_psf=rpsf)
-        D, _, Scorr, Fpsf, Fpsferr = zogy_frame_call()
+        rpsf = c.ref_psf if rows is not None and c.ref_psf is not None and c.sub_pr is c.ref_psf.stamps else None
+        frame_args = (scal, outs, rows, rpsf)
+        D, _, Scorr, Fpsf, Fpsferr = _zogy_frame_call(c, frame_args)
         res['D'], res['Scorr'], res['Fpsf'], res['Fpsferr'] = D, Scorr, Fpsf, Fpsferr
-    else:
-        Vn = Vn if Vn is not None else variance(ctx, work, bstd)
-        Vr = variance(ctx, rwork, rbstd)
-        subs = [cut_subimages(ctx, a, size, border) for a in (work, rwork, Vn, Vr)]
-        Pn, Pr = embed_psfs(ctx, sub_pn, L), embed_psfs(ctx, sub_pr, L)
-        D, S, Scorr, Fpsf, Fpsferr = run_zogy(ctx, subs[0], subs[1], Pn, Pr, subs[2], subs[3], scal)
-        del subs, Pn, Pr, S, Vr
-        for name, a in (('D', D), ('Scorr', Scorr), ('Fpsf', Fpsf), ('Fpsferr', Fpsferr)):
-            res[name] = stitch_subimages(ctx, a, (ny, nx), size, border)
-    del D, Scorr, Fpsf, Fpsferr
+        return scal, ms, frame_args
+    Vn = variance(ctx, c.work, c.bstd)
+    Vr = variance(ctx, rwork, rbstd)
+    subs = [cut_subimages(ctx, a, size, border) for a in (c.work, rwork, Vn, Vr)]
+    Pn, Pr = embed_psfs(ctx, c.sub_pn, c.L), embed_psfs(ctx, sub_pr, c.L)
+    D, S, Scorr, Fpsf, Fpsferr = run_zogy(ctx, subs[0], subs[1], Pn, Pr, subs[2], subs[3], scal)
+    del subs, Pn, Pr, S, Vr, Vn
+    for name, a in (('D', D), ('Scorr', Scorr), ('Fpsf', Fpsf), ('Fpsferr', Fpsferr)):
+        res[name] = stitch_subimages(ctx, a, (c.ny, c.nx), size, border)
+    return scal, ms, None
 
-    # ---- transient candidates: regions of |Scorr| >= T-NSIGMA, flux = Fpsf at the peak
-    nsig = settings.transient_nsigma if nsigma is None else nsigma
+
+def _zogy_frame_call(c, frame_args):
+    """bbx_zogy_frame on the call's frames and (scal, outs, rows, rpsf): the very ones of the first call when it is repeated"""
+    scal, outs, rows, rpsf = frame_args
+    rwork, rbstd = c.ref_side[:2]
+    # the kernel that writes Scorr lists the pixels above the transient threshold for the peak search below
+    check(lib.bbx_zogy_candidates(c.ctx.h, float(c.nsig)), 'bbx_zogy_candidates', c.ctx.h)
+    with (c.zogy_gate or _NoGate()):
+        return run_zogy_frame(c.ctx, c.work, rwork, c.bstd, rbstd, c.sub_pn, c.sub_pr, scal, c.size, c.border, outs=outs, ref_rows=rows,
+                              ref_psf=rpsf)
+
+
+def _transient_search(c, frame_args):
+    """transient candidates: regions of |Scorr| >= T-NSIGMA -> ys, xs, scorr of the peaks on the host, T-NTRANS"""
+    ctx = c.ctx
     for attempt in (0, 1):
         try:
             # (the first host wait behind bbx_zogy_frame: its device-side checks surface here)
-            tys, txs, tsc = find_peaks_arrays(ctx, res['Scorr'], nsig)
+            tys, txs, tsc = find_peaks_arrays(ctx, c.res['Scorr'], c.nsig)
             ntrans = int(tys.size)
         except _lib_BBXError as e:
-            if e.code == BBX_ERR_PSFWIN and frame_path and attempt == 0:
+            if e.code == BBX_ERR_PSFWIN and frame_args is not None and attempt == 0:
                 # the matched-filter kernels of these PSFs do not fit their row window (include/bbx.h, BBX_OPT_ZOGY_KWIN_OFF):
                 # V(S) of this call is off by more than the tolerance.  Once more on all rows -- the frame keeps its subtraction
                 check(lib.bbx_set_option(ctx.h, BBX_OPT_ZOGY_KWIN_OFF, 1), 'bbx_set_option', ctx.h)
                 try:
-                    zogy_frame_call()
+                    _zogy_frame_call(c, frame_args)
                 finally:
                     check(lib.bbx_set_option(ctx.h, BBX_OPT_ZOGY_KWIN_OFF, 0), 'bbx_set_option', ctx.h)
-                hdr_t['Z-KWIN'] = (False, 'ZOGY matched-filter kernels on a row window?')
+                c.hdr_t['Z-KWIN'] = (False, 'ZOGY matched-filter kernels on a row window?')
                 continue
             if e.code != BBX_ERR_OVERFLOW:
                 raise
@@ -775,49 +903,53 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
             tys = txs = np.zeros(0, np.int32); tsc = np.zeros(0, np.float32)
             ntrans = 'None'
         break
-    # the fluxes at the candidates and the frame statistics of the header: queued together, one copy back, one host wait
+    return tys, txs, tsc, ntrans
+
+
+def _transient_readback(c, scal, fk, tys, txs):
+    """the fluxes at the candidates, the fits, the thumbnails, the frame statistics of the header, the fake stars and the sky
+    positions: queued together, one copy back, one host wait -> {name: [array]} of those that were queued"""
+    ctx, res, hdr_t, new_mask, sub_pn, sub_pr = c.ctx, c.res, c.hdr_t, c.new_mask, c.sub_pn, c.sub_pr
+    rbstd = c.ref_side[1]
     d_fe = d_st = d_fl = None
-    want_thumbs = bool(thumbnails or thumbnail_pngs)
-    tsize = int(thumbnail_size or settings.size_thumbnails)
     if tys.size:
         d_ys, d_xs = push(ctx, tys.astype(np.int64), txs.astype(np.int64))
         d_fe = torch.stack([res['Fpsf'][d_ys, d_xs], res['Fpsferr'][d_ys, d_xs]])
     d_edge = None
-    if tys.size and ref_mask_remapped is not None:
+    if tys.size and c.ref_mask_remapped is not None:
         # the registered reference's mask under every candidate: where it carries the edge bit the frame has no reference, D
         # is the new frame there and every star a candidate
-        d_edge = (ref_mask_remapped[d_ys, d_xs] & settings.mask_value['edge']).to(torch.float32)
+        d_edge = (c.ref_mask_remapped[d_ys, d_xs] & settings.mask_value['edge']).to(torch.float32)
     d_tf = None
-    fit_size = int(settings.trans_fit_size if trans_fit_size is None else trans_fit_size)
-    if trans_psffit:
+    if c.trans_psffit:
         hdr_t['T-PSFD'] = trans_fit_header(False)['T-PSFD']          # until the fit has been read back
-    if trans_psffit and tys.size and sub_pn is not None and sub_pr is not None and tuple(sub_pn.shape) == tuple(sub_pr.shape):
+    if c.trans_psffit and tys.size and sub_pn is not None and sub_pr is not None and tuple(sub_pn.shape) == tuple(sub_pr.shape):
         try:
             d_pd, d_fold = pd_stamps(ctx, sub_pn, sub_pr, scal)
-            fit = _trans_psffit(ctx, res['D'], res['data_bkgsub'], res['ref_bkgsub'], bstd, rbstd, new_mask, d_pd, tys, txs, scal, size, nsx,
-                                fit_size=fit_size)
+            fit = _trans_psffit(ctx, res['D'], res['data_bkgsub'], res['ref_bkgsub'], c.bstd, rbstd, new_mask, d_pd, tys, txs, scal, c.size, c.nsx,
+                                fit_size=c.fit_size)
             d_tf = torch.cat([torch.stack(list(fit[:5]) + [fit[5].to(torch.float32)]).reshape(-1), d_fold])
         except Exception as e:                                       # the frame keeps today's table
             logging.getLogger(__name__).warning('fit of P_D to the transient candidates failed: %s', e)
             d_tf = None
     d_ts = None
-    shape_size = int(settings.trans_shape_size if trans_shape_size is None else trans_shape_size)
-    if trans_shapefit:
+    if c.trans_shapefit:
         hdr_t['T-SHAPE'] = trans_shape_header(False)['T-SHAPE']      # until the fits have been read back
-    if trans_shapefit and tys.size and sub_pn is not None and sub_pr is not None and tuple(sub_pn.shape) == tuple(sub_pr.shape):
+    if c.trans_shapefit and tys.size and sub_pn is not None and sub_pr is not None and tuple(sub_pn.shape) == tuple(sub_pr.shape):
         try:
-            sh_out, sh_fl = _trans_shapefit(ctx, res['D'], res['data_bkgsub'], res['ref_bkgsub'], bstd, rbstd, new_mask,
-                                            shape_start_fwhm(sub_pn, sub_pr), tys, txs, scal, size, nsx, fit_size=shape_size)
+            sh_out, sh_fl = _trans_shapefit(ctx, res['D'], res['data_bkgsub'], res['ref_bkgsub'], c.bstd, rbstd, new_mask,
+                                            shape_start_fwhm(sub_pn, sub_pr), tys, txs, scal, c.size, c.nsx, fit_size=c.shape_size)
             d_ts = torch.cat([sh_out.reshape(-1), sh_fl.to(torch.float32).reshape(-1)])
         except Exception as e:                                       # the frame keeps today's table
             logging.getLogger(__name__).warning('Gauss and Moffat fits to the transient candidates failed: %s', e)
             d_ts = None
-    if want_thumbs:
+    if c.thumbnails or c.thumbnail_pngs:
         # the cut-outs of the four frames, which are all still in HBM, and the mask flags under each peak in one pass; the
         # display planes from the cut-outs.  The reference's mask counts only where it shares the new frame's grid
-        d_fl = thumbnail_stamps(ctx, res, (res['data_bkgsub'], res['ref_bkgsub'], res['D'], res['Scorr']), tys, txs, tsize, new_mask,
-                                ref_mask if ref_grid is None else ref_mask_remapped, floats=thumbnails, pngs=thumbnail_pngs)
-    if frame_stats:
+        d_fl = thumbnail_stamps(ctx, res, (res['data_bkgsub'], res['ref_bkgsub'], res['D'], res['Scorr']), tys, txs,
+                                int(c.thumbnail_size or settings.size_thumbnails), new_mask,
+                                c.ref_mask if c.ref_grid is None else c.ref_mask_remapped, floats=c.thumbnails, pngs=c.thumbnail_pngs)
+    if c.frame_stats:
         # statistics over the unmasked pixels (new frame's mask), clipped like zogy's header values
         d_st = torch.stack([frame_clipped_stats_enqueue(ctx, res['Scorr'], new_mask),
                             frame_clipped_stats_enqueue(ctx, res['Fpsferr'], new_mask)])
@@ -826,116 +958,110 @@ def _optimal_subtraction(ctx, new, ref, new_mask, ref_mask, psf_new, psf_ref, fr
     d_fk = None
     if fk is not None:
         # the stars read back, with what the injection wrote per star: one more tensor in the same copy back
-        d_rec = _fake_recover(ctx, res['Scorr'], res['Fpsf'], res['Fpsferr'], fk['layout'], fk_radius, d_peaks=fk_peaks)
-        d_fk = torch.cat([d_rec.reshape(-1)] + [t.to(torch.float32) for t in fk_inj])
+        d_rec = _fake_recover(ctx, res['Scorr'], res['Fpsf'], res['Fpsferr'], fk['layout'], fk['radius'], d_peaks=fk['peaks'])
+        d_fk = torch.cat([d_rec.reshape(-1)] + [t.to(torch.float32) for t in fk['inj']])
     d_tsky = None
-    if tys.size and ast_sol is not None and ast_sol['ok']:
+    if tys.size and c.ast_sol is not None and c.ast_sol['ok']:
         # the sky positions of the candidates' peaks and, with the fit of P_D, of the fitted positions as X_PSF_D / Y_PSF_D will state
         # them (float32, formed here as catalogs.transient_table does): one more tensor in the same copy back
         t_y32, t_x32 = d_ys.to(torch.int32), d_xs.to(torch.int32)
-        parts = [astrometry_sky(ys=t_y32, xs=t_x32)]
+        parts = [_astrometry_sky(c, ys=t_y32, xs=t_x32)]
         if d_tf is not None:
             pf = torch.stack([t_x32.to(torch.float32) + fit[3], t_y32.to(torch.float32) + fit[2]], dim=1)
-            parts.append(astrometry_sky(pos=((pf.to(torch.float64) + 1.0).to(torch.float32).to(torch.float64) - 1.0).contiguous()))
+            parts.append(_astrometry_sky(c, pos=((pf.to(torch.float64) + 1.0).to(torch.float32).to(torch.float64) - 1.0).contiguous()))
         d_tsky = torch.cat(parts) if all(p is not None for p in parts) else None
-    back = [t for t in (d_fe, d_st, d_fl, d_tf, d_ts, d_edge, d_fk, d_tsky) if t is not None]
-    got = (fetch(ctx, *back) if len(back) > 1 else [fetch(ctx, back[0])]) if back else []
-    fe = got.pop(0) if d_fe is not None else None
-    st = got.pop(0) if d_st is not None else None
-    fl = got.pop(0) if d_fl is not None else None
-    tf = got.pop(0) if d_tf is not None else None
-    ts = got.pop(0) if d_ts is not None else None
-    edge_at = got.pop(0) if d_edge is not None else None
-    if d_fk is not None:
+    rb = Readback()
+    for name, t in (('fe', d_fe), ('stats', d_st), ('flags', d_fl), ('pd', d_tf), ('shapes', d_ts), ('edge', d_edge), ('fake', d_fk),
+                    ('sky', d_tsky)):
+        if t is not None:
+            rb.add(name, t)
+    return {name: a[0] for name, a in rb.fetch(ctx).items()}
+
+
+def _keep_thumbnails(res, keep):
+    """the thumbnails of the rows that stay"""
+    for k in ('thumbnails', 'thumbnail_png8'):
+        if k in res:
+            res[k] = res[k][torch.as_tensor(keep, dtype=torch.int64, device=res[k].device)]
+
+
+def _transient_rows(c, got, fk, tys, txs, tsc):
+    """res['transients'] from the host copies of _transient_readback (the columns: transients.py), the rows that leave with their
+    thumbnails, the header keys of the fits and of the fake stars"""
+    res, hdr_t = c.res, c.hdr_t
+    tf, ts = got.get('pd'), got.get('shapes')
+    if fk is not None:
         nfk = int(fk['layout']['ys'].size)
-        fkh = got.pop(0)
+        fkh = got['fake']
         fk_rec, fk_host = fkh[:6 * nfk].reshape(nfk, 6), [fkh[(6 + j) * nfk:(7 + j) * nfk] for j in range(3)] + [fkh[9 * nfk:].astype(np.uint8)]
         fk_first = np.zeros(0, np.int32)
-    tsky = got.pop(0) if d_tsky is not None else None
     if tys.size:
-        res['transients'] = [dict(y=y, x=x, scorr=sc, fpsf=f, fpsferr=e)
-                             for y, x, sc, f, e in zip(tys.tolist(), txs.tolist(), tsc.tolist(), fe[0].tolist(), fe[1].tolist())]
-        if tsky is not None:
-            n = int(tys.size)
-            for i, d in enumerate(res['transients']):
-                d.update(ra_peak=float(tsky[i, 0]), dec_peak=float(tsky[i, 1]))
-                if len(tsky) == 2 * n:
-                    d.update(ra_psf_d=float(tsky[n + i, 0]), dec_psf_d=float(tsky[n + i, 1]))
-        if fl is not None:
-            for d, v in zip(res['transients'], fl.tolist()):
+        rows = res['transients'] = _tr.candidate_rows(tys, txs, tsc, got['fe'])
+        if 'sky' in got:
+            _tr.sky_columns(rows, got['sky'])
+        if 'flags' in got:
+            for d, v in zip(rows, got['flags'].tolist()):
                 d['flags'] = v
-        if d_fk is not None:
+        if fk is not None:
             # the rows that are fake stars: flagged here, so that every drop below carries the flag along with its row
-            fk_first = fake_match(res['transients'], fk['layout'], fk_radius, flags=fk_host[3])
-            for d, v in zip(res['transients'], fk_first.tolist()):
+            fk_first = fake_match(rows, fk['layout'], fk['radius'], flags=fk_host[3])
+            for d, v in zip(rows, fk_first.tolist()):
                 d['fake_star'] = v
         if tf is not None:
-            n = int(tys.size)
-            cols, fold = tf[:6 * n].reshape(6, n), tf[6 * n:]
-            for i, d in enumerate(res['transients']):
-                d.update(y_psf_d=float(d['y'] + cols[2, i]), x_psf_d=float(d['x'] + cols[3, i]), flux_psf_d=float(cols[0, i]),
-                         fluxerr_psf_d=float(cols[1, i]), chi2_psf_d=float(cols[4, i]), flags_psf_d=int(cols[5, i]))
-            hdr_t.update(trans_fit_header(True, fit_size, res['transients'], fold))
+            fold = _tr.pd_columns(rows, tf)
+            hdr_t.update(trans_fit_header(True, c.fit_size, rows, fold))
             if len(fold) and float(np.max(fold)) > PD_FOLD_WARN:
                 logging.getLogger(__name__).warning('P_D leaves %.3g of its |sum| outside its stamp (T-PDFOLD)', float(np.max(fold)))
         if ts is not None:
-            n = int(tys.size)
-            planes, sfl = ts[:14 * n].reshape(2, 7, n), ts[14 * n:].reshape(2, n)
-            for m, name in enumerate(('gauss', 'moffat')):
-                for i, d in enumerate(res['transients']):
-                    d.update({'x_%s_d' % name: float(d['x'] + planes[m, 1, i]), 'xerr_%s_d' % name: float(planes[m, 3, i]),
-                              'y_%s_d' % name: float(d['y'] + planes[m, 0, i]), 'yerr_%s_d' % name: float(planes[m, 2, i]),
-                              'fwhm_%s_d' % name: float(planes[m, 4, i]), 'elong_%s_d' % name: float(planes[m, 5, i]),
-                              'chi2_%s_d' % name: float(planes[m, 6, i]), 'flags_%s_d' % name: int(sfl[m, i])})
-            hdr_t.update(trans_shape_header(True, shape_size, settings.trans_moffat_beta, res['transients']))
-        if edge_at is not None:
+            _tr.shapefit_columns(rows, ts)
+            hdr_t.update(trans_shape_header(True, c.shape_size, settings.trans_moffat_beta, rows))
+        if 'edge' in got:
             # candidates without a reference under their peak leave, with their thumbnails; T-NTRANS stays the count before
-            keep = [i for i, v in enumerate(edge_at.tolist()) if not v]
-            if len(keep) < len(res['transients']):
-                res['transients'] = [res['transients'][i] for i in keep]
-                for k in ('thumbnails', 'thumbnail_png8'):
-                    if k in res:
-                        res[k] = res[k][torch.as_tensor(keep, dtype=torch.int64, device=res[k].device)]
+            kept, keep = _tr.drop_edge_rows(rows, got['edge'])
+            if len(keep) < len(rows):
+                res['transients'] = kept
+                _keep_thumbnails(res, keep)
             hdr_t['T-NOFFR'] = (int(tys.size) - len(keep), 'candidates dropped: no reference there')
         # the vetting: the chi2 bound needs the fit of P_D, the Gauss bounds the shape fits
-        bounds = dict(chi2_max=trans_chi2_max if tf is not None else None)
-        if ts is not None:
-            bounds.update(fwhm_gauss_min=trans_fwhm_gauss_min, fwhm_gauss_max=trans_fwhm_gauss_max, elong_gauss_max=trans_elong_gauss_max)
-        if any(v is not None for v in bounds.values()):
-            res['transients'], keep = vet_transients(res['transients'], **{k: None if v is None else float(v) for k, v in bounds.items()})
-            for k in ('thumbnails', 'thumbnail_png8'):
-                if k in res:
-                    res[k] = res[k][torch.as_tensor(keep, dtype=torch.int64, device=res[k].device)]
+        kept, keep = _tr.vet_rows(res['transients'], tf is not None, ts is not None, chi2_max=c.trans_chi2_max, fwhm_gauss_min=c.trans_fwhm_gauss_min,
+                                  fwhm_gauss_max=c.trans_fwhm_gauss_max, elong_gauss_max=c.trans_elong_gauss_max)
+        if keep is not None:
+            res['transients'] = kept
+            _keep_thumbnails(res, keep)
             hdr_t['T-NVET'] = (len(keep), 'number of transient candidates that passed the vetting')
     else:
         res['transients'] = []
-    if d_fk is not None:
-        tab = fake_table(fk['layout'], fk_host, fk_rec, nsig, fk_first, [d['fake_star'] for d in res['transients']])
+    if fk is not None:
+        tab = fake_table(fk['layout'], fk_host, fk_rec, c.nsig, fk_first, [d['fake_star'] for d in res['transients']])
         res['fakestars'] = dict(table=tab, layout=fk['layout'])
-        hdr_t.update(fake_header(True, tab, fk['layout'], fk_noise, fk_radius, int((fk_first > 0).sum())))
-    if ref_mask_remapped is not None and 'T-NOFFR' not in hdr_t:
+        hdr_t.update(fake_header(True, tab, fk['layout'], fk['noise'], fk['radius'], int((fk_first > 0).sum())))
+
+
+def _closing_headers(c, scal, ms, st, ntrans):
+    """the Z- and T- keys that close the two headers, and the result's own entries for them (st: the frame statistics, or None)"""
+    res, hdr, hdr_t = c.res, c.hdr, c.hdr_t
+    if c.ref_mask_remapped is not None and 'T-NOFFR' not in hdr_t:
         hdr_t['T-NOFFR'] = (0, 'candidates dropped: no reference there')
     hdr['Z-P'] = (True, 'successfully processed by ZOGY?')
     for h in (hdr, hdr_t):
-        h['Z-SIZE'] = (size, '[pix] size of (square) ZOGY subimages')
-        h['Z-BSIZE'] = (border, '[pix] size of ZOGY subimage borders')
+        h['Z-SIZE'] = (c.size, '[pix] size of (square) ZOGY subimages')
+        h['Z-BSIZE'] = (c.border, '[pix] size of ZOGY subimage borders')
     if ms is not None:
         hdr_t.update(ms['header'])
     else:
-        hdr_t['Z-DX'] = (float(np.median(dx)), '[pix] dx median offset full image')
-        hdr_t['Z-DY'] = (float(np.median(dy)), '[pix] dy median offset full image')
-        hdr_t['Z-FNR'] = (float(np.median(fratio)), 'median flux ratio (Fnew/Fref) full image')
-    if frame_stats:
+        hdr_t['Z-DX'] = (float(np.median(c.dx)), '[pix] dx median offset full image')
+        hdr_t['Z-DY'] = (float(np.median(c.dy)), '[pix] dy median offset full image')
+        hdr_t['Z-FNR'] = (float(np.median(c.fratio)), 'median flux ratio (Fnew/Fref) full image')
+    if c.frame_stats:
         hdr_t['Z-SCMED'] = (float(st[0, 1]), 'median Scorr full image')
         hdr_t['Z-SCSTD'] = (float(st[0, 3]), 'sigma (STD) Scorr full image')
         hdr_t['Z-FPEMED'] = (float(st[1, 1]), '[e-] median Fpsferr full image')
         hdr_t['Z-FPESTD'] = (float(st[1, 3]), '[e-] sigma (STD) Fpsferr full image')
-    hdr_t['T-NSIGMA'] = (float(nsig), '[sigma] transient detection threshold')
+    hdr_t['T-NSIGMA'] = (float(c.nsig), '[sigma] transient detection threshold')
     hdr_t['T-NTRANS'] = (ntrans, 'number of transient candidates')
     res['header'] = _HeaderView(hdr, hdr_t)
     res['header_new'], res['header_trans'] = hdr, hdr_t
     res['scal'] = scal
-    return res
 
 
 class _HeaderView(dict):

@@ -96,6 +96,17 @@ def test_orchestration_stays():
     assert '_trans_psffit' in vars(zogy) and '_trans_shapefit' in vars(zogy) and 'pd_stamps' in vars(zogy)
 
 
+def test_orchestration_is_a_list_of_stage_functions():
+    """_optimal_subtraction calls module-level functions of zogy.py that share one state object: no closure, no nonlocal"""
+    import ast
+    import textwrap
+    assert 'nonlocal' not in open(os.path.join(PKG, 'zogy.py')).read()
+    tree = ast.parse(textwrap.dedent(inspect.getsource(zogy._optimal_subtraction)))
+    nested = [getattr(n, 'name', 'lambda') for n in ast.walk(tree.body[0])
+              if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef, ast.Lambda)) and n is not tree.body[0]]
+    assert nested == []
+
+
 @pytest.mark.parametrize('module', MODULES)
 def test_imports_alone(module):
     """no hidden cycle or order dependence: each module imports first in a fresh interpreter"""
