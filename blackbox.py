@@ -1046,7 +1046,7 @@ class _ListRun:
         # products the frame's QC decided against (red flag: no subtraction products) were queued before the flag
         # was known: take them away again
         for p in group.paths:
-            if p not in getattr(f, 'staged_wanted', set(group.paths)):
+            if f.staged_wanted is not None and p not in f.staged_wanted:       # (None: the hook did not get that far)
                 try:
                     os.unlink(p)
                 except OSError:
@@ -1062,7 +1062,7 @@ class _ListRun:
         try:
             if self.stage is None:
                 self.finish(f, _Products(self.r))
-            self.out[fn] = getattr(f, 'written_name', None)
+            self.out[fn] = f.written_name
         except Exception:
             log.exception('exception was raised during [blackbox_reduce] of %s', fn)
             self.out[fn] = None

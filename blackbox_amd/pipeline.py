@@ -15,6 +15,7 @@ the many short kernels of one frame (flood fill, select, sparse LA-Cosmic steps)
 with the streaming kernels of the next; stage A uses no workspace and overlaps with both.
 No collective, no inter-GPU traffic: one FramePipeline per GPU / process.
 """
+import contextlib
 import ctypes as C
 import multiprocessing as mp
 import os
@@ -30,6 +31,46 @@ from . import reduce as R
 from ._lib import lib, check
 
 get_par = settings.get_par
+
+# The per-frame result record: what the device stage hands the host, in one small buffer that one copy brings back.
+# (name, dtype, count): the 16 channel sigmas | NOBJ-SAT | LA-Cosmic's statistics | the trail count | the mask's pixel counts |
+# the device-side error words per step (reduce.STEP_SLOTS)
+RECORD_FIELDS = (('std', torch.float64, 16), ('nobj', torch.int32, 1), ('stats', torch.int32, 16), ('nsats', torch.int32, 1),
+                 ('cnt6', torch.int64, 6), ('steps', torch.int32, 8))
+
+
+def record_layout(fields=RECORD_FIELDS):
+    """-> ({name: (byte offset, bytes, dtype)}, size of the record: whole 16-byte words)"""
+    where, o = {}, 0
+    for name, dt, n in fields:
+        where[name] = (o, n * dt.itemsize, dt)
+        o += n * dt.itemsize
+    return where, (o + 15) // 16 * 16
+
+
+RECORD_WHERE, RECORD_BYTES = record_layout()
+
+
+def record_views(buf):
+    """{name: typed view} of the record held by the uint8 tensor [buf] (device memory or pinned host memory)"""
+    return {name: buf[o:o + nb].view(dt) for name, (o, nb, dt) in RECORD_WHERE.items()}
+
+
+class RecordParts:
+    """the parts of a record that a frame has, read by name (rec.std, 'nobj' in rec): made[name] is None where the step that
+    fills the part did not run or failed on the host -- that part is absent, and reading it says so"""
+
+    def __init__(self, views, **made):
+        for name, v in views.items():
+            if made.get(name, True) is not None:
+                setattr(self, name, v)
+
+    def __contains__(self, name):
+        return name in self.__dict__
+
+    def __getattr__(self, name):                                     # (reached for what is not there only)
+        raise AttributeError('the frame\'s result record has no part %r%s' % (
+            name, ': its step did not run, or failed on the host' if name in RECORD_WHERE else ''))
 
 
 def cpu_budget():
@@ -225,9 +266,26 @@ def _shm_phase2(args):
 
 
 class _Frame:
-    __slots__ = ('idx', 'raw', 'header', 'hm', 'state', 'evA', 'h_mean', 'h_hos', 'h_ninf', 'res', 'res2',
-                 'evC', 'data', 'mask', 'h_out', 'd_keep', 'p1', 'h_cnt', 'evS', 't0', 'tA', 'tB', 'tC', 'slot', 'lane', 'err',
-                 'sub', 'failed', 'os_ok', 'os_fail', 'out_group', 'out_base', 'out_names', 'written_name', 'staged_wanted')
+    """one frame in flight.  For the caller (on_done, the hooks): idx raw header hm data mask sub failed out_base out_names
+    out_group; written_name and staged_wanted are the caller's own to set"""
+    __slots__ = ('idx', 'raw', 'header', 'hm', 'state', 'slot', 'lane', 'err', 't0', 'tA', 'tB', 'tC',
+                 'evA', 'evS', 'evC', 'h_ninf', 'h_cnt', 'res', 'res2', 'p1', 'os_ok', 'os_fail',
+                 'data', 'mask', 'sub', 'failed', 'h_out', 'd_keep',
+                 'out_group', 'out_base', 'out_names', 'written_name', 'staged_wanted')
+
+    def __init__(self, idx, raw, header):
+        self.idx, self.raw, self.header, self.hm = idx, raw, header, {}
+        self.state, self.slot, self.lane, self.err = None, None, None, None
+        self.t0, self.tA, self.tB, self.tC = time.perf_counter(), None, None, None
+        self.evA = self.evS = self.evC = None                        # the slot's events, once recorded
+        self.h_ninf = self.h_cnt = None                              # pinned host views of stage A's / the column counts' copies
+        self.res = self.res2 = self.p1 = None                        # the host fits: async results, phase-1 results
+        self.os_ok, self.os_fail = None, None                        # overscan solved?  (channel, message) where os_corr raised
+        self.data = self.mask = self.sub = None
+        self.failed = []                                             # steps that failed for this frame
+        self.h_out, self.d_keep = None, None                         # RecordParts of the slot's host record; device tensors in use
+        self.out_group = self.out_base = self.out_names = None       # output stage: the frame's group, product path, file names
+        self.written_name = self.staged_wanted = None
 
 
 class _LaneCtx:
@@ -290,6 +348,58 @@ def _new_event():
     return ev
 
 
+class _RunReference:
+    """what is the same for every frame of a run with one reference, made by the first subtraction that gets there, on
+    whichever lane that is, and handed to every later call: bkg_std, the reference's sigma image; rows, the zogy.RefRows made
+    of it; psf, the zogy.RefPsf of the run's reference PSF (BBX_REF_PSF=0: none); catalog, the zogy.RefCatalog of the star
+    match; stars, the zogy.RefStars of ref_align (the reference's stars on its own grid)"""
+
+    def __init__(self):
+        self.bkg_std = self.rows = self.psf = self.catalog = self.stars = None
+        self.lock = threading.Lock()                                 # one lane makes the products and hands them over
+
+    def kwargs(self, align):
+        """the products as keyword arguments of zogy.optimal_subtraction"""
+        kw = dict(ref_bkg_std=self.bkg_std, ref_rows=self.rows, ref_psf=self.psf, ref_catalog=self.catalog)
+        if align:
+            kw['ref_stars'] = self.stars
+        return kw
+
+    def adopt(self, ctx, sub, subtract, shape, align):
+        """keep what the call that returned [sub] made for the run; subtract: the run's own arguments of the call, shape: the
+        frame's.  The lane's stream has finished with a product (bbx_wait) before another lane can pick it up"""
+        if align and self.stars is None and sub.get('ref_stars') is not None:
+            # the reference's star list on its own grid is the same for every frame of the run (the registered
+            # reference is not: every frame has its own lattice, so nothing below is kept)
+            with self.lock:
+                if self.stars is None:
+                    check(lib.bbx_wait(ctx.h, ctx.sp), 'bbx_wait', ctx.h)
+                    self.stars = sub['ref_stars']
+        if (self.bkg_std is None and subtract.get('ref_is_bkgsub') and subtract.get('ref_bkg_std_mini') is not None
+                and subtract.get('ref_grid') is None and not align and 'bkg_std_ref' in sub):
+            with self.lock:
+                if self.bkg_std is None:
+                    from . import zogy as G
+                    # the reference's sigma image is the same for every frame of the run: made once;
+                    # and so are the row transforms of the reference and of its variance image inside bbx_zogy_frame:
+                    # one buffer (1 GB at full size) for all lanes, where the geometry has the aligned row path
+                    # and the spectra of the reference's PSF (--psf_ref is loaded once per run): one more buffer (505 MB
+                    # at full size) where there are rows; BBX_REF_PSF=0 leaves it out (A/B runs of one build)
+                    rows = rpsf = None
+                    zsize, zborder = sub['header_new']['Z-SIZE'][0], sub['header_new']['Z-BSIZE'][0]
+                    if G.frame_path_supported(zsize + 2 * zborder) and G.RefRows.supported(shape, zsize, zborder):
+                        rows = G.RefRows(ctx, sub['ref_bkgsub'], sub['bkg_std_ref'], zsize, zborder)
+                        if (os.environ.get('BBX_REF_PSF', '1') != '0' and subtract.get('psf_ref') is not None
+                                and G.RefPsf.supported(shape, zsize, zborder)):
+                            rpsf = G.RefPsf(ctx, subtract['psf_ref'], shape, zsize, zborder)
+                    check(lib.bbx_wait(ctx.h, ctx.sp), 'bbx_wait', ctx.h)
+                    # (the star match's catalogue of the reference, where the switch is on: the one this call made of
+                    # the same two tensors)
+                    self.catalog = sub.get('ref_catalog')
+                    self.psf = rpsf
+                    self.rows, self.bkg_std = rows, sub['bkg_std_ref']
+
+
 class FramePipeline:
     def __init__(self, ctx, tel, geom, mflat=None, mbias=None, bpm=None, xtalk_coeffs=None, exptime=60.0,
                  pool=None, depth=4, do_cosmics=True, do_finish=False, accum='f32seq', keep_outputs=False, lanes=2,
@@ -330,20 +440,17 @@ class FramePipeline:
         self.do_cosmics, self.do_finish, self.accum = do_cosmics, do_finish, accum
         self.detect_sats = detect_sats and bool(get_par(settings.detect_sats, tel))
         self.subtract = dict(subtract) if subtract else None
-        # one lane at a time inside bbx_zogy_frame (BBX_ZOGY_GATE=0 switches the gate off)
-        self.ref_bkg_std = None
-        self.ref_rows = None                                         # zogy.RefRows of the run's reference (made with ref_bkg_std)
-        self.ref_psf = None                                          # zogy.RefPsf of the run's reference PSF (made with them; BBX_REF_PSF=0: none)
-        self.ref_catalog = None                                      # zogy.RefCatalog of the run's reference (star match; made with them)
-        self.ref_stars = None                                        # zogy.RefStars of the run's reference (ref_align: its stars on its own grid)
-        self._ref_lock = threading.Lock()                            # one lane makes the two and hands them over
-        self.zogy_gate = None
+        self.ref = _RunReference()
+        self.zogy_gate = None                                        # one lane at a time inside bbx_zogy_frame (BBX_ZOGY_GATE=0: off)
         self.fpack_in_gate = os.environ.get('BBX_FPACK_GATE', '0') == '1'
         if self.subtract and os.environ.get('BBX_ZOGY_GATE', '1') != '0':
             from . import zogy as G
             # (BBX_ZOGY_PRIO=1: the sections on one high-priority stream instead of the lanes' own -- measured in round 3: the
             # section's kernels take 13.5 instead of 7.9 ms per frame in the pipeline and the frame rate drops 2 %)
             self.zogy_gate = G.StreamGate(device=ctx.device, priority=os.environ.get('BBX_ZOGY_PRIO', '0') == '1')
+        # the compression of the frame's images as a section of its own behind the subtraction's (BBX_FPACK_GATE=1): `k_fp_tile`
+        # and the ZOGY kernels each hold a CU's LDS and wave slots in pairs; side by side each runs with half of them
+        self.out_gate = self.zogy_gate if (self.zogy_gate is not None and self.fpack_in_gate) else contextlib.nullcontext()
         self.keep_sub = ('D', 'Scorr', 'Fpsf', 'Fpsferr')        # device products kept on the frame when keep_outputs
         self.log = log
         self.outstage, self.out_base, self.on_written, self.header_hook = outstage, out_base, on_written, header_hook
@@ -387,55 +494,11 @@ class FramePipeline:
         self.lane_cpu = [0.0, 0.0, 0]          # lane threads: CPU seconds, wall seconds inside the device stage, frames
         # staging buffers, one set per frame in flight (pinned host + device), allocated once:
         # pin_memory()/hipHostMalloc costs ~10 ms per call and must stay out of the frame loop
-        dev = ctx.device
         self.arena = ShmArena(depth, self.dy, self.dx, self.hos_rows, self.xsz)
         if not self.arena.register():
             raise RuntimeError('hipHostRegister of the staging arena failed')
         self.layout = self.arena.layout()
-        # per slot: the device mirrors of the arena regions (one copy each way per stage instead
-        # of one per array: a torch copy_ costs ~30 us of the orchestrating thread) and one
-        # packed result record
-        ar = self.arena
-        self.slots = []
-        for i in range(depth):
-            n_in = ar.off['ninf'] + ar.sizes['ninf'] - ar.off['mean']
-            n_vo = ar.off['oscan'] + ar.sizes['oscan'] - ar.off['vfit']
-            d_in = torch.empty(n_in, dtype=torch.uint8, device=dev)
-            d_vo = torch.empty(n_vo, dtype=torch.uint8, device=dev)
-
-            def dv(buf, base, k, dt, shape=None):
-                o = ar.off[k] - ar.off[base]
-                t = buf[o:o + ar.sizes[k]].view(dt)
-                return t.view(shape) if shape else t
-            # std[16] f64 | nobj i32 | stats[16] i32 | nsats i32 | cnt[6] i64 | step error flags [8] i32 (248..280)
-            d_res = torch.zeros(288, dtype=torch.uint8, device=dev)
-            h_res = torch.zeros(288, dtype=torch.uint8, pin_memory=True)
-            h_in_np, h_vo_np = ar.span(i, 'mean', 'ninf'), ar.span(i, 'vfit', 'oscan')
-            h_cnt = torch.empty((2, 16, self.xsz), dtype=torch.int32, pin_memory=True)
-            d_cnt = torch.empty((2, 16, self.xsz), dtype=torch.int32, device=dev)
-            self.slots.append(dict(
-                evA=_new_event(), evS=_new_event(), evC=_new_event(),
-                # (dst, src, nbytes, kind) of the packed copies, for bbx_copy_async
-                cp_in=(C.c_void_p(h_in_np.ctypes.data), R._ptr(d_in), n_in, 1),
-                cp_vo=(R._ptr(d_vo), C.c_void_p(h_vo_np.ctypes.data), n_vo, 0),
-                cp_res=(R._ptr(h_res), R._ptr(d_res), 288, 1),
-                cp_cnt=(R._ptr(h_cnt), R._ptr(d_cnt), h_cnt.numel() * 4, 1),
-                d_in=d_in, h_in=torch.from_numpy(ar.span(i, 'mean', 'ninf')),
-                d_mean=dv(d_in, 'mean', 'mean', torch.float64),
-                d_hos=dv(d_in, 'mean', 'hos', torch.float32, (16, self.hos_rows, self.dx)),
-                d_ninf=dv(d_in, 'mean', 'ninf', torch.int64),
-                h_ninf=torch.from_numpy(ar.view(i, 'ninf')),
-                d_vo=d_vo, h_vo=torch.from_numpy(ar.span(i, 'vfit', 'oscan')),
-                d_vfit=dv(d_vo, 'vfit', 'vfit', torch.float64), d_oscan=dv(d_vo, 'vfit', 'oscan', torch.float64),
-                d_res=d_res, h_res=h_res,
-                d_std=d_res[0:128].view(torch.float64), d_nobj=d_res[128:132].view(torch.int32),
-                d_stats=d_res[132:196].view(torch.int32), d_nsats=d_res[196:200].view(torch.int32),
-                d_cnt6=d_res[200:248].view(torch.int64), d_steps=d_res[248:280].view(torch.int32),
-                d_info=torch.zeros(8, dtype=torch.float32, device=dev), d_med=torch.empty(16, dtype=torch.float32, device=dev),
-                h_std=h_res[0:128].view(torch.float64), h_nobj=h_res[128:132].view(torch.int32),
-                h_stats=h_res[132:196].view(torch.int32), h_nsats=h_res[196:200].view(torch.int32),
-                h_cnt6=h_res[200:248].view(torch.int64), h_steps=h_res[248:280].view(torch.int32),
-                h_cnt=h_cnt, d_cnt=d_cnt))
+        self.slots = [self._new_slot(i) for i in range(depth)]
         # header keys / comments are the same for every frame
         self._k_bias = [[('BIAS{}A{}'.format(c + 1, k), '[e-] channel {} vert. overscan A{} polyfit coeff'.format(c + 1, k))
                          for k in range(settings.voscan_poldeg + 1)] for c in range(16)]
@@ -446,6 +509,50 @@ class FramePipeline:
         # frames still to run with LA-Cosmic's background level prepared in advance (include/bbx.h,
         # BBX_OPT_LAC_LEVEL_FEED); BBX_LAC_FEED_FRAMES sets the start value (0: only after a frame needed it)
         self.level_feed_left = int(os.environ.get('BBX_LAC_FEED_FRAMES', '0'))
+
+    def _new_slot(self, i):
+        """the buffers, packed copies and events of frame-in-flight [i]: the device mirrors of the arena regions (one copy each
+        way per stage instead of one per array: a torch copy_ costs ~30 us of the orchestrating thread) and the result record
+        on the device and in pinned host memory"""
+        ar, dev = self.arena, self.ctx.device
+        n_in = ar.off['ninf'] + ar.sizes['ninf'] - ar.off['mean']
+        n_vo = ar.off['oscan'] + ar.sizes['oscan'] - ar.off['vfit']
+        d_in = torch.empty(n_in, dtype=torch.uint8, device=dev)
+        d_vo = torch.empty(n_vo, dtype=torch.uint8, device=dev)
+
+        def dv(buf, base, k, dt, shape=None):
+            o = ar.off[k] - ar.off[base]
+            t = buf[o:o + ar.sizes[k]].view(dt)
+            return t.view(shape) if shape else t
+        d_res = torch.zeros(RECORD_BYTES, dtype=torch.uint8, device=dev)
+        h_res = torch.zeros(RECORD_BYTES, dtype=torch.uint8, pin_memory=True)
+        h_in_np, h_vo_np = ar.span(i, 'mean', 'ninf'), ar.span(i, 'vfit', 'oscan')
+        h_cnt = torch.empty((2, 16, self.xsz), dtype=torch.int32, pin_memory=True)
+        d_cnt = torch.empty((2, 16, self.xsz), dtype=torch.int32, device=dev)
+        return dict(
+            evA=_new_event(), evS=_new_event(), evC=_new_event(),
+            # (dst, src, nbytes, kind) of the packed copies, for bbx_copy_async
+            cp_in=(C.c_void_p(h_in_np.ctypes.data), R._ptr(d_in), n_in, 1),
+            cp_vo=(R._ptr(d_vo), C.c_void_p(h_vo_np.ctypes.data), n_vo, 0),
+            cp_res=(R._ptr(h_res), R._ptr(d_res), RECORD_BYTES, 1),
+            cp_cnt=(R._ptr(h_cnt), R._ptr(d_cnt), h_cnt.numel() * 4, 1),
+            d_in=d_in, h_in=torch.from_numpy(ar.span(i, 'mean', 'ninf')),
+            d_mean=dv(d_in, 'mean', 'mean', torch.float64),
+            d_hos=dv(d_in, 'mean', 'hos', torch.float32, (16, self.hos_rows, self.dx)),
+            d_ninf=dv(d_in, 'mean', 'ninf', torch.int64),
+            h_ninf=torch.from_numpy(ar.view(i, 'ninf')),
+            d_vo=d_vo, h_vo=torch.from_numpy(ar.span(i, 'vfit', 'oscan')),
+            d_vfit=dv(d_vo, 'vfit', 'vfit', torch.float64), d_oscan=dv(d_vo, 'vfit', 'oscan', torch.float64),
+            d_res=d_res, h_res=h_res, d_rec=record_views(d_res), h_rec=record_views(h_res),
+            d_info=torch.zeros(8, dtype=torch.float32, device=dev), d_med=torch.empty(16, dtype=torch.float32, device=dev),
+            h_cnt=h_cnt, d_cnt=d_cnt)
+
+    # the run's reference products under the names they have always had on the pipeline
+    ref_bkg_std = property(lambda self: self.ref.bkg_std)
+    ref_rows = property(lambda self: self.ref.rows)
+    ref_psf = property(lambda self: self.ref.psf)
+    ref_catalog = property(lambda self: self.ref.catalog)
+    ref_stars = property(lambda self: self.ref.stars)
 
     def close(self):
         lib.bbx_set_option(self.ctx.h, 7, 0)
@@ -461,7 +568,7 @@ class FramePipeline:
                 lib.bbx_event_destroy(sl[k])
         self.slots = []
         self.lane_out = None
-        self.ref_rows = self.ref_psf = self.ref_bkg_std = self.ref_catalog = self.ref_stars = None
+        self.ref = _RunReference()                                   # (the run's reference products go with it)
         self.arena.close()
         for c in self.own_ctx:
             c.close()
@@ -476,8 +583,7 @@ class FramePipeline:
                 or tuple(raw.shape) != (self.geom.ny_raw, self.geom.nx_raw)):
             raise ValueError('frame {}: contiguous device tensor of shape {} expected'.format(
                 idx, (self.geom.ny_raw, self.geom.nx_raw)))
-        f = _Frame()
-        f.idx, f.raw, f.header, f.hm, f.t0, f.err = idx, raw, header, {}, time.perf_counter(), None
+        f = _Frame(idx, raw, header)
         R.gain_corr(header, self.tel)
         f.slot = self.free_slots.pop()
         f.lane = idx % len(self.lane_ctx)
@@ -506,16 +612,19 @@ class FramePipeline:
             tasks = [(self.layout, f.slot, c, self.ysz, self.xsz, settings.voscan_poldeg, self.accum)
                      for c in range(16)]
             f.res = self.pool.submit(_shm_phase1, tasks)
-        f.d_keep = None
         f.state = 'B'
 
-    def _fill_header_vos(self, f, results):
+    def _fill_header_vos(self, f, results, upto=None):
+        """the cards of the vertical fits and their levels; upto: os_corr raised on channel upto - 1 -- the fits of the
+        channels it got to (the levels are the zero overscan's then: reduce.zero_overscan_solution)"""
         h = f.header
-        h['N-INFNAN'] = (int(f.h_ninf.item()), 'number of pixels with infinite/nan values')
-        for c, r in enumerate(results):
-            for (key, comment), v in zip(self._k_bias[c], r['coeffs']):
-                h[key] = (float(v) if np.isfinite(v) else 'None', comment)
-            h[self._k_vfitok[c][0]] = (bool(r['ok']), self._k_vfitok[c][1])
+        for c, r in enumerate(results[:upto]):
+            if upto is None or r.get('coeffs') is not None:
+                for (key, comment), v in zip(self._k_bias[c], r['coeffs']):
+                    h[key] = (float(v) if np.isfinite(v) else 'None', comment)
+                h[self._k_vfitok[c][0]] = (bool(r['ok']), self._k_vfitok[c][1])
+        if upto is not None:
+            return
         mean_vos = np.array([r['level'] for r in results])
         for c in range(16):
             h[self._k_biasm[c][0]] = (float(mean_vos[c]), self._k_biasm[c][1])
@@ -582,59 +691,81 @@ class FramePipeline:
         self.lane_cpu[2] += 1
 
     def _device_stage_on_lane(self, f, results, ctx):
-        geom, tel = self.geom, self.tel
-        sp = ctx.sp
-        h, hm = f.header, f.hm
-        sl = self.slots[f.slot]
-        d_steps = sl['d_steps']
+        """the frame's steps in the order they are queued on the lane's stream; no host wait (but the two once-per-run
+        hand-overs of _RunReference.adopt)"""
         f.failed, f.sub = [], None
-        check(lib.bbx_stream_wait_event(sp, f.evA), 'bbx_stream_wait_event')
-        sol = R.OverscanSolution()
-        d_std = sl['d_std']
+        check(lib.bbx_stream_wait_event(ctx.sp, f.evA), 'bbx_stream_wait_event')
+        sol = self._overscan_solution(f, results, ctx)
+        data, mask, made = self._front_end(f, ctx, sol)
+        if self.subtract is not None:
+            self._subtract(f, ctx, data, mask)
+        if self.outstage is not None:
+            self._submit_outputs(f, ctx, data, mask)
+        if not self.keep_outputs and f.sub is not None:
+            for k in list(f.sub):
+                if torch.is_tensor(f.sub[k]):
+                    del f.sub[k]                                      # device products stay only on request
+        self._queue_record(f, ctx, sol, made)
+        f.data, f.mask = (data, mask) if self.keep_outputs else (None, None)
+        f.state = 'C'
+
+    def _overscan_solution(self, f, results, ctx):
+        """-> the frame's reduce.OverscanSolution on the device; the header cards of the fits, N-INFNAN and OS-P; the channels'
+        read noise into the record -- one branch per outcome of the host fits"""
+        h, geom = f.header, self.geom
+        d_std = self.slots[f.slot]['d_rec']['std']
+        ninf = (int(f.h_ninf.item()), 'number of pixels with infinite/nan values')
+        f.os_ok = results is not None and f.os_fail is None
         if results is None:
-            # the host fits failed: overscan of zero, RDN = 10 (blackbox.py:1537-1585)
-            zs = R.zero_overscan_solution(ctx, h, geom)
-            sol.vfit, sol.oscan, sol.d_vfit, sol.d_oscan = zs.vfit, zs.oscan, zs.d_vfit, zs.d_oscan
-            h['N-INFNAN'] = (int(f.h_ninf.item()), 'number of pixels with infinite/nan values')
+            # the host fits failed as a whole: overscan of zero, RDN = 10 (blackbox.py:1537-1585)
+            sol = R.zero_overscan_solution(ctx, h, geom)
+            h['N-INFNAN'] = ninf
             d_std.fill_(10.0)
-            f.os_ok = False
-        elif getattr(f, 'os_fail', None) is not None:
+        elif f.os_fail is not None:
             # os_corr raised part-way: the crop of the reference's half-processed array (_partial_overscan)
-            k = f.os_fail[0]
-            for c, r in enumerate(results[:k + 1]):
-                if r.get('coeffs') is not None:
-                    for (key, comment), v in zip(self._k_bias[c], r['coeffs']):
-                        h[key] = (float(v) if np.isfinite(v) else 'None', comment)
-                    h[self._k_vfitok[c][0]] = (bool(r['ok']), self._k_vfitok[c][1])
+            self._fill_header_vos(f, results, upto=f.os_fail[0] + 1)
             R.zero_overscan_solution(None, h, geom, header_only=True)
-            h['N-INFNAN'] = (int(f.h_ninf.item()), 'number of pixels with infinite/nan values')
-            sol.vfit, sol.oscan = self.arena.view(f.slot, 'vfit'), self.arena.view(f.slot, 'oscan')
-            sol.d_vfit, sol.d_oscan = sl['d_vfit'], sl['d_oscan']
-            check(lib.bbx_copy_async(*sl['cp_vo'], sp), 'bbx_copy_async')
+            h['N-INFNAN'] = ninf
+            sol = self._arena_solution(f, ctx)
             d_std.fill_(10.0)
-            f.os_ok = False
         else:
+            h['N-INFNAN'] = ninf
             self._fill_header_vos(f, results)
             dlevel = np.float32([r['dlevel'] for r in results])
-            sol.vfit, sol.oscan = self.arena.view(f.slot, 'vfit'), self.arena.view(f.slot, 'oscan')
-            sol.d_vfit, sol.d_oscan = sl['d_vfit'], sl['d_oscan']
-            check(lib.bbx_copy_async(*sl['cp_vo'], sp), 'bbx_copy_async')     # vfit | oscan in one copy
+            sol = self._arena_solution(f, ctx)
             check(lib.bbx_vos_std(ctx.h, C.byref(geom), R._ptr(f.raw), R.raw_type_of(f.raw), self.g32,
-                                  R._ptr(sol.d_vfit), _lib.f32x16(dlevel), R._ptr(d_std), sp),
+                                  R._ptr(sol.d_vfit), _lib.f32x16(dlevel), R._ptr(d_std), ctx.sp),
                   'bbx_vos_std', ctx.h)
-            f.os_ok = True
         h['OS-P'] = (f.os_ok, 'corrected for overscan?')
+        return sol
+
+    def _arena_solution(self, f, ctx):
+        """the vectors the host fits left in the frame's arena slot, on their way to the device: vfit | oscan in one copy"""
+        sl, sol = self.slots[f.slot], R.OverscanSolution()
+        sol.vfit, sol.oscan = self.arena.view(f.slot, 'vfit'), self.arena.view(f.slot, 'oscan')
+        sol.d_vfit, sol.d_oscan = sl['d_vfit'], sl['d_oscan']
+        check(lib.bbx_copy_async(*sl['cp_vo'], ctx.sp), 'bbx_copy_async')
+        return sol
+
+    def _front_end(self, f, ctx, sol):
+        """calibrate ... finish (reduce_object's steps, each closed by its step_mark) -> (data, mask, the device tensors of
+        the record's optional parts: None where the step did not run or its launch failed)"""
+        geom, tel, sp = self.geom, self.tel, ctx.sp
+        h, hm = f.header, f.hm
+        sl = self.slots[f.slot]
+        rec = sl['d_rec']
+        d_steps = rec['steps']
         out = self.lane_out[f.lane] if self.lane_out is not None else None
         data, mask = R.calibrate(ctx, f.raw, sol, h, hm, tel, geom, mbias=self.mbias, mflat=self.mflat, bpm=self.bpm, out=out)
         h['MBIAS-P'] = (self.mbias is not None, 'corrected for master bias?')
         h['MFLAT-P'] = (self.mflat is not None, 'corrected for master flat?')
         R.step_mark(ctx, d_steps, 'calibrate')
         try:
-            d_nobj = R.mask_init_finish(ctx, mask, h, hm, geom, d_n=sl['d_nobj'])
+            d_nobj = R.mask_init_finish(ctx, mask, h, hm, geom, d_n=rec['nobj'])
             h['MASK-P'] = (True, 'mask image created?')
         except _lib.BBXError:
             d_nobj = None
-            h['MASK-P'] = (False, 'mask image created?')
+            R.step_failed(h, hm, 'mask')
         R.step_mark(ctx, d_steps, 'mask')
         d_stats = None
         if self.do_cosmics:
@@ -642,24 +773,23 @@ class FramePipeline:
                 # background level: prepared in advance only while recent frames needed it (st[15])
                 check(lib.bbx_set_option(ctx.h, 1, 1 if self.level_feed_left > 0 else 0), 'bbx_set_option', ctx.h)
                 # RDNOISE = nanmean of the 16 channel sigmas is formed on the device
-                d_stats = R.cosmics_corr(ctx, data, h, mask, hm, tel, d_rdn16=d_std, d_stats=sl['d_stats'])
+                d_stats = R.cosmics_corr(ctx, data, h, mask, hm, tel, d_rdn16=rec['std'], d_stats=rec['stats'])
                 h['COSMIC-P'] = (True, 'corrected for cosmic rays?')
             except _lib.BBXError:
                 d_stats = None
-                f.failed.append('cosmics')
+                f.failed.append('cosmics')                           # (its cards: _finalize, behind the frame's other scalars)
         R.step_mark(ctx, d_steps, 'cosmics')
-        d_cnt = sl['d_cnt6']
         if self.do_finish and self.xtalk is not None:
             try:
                 R.xtalk_corr(ctx, data, self.xtalk, mask, geom)
                 h['XTALK-P'] = (True, 'corrected for crosstalk?')
             except _lib.BBXError:
-                h['XTALK-P'] = (False, 'corrected for crosstalk?')
+                R.step_failed(h, hm, 'xtalk')
         R.step_mark(ctx, d_steps, 'xtalk')
         d_nsats = None
         if self.detect_sats:
             try:
-                d_nsats = sl['d_nsats']
+                d_nsats = rec['nsats']
                 check(lib.bbx_sat_trails(ctx.h, data.shape[0], data.shape[1], R._ptr(data), R._ptr(mask), R.sat_cos_sin(),
                                          R.NTHETA_SAT, *R.sat_gauss_weights(), R._ptr(d_nsats), R._ptr(sl['d_info']), sp),
                       'bbx_sat_trails', ctx.h)
@@ -669,150 +799,110 @@ class FramePipeline:
                 f.failed.append('sat')
         R.step_mark(ctx, d_steps, 'sat')
         if self.do_finish:
-            check(lib.bbx_mask_counts(ctx.h, mask.numel(), R._ptr(mask), R._ptr(d_cnt), sp), 'bbx_mask_counts', ctx.h)
+            check(lib.bbx_mask_counts(ctx.h, mask.numel(), R._ptr(mask), R._ptr(rec['cnt6']), sp), 'bbx_mask_counts', ctx.h)
             check(lib.bbx_edge_fill(ctx.h, C.byref(geom), R._ptr(data), R._ptr(mask), R._ptr(sl['d_med']), sp),
                   'bbx_edge_fill', ctx.h)
         R.step_mark(ctx, d_steps, 'finish')
-        if self.subtract is not None:
-            from . import zogy as G
-            try:
-                align = bool(self.subtract.get('ref_align'))
-                more = dict(ref_stars=self.ref_stars) if align else {}
-                if self.subtract.get('astrometry'):
-                    from . import astrometry
-                    more['ast_pointing'] = astrometry.frame_pointing(h, *self.ast_pointing)
-                sub = G.optimal_subtraction(ctx, data, new_mask=mask, zogy_gate=self.zogy_gate, ref_bkg_std=self.ref_bkg_std,
-                                            ref_rows=self.ref_rows, ref_psf=self.ref_psf, ref_catalog=self.ref_catalog, **more, **self.subtract)
-                if align and self.ref_stars is None and sub.get('ref_stars') is not None:
-                    # the reference's star list on its own grid is the same for every frame of the run (the registered
-                    # reference is not: every frame has its own lattice, so nothing below is kept)
-                    with self._ref_lock:
-                        if self.ref_stars is None:
-                            check(lib.bbx_wait(ctx.h, ctx.sp), 'bbx_wait', ctx.h)
-                            self.ref_stars = sub['ref_stars']
-                if (self.ref_bkg_std is None and self.subtract.get('ref_is_bkgsub') and self.subtract.get('ref_bkg_std_mini') is not None
-                        and self.subtract.get('ref_grid') is None and not align and 'bkg_std_ref' in sub):
-                    with self._ref_lock:
-                        if self.ref_bkg_std is None:
-                            # the reference's sigma image is the same for every frame of the run: made once, on whichever lane
-                            # comes first (its stream has finished with it before any other lane can pick it up: see below);
-                            # and so are the row transforms of the reference and of its variance image inside bbx_zogy_frame:
-                            # one buffer (1 GB at full size) for all lanes, where the geometry has the aligned row path
-                            # and the spectra of the reference's PSF (--psf_ref is loaded once per run): one more buffer (505 MB
-                            # at full size) where there are rows; BBX_REF_PSF=0 leaves it out (A/B runs of one build)
-                            rows = rpsf = None
-                            zsize, zborder = sub['header_new']['Z-SIZE'][0], sub['header_new']['Z-BSIZE'][0]
-                            if G.frame_path_supported(zsize + 2 * zborder) and G.RefRows.supported(data.shape, zsize, zborder):
-                                rows = G.RefRows(ctx, sub['ref_bkgsub'], sub['bkg_std_ref'], zsize, zborder)
-                                if (os.environ.get('BBX_REF_PSF', '1') != '0' and self.subtract.get('psf_ref') is not None
-                                        and G.RefPsf.supported(data.shape, zsize, zborder)):
-                                    rpsf = G.RefPsf(ctx, self.subtract['psf_ref'], data.shape, zsize, zborder)
-                            check(lib.bbx_wait(ctx.h, ctx.sp), 'bbx_wait', ctx.h)
-                            # (the star match's catalogue of the reference, where the switch is on: the one this call made of
-                            # the same two tensors)
-                            self.ref_catalog = sub.get('ref_catalog')
-                            self.ref_psf = rpsf
-                            self.ref_rows, self.ref_bkg_std = rows, sub['bkg_std_ref']
-                for k in ('thumbnails', 'thumbnail_png8'):
-                    # the thumbnails of the transient candidates leave the GPU on this lane, behind the kernels that made them
-                    # (float cut-outs / uint8 display planes: whichever was asked for); the frame's completion reads them
-                    if sub.get(k) is not None:
-                        sub[k + '_host'] = torch.empty(sub[k].shape, dtype=sub[k].dtype, pin_memory=True).copy_(sub[k], non_blocking=True)
-                f.sub = sub
-            except (_lib.BBXError, ValueError) as e:
-                f.failed.append('zogy')
-                if self.log is not None:
-                    self.log.error('frame %d: [optimal_subtraction] failed: %s', f.idx, e)
-            R.step_mark(ctx, d_steps, 'zogy')
-        f.out_group = None
-        if self.outstage is not None:
-            if self.zogy_gate is not None and self.fpack_in_gate:
-                # the compression of the frame's images as a section of its own behind the subtraction's: `k_fp_tile` and the
-                # ZOGY kernels each hold a CU's LDS and wave slots in pairs; side by side each runs with half of them
-                with self.zogy_gate:
-                    self._submit_outputs(f, ctx, data, mask)
-            else:
-                self._submit_outputs(f, ctx, data, mask)
-        if not self.keep_outputs and f.sub is not None:
-            for k in list(f.sub):
-                if torch.is_tensor(f.sub[k]):
-                    del f.sub[k]                                      # device products stay only on request
-        # scalar results: one small pinned D2H of the packed record
-        f.h_out = (sl['h_std'], sl['h_nobj'] if d_nobj is not None else None, sl['h_stats'] if d_stats is not None else None,
-                   sl['h_cnt6'], sl['h_nsats'] if d_nsats is not None else None, sl['h_steps'])
+        return data, mask, dict(nobj=d_nobj, stats=d_stats, nsats=d_nsats)
+
+    def _subtract(self, f, ctx, data, mask):
+        """zogy.optimal_subtraction of the reduced frame on its lane -> f.sub (the result as it is, with pinned host copies
+        of the candidates' thumbnails on their way), or 'zogy' in f.failed"""
+        from . import zogy as G
+        try:
+            align = bool(self.subtract.get('ref_align'))
+            more = self.ref.kwargs(align)
+            if self.subtract.get('astrometry'):
+                from . import astrometry
+                more['ast_pointing'] = astrometry.frame_pointing(f.header, *self.ast_pointing)
+            sub = G.optimal_subtraction(ctx, data, new_mask=mask, zogy_gate=self.zogy_gate, **more, **self.subtract)
+            self.ref.adopt(ctx, sub, self.subtract, data.shape, align)
+            for k in ('thumbnails', 'thumbnail_png8'):
+                # the thumbnails of the transient candidates leave the GPU on this lane, behind the kernels that made them
+                # (float cut-outs / uint8 display planes: whichever was asked for); the frame's completion reads them
+                if sub.get(k) is not None:
+                    sub[k + '_host'] = torch.empty(sub[k].shape, dtype=sub[k].dtype, pin_memory=True).copy_(sub[k], non_blocking=True)
+            f.sub = sub
+        except (_lib.BBXError, ValueError) as e:
+            f.failed.append('zogy')
+            if self.log is not None:
+                self.log.error('frame %d: [optimal_subtraction] failed: %s', f.idx, e)
+        R.step_mark(ctx, self.slots[f.slot]['d_rec']['steps'], 'zogy')
+
+    def _queue_record(self, f, ctx, sol, made):
+        """the frame's scalar results: one small pinned D2H of the packed record, the event the orchestrating thread polls,
+        and what must outlive the stream's work on the frame"""
+        sl = self.slots[f.slot]
+        f.h_out = RecordParts(sl['h_rec'], **made)
         # (by a kernel: the record must not queue behind the output stage's transfers on the copy engines)
-        check(lib.bbx_copy_kernel(sl['cp_res'][0], sl['cp_res'][1], sl['cp_res'][2], sp), 'bbx_copy_kernel')
+        check(lib.bbx_copy_kernel(sl['cp_res'][0], sl['cp_res'][1], sl['cp_res'][2], ctx.sp), 'bbx_copy_kernel')
         f.evC = sl['evC']
-        check(lib.bbx_event_record(f.evC, sp), 'bbx_event_record')
-        f.d_keep = (sol, d_std, d_nobj, d_stats, d_cnt)
-        f.data, f.mask = (data, mask) if self.keep_outputs else (None, None)
-        f.state = 'C'
+        check(lib.bbx_event_record(f.evC, ctx.sp), 'bbx_event_record')
+        f.d_keep = (sol, made)
 
     def _submit_outputs(self, f, ctx, data, mask):
         """queue the frame's image products on this lane for the output stage (no host wait)"""
-        st = self.outstage
-        base = self.out_base(f.idx, f.header)
-        g = st.new_group(f, self._group_done)
-        f.out_group, f.out_base = g, base
-        names = {}
-        names['red'] = st.submit(ctx, g, data, base + '.fits')
-        names['mask'] = st.submit(ctx, g, mask, base.replace('_red', '_mask') + '.fits') if base.endswith('_red') else \
-            st.submit(ctx, g, mask, base + '_mask.fits')
-        sub = f.sub
-        if sub is not None and sub.get('objmask') is not None:
-            names['objmask'] = st.submit(ctx, g, sub['objmask'], base + '_objmask.fits')
-        if sub is not None and sub.get('limflux') is not None and sub['header_new']['LIMMAG-P'][0]:
-            # `_red_limmag` as a flux limit; with a zeropoint the caller makes the image in magnitudes, as for `_trans_limmag`
-            if self.stage_limmag(f.header) if callable(self.stage_limmag) else self.stage_limmag:
+        with self.out_gate:
+            st = self.outstage
+            base = self.out_base(f.idx, f.header)
+            g = st.new_group(f, self._group_done)
+            f.out_group, f.out_base = g, base
+            names = {}
+            names['red'] = st.submit(ctx, g, data, base + '.fits')
+            names['mask'] = st.submit(ctx, g, mask, base.replace('_red', '_mask') + '.fits') if base.endswith('_red') else \
+                st.submit(ctx, g, mask, base + '_mask.fits')
+            sub = f.sub
+            # the caller's say on the limiting-magnitude images, asked once and only of a frame that has one to queue
+            has_lim = sub is not None and sub.get('limflux') is not None and sub['header_new']['LIMMAG-P'][0]
+            stage_lim = (sub is not None and (has_lim or sub.get('D') is not None)
+                         and (self.stage_limmag(f.header) if callable(self.stage_limmag) else self.stage_limmag))
+            if sub is not None and sub.get('objmask') is not None:
+                names['objmask'] = st.submit(ctx, g, sub['objmask'], base + '_objmask.fits')
+            if has_lim and stage_lim:
+                # `_red_limmag` as a flux limit; with a zeropoint the caller makes the image in magnitudes, as for `_trans_limmag`
                 names['red_limmag'] = st.submit(ctx, g, sub['limflux'], base + '_limmag.fits')
-        if sub is not None and sub.get('D') is not None:
-            for ext in ('D', 'Scorr', 'Fpsf'):
-                names[ext] = st.submit(ctx, g, sub[ext], '{}_{}.fits'.format(base, ext))
-            stage_lim = self.stage_limmag(f.header) if callable(self.stage_limmag) else self.stage_limmag
-            if stage_lim:
-                nsig = float(sub['header_trans']['T-NSIGMA'][0])
-                # `_trans_limmag` as a flux limit (no zeropoint on this path): T-NSIGMA x Fpsferr, multiplied by the compression
-                # kernel as it loads Fpsferr (no image of its own)
-                names['limmag'] = st.submit(ctx, g, sub['Fpsferr'], base + '_trans_limmag.fits', scale=nsig)
-        f.out_names = names
-        g.seal()
+            if sub is not None and sub.get('D') is not None:
+                for ext in ('D', 'Scorr', 'Fpsf'):
+                    names[ext] = st.submit(ctx, g, sub[ext], '{}_{}.fits'.format(base, ext))
+                if stage_lim:
+                    nsig = float(sub['header_trans']['T-NSIGMA'][0])
+                    # `_trans_limmag` as a flux limit (no zeropoint on this path): T-NSIGMA x Fpsferr, multiplied by the compression
+                    # kernel as it loads Fpsferr (no image of its own)
+                    names['limmag'] = st.submit(ctx, g, sub['Fpsferr'], base + '_trans_limmag.fits', scale=nsig)
+            f.out_names = names
+            g.seal()
 
     def _group_done(self, g):
         if self.on_written is not None:
             self.on_written(g.token, g)
 
     def _finalize(self, f):
-        h, hm = f.header, f.hm
+        h, hm, out = f.header, f.hm, f.h_out
         if f.os_ok:
-            std = f.h_out[0].numpy()
+            std = out.std.numpy()
             for c in range(16):
                 h[self._k_rdn[c][0]] = (float(std[c]), self._k_rdn[c][1])
             h['RDNOISE'] = (float(np.nanmean(std)), '[e-] average all channel sigmas vert. overscan')
-        if f.h_out[1] is not None:
-            nobj = int(f.h_out[1].item())
+        if 'nobj' in out:
+            nobj = int(out.nobj.item())
             h['NOBJ-SAT'] = hm['NOBJ-SAT'] = (nobj, 'number of saturated objects')
-        if f.h_out[2] is not None:
-            st = f.h_out[2].numpy()
+        if 'stats' in out:
+            st = out.stats.numpy()
             h['NCOSMICS'] = hm['NCOSMICS'] = (float(st[6]) / float(self.exptime), '[/s] number of cosmic rays identified')
             h['NCRPIX'] = (int(st[7]), 'number of cosmic-ray pixels')
             if st[15]:
                 self.level_feed_left = 64             # a frame needed the level: feed it for the next frames
             elif self.level_feed_left > 0:
                 self.level_feed_left -= 1
-        if f.h_out[4] is not None:
-            h['NSATS'] = hm['NSATS'] = (int(f.h_out[4].item()), 'number of satellite trails identified')
+        if 'nsats' in out:
+            h['NSATS'] = hm['NSATS'] = (int(out.nsats.item()), 'number of satellite trails identified')
         if self.do_finish:
-            R.fill_mask_header(hm, f.h_out[3].numpy())
+            R.fill_mask_header(hm, out.cnt6.numpy())
         for step in f.failed:                                    # host-side failures of a step's launch
-            if step == 'cosmics':
-                h['COSMIC-P'] = (False, 'corrected for cosmic rays?')
-                h['NCOSMICS'] = hm['NCOSMICS'] = ('None', '[/s] number of cosmic rays identified')
-            elif step == 'sat':
-                h['SAT-P'] = (False, 'processed for satellite trails?')
-                h['NSATS'] = hm['NSATS'] = ('None', 'number of satellite trails identified')
+            R.step_failed(h, hm, step)
         # device-side error flags per step (bbx_step_mark) -> <STEP>-P False for this frame only
-        f.failed += R.apply_step_errors(h, hm, f.h_out[5].numpy(), self.log)
-        if getattr(f, 'out_group', None) is not None:
+        f.failed += R.apply_step_errors(h, hm, out.steps.numpy(), self.log)
+        if f.out_group is not None:
             # the headers the writers were waiting for: reduction keywords for _red, mask keywords for _mask, reduction +
             # transient keywords for the subtraction images
             hdrs = {None: h, f.out_names['mask']: hm}
@@ -861,7 +951,7 @@ class FramePipeline:
             return self._run(it, live, ndone, exhausted, on_done)
         except BaseException as e:
             for f in live:
-                if getattr(f, 'err', None) is None:
+                if f.err is None:
                     f.err = e
             self._abort(live)
             raise
@@ -870,7 +960,7 @@ class FramePipeline:
         """after an error: let the fit workers and the lanes finish what was queued, drain the streams
         and take all slots back"""
         for f in live:
-            for r in (getattr(f, 'res', None), getattr(f, 'res2', None)):
+            for r in (f.res, f.res2):
                 try:
                     if r is not None:
                         r.wait(30.0)
@@ -889,9 +979,9 @@ class FramePipeline:
         # frames of the output stage that will never be finalised: their writers wait for headers -- tell them
         # (the lanes have drained: every live frame that got as far as _submit_outputs has its group by now)
         for f in live:
-            g = getattr(f, 'out_group', None)
+            g = f.out_group
             if g is not None and not g.header_ready.is_set():
-                g.cancel(getattr(f, 'err', None))
+                g.cancel(f.err)
         self.free_slots = list(range(self.depth))
 
     def _run(self, it, live, ndone, exhausted, on_done):

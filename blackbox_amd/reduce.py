@@ -619,23 +619,41 @@ def zero_overscan_solution(ctx, header, geom, partial=None, header_only=False):
     return sol
 
 
+# step -> (its <STEP>-P flag, the count it would have written or None), each (key, comment); the steps that are not
+# listed have no card of their own
+STEP_FAILED = {
+    'calibrate': (('MASK-P', 'mask image created?'), None),
+    'mask': (('MASK-P', 'mask image created?'), None),
+    'cosmics': (('COSMIC-P', 'corrected for cosmic rays?'), ('NCOSMICS', '[/s] number of cosmic rays identified')),
+    'xtalk': (('XTALK-P', 'corrected for crosstalk?'), None),
+    'sat': (('SAT-P', 'processed for satellite trails?'), ('NSATS', 'number of satellite trails identified')),
+}
+
+
+def step_failed(header, header_mask, step, in_handler=False):
+    """what a failed step leaves in the headers (blackbox.py:1750-1761, 1866-1878, 1897-1912, 1919-1952): <STEP>-P = False,
+    and 'None' where its count would have been.  The one place that says so, for the device-side flags (apply_step_errors),
+    for the pipeline's host-side failures and for reduce_object's handlers.  The callers differ in one respect, kept as it
+    was: after the frame's synchronisation the flag goes in first and the 'None' into both headers; reduce_object's handler
+    of a step that raised (in_handler) writes the 'None' first and into the image header only (the mask header gets no
+    such card there)"""
+    if step not in STEP_FAILED:
+        return
+    (flag, comment), count = STEP_FAILED[step]
+    if count is not None and in_handler:
+        header[count[0]] = ('None', count[1])
+    header[flag] = (False, comment)
+    if count is not None and not in_handler:
+        header[count[0]] = header_mask[count[0]] = ('None', count[1])
+
+
 def apply_step_errors(header, header_mask, errs, log=None):
     """device-side failures of the asynchronous stages (list overflow, non-convergence), read
-    per step after the frame's synchronisation -> the reference's convention (blackbox.py:
-    1750-1761, 1866-1878, 1897-1912, 1919-1952): flag the step, keep going with what there is"""
-    def bad(step):
-        return int(errs[STEP_SLOTS.index(step)]) != 0
-    if bad('calibrate') or bad('mask'):
-        header['MASK-P'] = (False, 'mask image created?')
-    if bad('cosmics'):
-        header['COSMIC-P'] = (False, 'corrected for cosmic rays?')
-        header['NCOSMICS'] = header_mask['NCOSMICS'] = ('None', '[/s] number of cosmic rays identified')
-    if bad('xtalk'):
-        header['XTALK-P'] = (False, 'corrected for crosstalk?')
-    if bad('sat'):
-        header['SAT-P'] = (False, 'processed for satellite trails?')
-        header['NSATS'] = header_mask['NSATS'] = ('None', 'number of satellite trails identified')
-    failed = [s for s in STEP_SLOTS if bad(s)]
+    per step after the frame's synchronisation -> the reference's convention: flag the step
+    (step_failed), keep going with what there is"""
+    failed = [s for i, s in enumerate(STEP_SLOTS) if int(errs[i]) != 0]
+    for s in failed:
+        step_failed(header, header_mask, s)
     if failed and log is not None:
         log.error('device-side error flags %s in step(s) %s', [int(e) for e in errs], failed)
     return failed
@@ -714,7 +732,7 @@ def reduce_object(ctx, raw, header, tel, mflat=None, mbias=None, bpm=None, xtalk
         header['MASK-P'] = (True, 'mask image created?')
     except _lib.BBXError:
         logexc('mask_init')
-        header['MASK-P'] = (False, 'mask image created?')
+        step_failed(header, header_mask, 'mask', in_handler=True)
     step_mark(ctx, d_steps, 'mask')
     d_stats = None
     if crmask_override is not None:
@@ -727,8 +745,7 @@ def reduce_object(ctx, raw, header, tel, mflat=None, mbias=None, bpm=None, xtalk
         except _lib.BBXError:
             logexc('cosmics_corr')
             d_stats = None
-            header['NCOSMICS'] = ('None', '[/s] number of cosmic rays identified')
-            header['COSMIC-P'] = (False, 'corrected for cosmic rays?')
+            step_failed(header, header_mask, 'cosmics', in_handler=True)
     step_mark(ctx, d_steps, 'cosmics')
     if xtalk_coeffs is not None:
         try:
@@ -736,7 +753,7 @@ def reduce_object(ctx, raw, header, tel, mflat=None, mbias=None, bpm=None, xtalk
             header['XTALK-P'] = (True, 'corrected for crosstalk?')
         except (_lib.BBXError, ValueError):
             logexc('xtalk_corr')
-            header['XTALK-P'] = (False, 'corrected for crosstalk?')
+            step_failed(header, header_mask, 'xtalk', in_handler=True)
     step_mark(ctx, d_steps, 'xtalk')
     if stages is not None:
         stages['data_xtalk'] = data.clone()
@@ -748,8 +765,7 @@ def reduce_object(ctx, raw, header, tel, mflat=None, mbias=None, bpm=None, xtalk
         except _lib.BBXError:
             logexc('sat_detect')
             d_nsats = None
-            header['NSATS'] = ('None', 'number of satellite trails identified')
-            header['SAT-P'] = (False, 'processed for satellite trails?')
+            step_failed(header, header_mask, 'sat', in_handler=True)
     step_mark(ctx, d_steps, 'sat')
     mask_header(ctx, mask, header_mask)
     edge_fill(ctx, data, mask, geom)

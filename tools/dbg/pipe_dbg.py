@@ -36,7 +36,7 @@ def main():
         pipe = FramePipeline(ctx, 'ML1', geom, mflat=dev(case['flat']), bpm=dev(case['bpm']), xtalk_coeffs=coeffs, exptime=60.0,
                              pool=pool, depth=3, lanes=lanes, do_finish=True, detect_sats=True, keep_outputs=True, subtract=sub,
                              log=logging.getLogger('p'))
-        pipe.run([(dev(c['raw']), {}) for c in cases], on_done=lambda i, f: print('lanes', lanes, 'frame', i, 'failed', f.failed, 'steps', f.h_out[5].numpy().tolist()))
+        pipe.run([(dev(c['raw']), {}) for c in cases], on_done=lambda i, f: print('lanes', lanes, 'frame', i, 'failed', f.failed, 'steps', f.h_out.steps.numpy().tolist()))
         pipe.close()
     pool.close()
 
